@@ -7,14 +7,24 @@ all-reduce(max) selecting the winner and every rank finalizing E + inlier mask. 
 timed region.  Before the W warm-up steps the script runs enough untimed steps to have done 20 in total, so that short
 invocations (--warmup 3) do not time the clock ramp; the timed region is exactly K steps.  Rank 0 prints ONE JSON line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|c3|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|c3|c4|c5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no RANK in the environment launches the N ranks itself: the parent process
 (which never imports torch and never touches HIP) starts one child per GPU with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*
 set, relays rank 0's JSON line and exits non-zero as soon as any child fails.
 
-What the line carries besides the contract's keys:
+A plain run does only what the headline figure needs: set-up, the untimed wake-up and warm-up steps, ONE timed region of K
+steps and the line (metric, value, unit, higher_is_better, dtype, ms_per_step, the step's result and configuration).
+--dump-outputs DIR writes what the last step of that region computed, as DIR/<name>.npy: E (3 x 3), inlier_mask (one 0 / 1
+per match) and best (hypothesis id, inlier count); for --config c5 records (one 28-float record per view pair, -1 where a
+pair has none) and feature_counts (per view).  The inputs depend only on the arguments, so two builds can be compared
+output for output.
+
+--full adds everything else, as listed below (--regions and the --no-* switches narrow it):
+  ms_per_step_regions       (--regions - 1) more timed regions of K steps, back to back after the contractual one
+  serial_ms_per_step, exchange_us
+                            a region of serial calls after pipelined ones, and the exchange step timed alone
   result.parity_vs_oracle   N = 1: EVERY inlier count of the step's H hypotheses, the arg-max key (first maximum), the winner's
                             E (bit for bit) and the inlier mask against the CPU oracle (oracle/ is the checker, never the path).
                             N > 1: every rank must report nccl_ranks == N and the same (key, E, mask) -- else exit code 1.
@@ -105,7 +115,30 @@ def parse_args(argv=None):
                                                                      "(skipped by itself under rocprofv3 / any preloaded tool)")
     ap.add_argument("--launch-timeout", type=float, default=900.0,
                     help="--gpus N started without a launcher: seconds after which bench.py's own launcher reports every rank's last stage, stops the ranks and exits 124")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the extra timed regions, the serial region, the exchange probe, the roofline's kernel "
+                         "samples, the rank agreement check, the CPU baseline with the oracle parity sweep, the other solver and the other BASELINE configurations "
+                         "(--regions and the --no-* switches apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last step of the (first) timed region computed as DIR/<name>.npy (float32 / float64)")
+    args = ap.parse_args(argv)
+    if not args.full:                   # a plain run: set up, warm up, ONE timed region of K steps, the line
+        args.regions = 1
+        args.no_cpu = args.no_variants = args.no_extra = args.no_exchange_probe = True
+    return args
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: name -> array, written as directory/<name>.npy in float32 (float64 where float32 would round)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype in (np.float64, np.int64, np.uint64, np.uint32) else np.float32)
+        total += a.nbytes
+        assert total <= 64 << 20, "--dump-outputs: more than 64 MB"
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -966,6 +999,10 @@ def rank_main(args):
     elapsed = time.perf_counter() - t0
     solve_ms, score_ms, calls = ctx.kernel_timing_read() if events_in_region else (0.0, 0.0, 0)
     ctx.kernel_timing(False)
+    if args.dump_outputs and rank == 0:                   # what a caller of estimateE receives from the last timed step
+        dh, dc = pair.get_best()
+        dump_outputs(args.dump_outputs, {"E": pair.get_E(), "inlier_mask": pair.get_inlier_mask(),
+                                         "best": np.array([dh, dc], np.float64)})
     # The contractual region above is ONE sample (12 ms at --steps 20).  Four more regions of the same K steps, timed the same way
     # (fence on both sides, no events), say how much one sample is worth: the line carries median / min / max next to it.
     region_s = [elapsed]
@@ -983,7 +1020,7 @@ def rank_main(args):
     main_mask = pair.get_inlier_mask().copy()
     main_E = pair.get_E().copy()
     mask_sum = int(main_mask.sum())
-    if pipelined:
+    if pipelined and args.full:
         # In the timed region consecutive steps overlap on the device, which stretches every kernel's own duration (two
         # launches share the CUs).  The roofline figures describe the kernel, so they come from serial steps: 20 calls of
         # the one-at-a-time entry point right after the timed region, this rank's shard, no exchange.
@@ -1007,7 +1044,7 @@ def rank_main(args):
     #   exchange    world > 1: the 8-byte all-reduce + the finalize behind it, alone, 100 times (what does not shrink with the shard);
     #               world == 1: the same through a one-rank RCCL communicator (a floor: no peer to wait for).
     other_mode = None
-    if pipelined and args.regions > 0:
+    if pipelined and args.full and args.regions > 0:
         ks = max(5, min(args.steps, 50))
         for _ in range(3):
             step(serial=True)
@@ -1019,7 +1056,7 @@ def rank_main(args):
         other_mode = {"mode": "serial", "steps": ks, "seconds": time.perf_counter() - s0}
     xprobe = None
     try:
-        if comm is not None:
+        if comm is not None and args.full:
             xprobe = exchange_probe(S, torch, comm, ctx, pair, n, H, args.kernel, params.jacobi_sweeps, last_seed, world, fence)
         elif world == 1 and not any(args.reserved) and args.regions > 0 and not args.no_exchange_probe and not under_profiler():
             # one rank: the same probe through a one-rank RCCL communicator, in a CHILD process -- the one-GPU line must not depend on
@@ -1050,6 +1087,7 @@ def rank_main(args):
         if xprobe and "seconds" in xprobe:
             xprobe["seconds"] = allv[-1]
         elapsed = region_s[0]
+    if world > 1 and args.full:
         gathered = [None] * world
         dist.all_gather_object(gathered, per_rank[0])
         per_rank = gathered
@@ -1068,7 +1106,7 @@ def rank_main(args):
 
     # one serial call of this rank's own path for the parity check (N = 1: counts of all H hypotheses, key, E, mask)
     serial_result = None
-    if world == 1:
+    if world == 1 and args.full:
         pair.estimateE(params)
         serial_result = (pair.get_inlier_counts(H).copy(), pair.get_key(), pair.get_E().copy(), pair.get_inlier_mask().copy())
         s_hyp, s_cnt = pair.get_best()
@@ -1154,12 +1192,13 @@ def rank_main(args):
                        "nccl_ranks": comm.nccl_ranks() if comm is not None else (world if mode == "torch" else 1),
                        "per_rank_kernel_ms": [{"rank": r, "solve": v[0], "score": v[1], "shader_clock_mhz": v[2]} for r, v in enumerate(per_rank)]},
             "roofline": roofline_block(launch["kernel"], n, local_hyps, score_s, solve_s, clock_mhz, measured_in,
-                                       rule=reserved_rule(args.reserved)),
+                                       rule=reserved_rule(args.reserved)) if args.full else None,
             "result": {"best_hypothesis": hyp, "inliers": cnt, "mask_sum": mask_sum, "sampler_seed_of_this_result": last_seed},
         }
         # which form of the pre-filter the timed steps ran (the first call after a fillXU runs per-hypothesis operands; the wake-up and warm-up
         # steps come before the timed region, so the timed steps run per-tile operands): sfm_ransac_last_prefilter_rule
-        out["roofline"]["operands"] = {2: "per hypothesis (whole-view boxes)", 3: "per (hypothesis, tile) over the ordered copy"}.get(launch.get("prefilter_rule"))
+        if out["roofline"] is not None:
+            out["roofline"]["operands"] = {2: "per hypothesis (whole-view boxes)", 3: "per (hypothesis, tile) over the ordered copy"}.get(launch.get("prefilter_rule"))
         if agree is not None:
             out["result"]["multi_gpu"] = agree
         if variant is not None:
@@ -1283,7 +1322,7 @@ def c5_rank_main(args):
                     pass
             comm = None
             mode = "torch"
-        else:
+        elif args.full:
             tres, tcounts = torch_step()                  # cross-check of the first real multi-rank run: same records from both paths
             same = list(tcounts) == list(first[1]) and sorted(tres) == sorted(first[0]) and all(np.array_equal(tres[k].view(np.uint32), first[0][k].view(np.uint32)) for k in tres)
             xstats["c_path_equals_torch_path"] = bool(same)
@@ -1312,23 +1351,30 @@ def c5_rank_main(args):
     stage("warm-up done, timed regions next")
     steps = args.steps
     region_s = []
+
+    def records(res):                                     # one 28-float record per pair, -1 where a pair has none
+        return np.stack([res[k] if k in res else np.full(28, -1.0, np.float32) for k in range(len(pairs))])
+
     for _ in range(max(1, args.regions)):
         t0 = time.perf_counter()
         for _ in range(steps):
             res, counts = step()
         fence()
         region_s.append(time.perf_counter() - t0)
+        if args.dump_outputs and rank == 0 and len(region_s) == 1:      # what the last step of the contractual region returned
+            dump_outputs(args.dump_outputs, {"records": records(res), "feature_counts": np.asarray(counts, np.float64)})
     stage("timed regions done")
     rc = 0
     if xstats.get("c_path_equals_torch_path") is False:
         print("bench.py: sfm_process_views_sharded and the torch.distributed harness returned different records", file=sys.stderr)
         rc = 1
-    rec = np.stack([res[k] if k in res else np.full(28, -1.0, np.float32) for k in range(len(pairs))])
+    rec = records(res)
     agree = None
     if world > 1:
         t = torch.tensor(region_s, dtype=torch.float64, device=ctl_device(dev))
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         region_s = [float(v) for v in t.cpu().numpy()]
+    if world > 1 and args.full:
         mine = {"rank": rank, "records_sha": hashlib.sha256(rec.tobytes()).hexdigest()[:16], "pairs_done": len(res), "counts_sha": hashlib.sha256(np.asarray(counts, np.int32).tobytes()).hexdigest()[:16],
                 "nccl_ranks": comm.nccl_ranks() if comm is not None else world, "exchange": dict(xstats)}
         allr = [None] * world

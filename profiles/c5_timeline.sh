@@ -3,7 +3,7 @@
 # the LAST step (front end / matcher launches / estimateE + poses), busy time per kernel kind and the gaps between phases.
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $O/c5_trace -o t -- python3 $R/bench.py --config c5 --steps 6 --warmup 3 --regions 1 --no-cpu > $O/c5_timeline_run.txt 2>/dev/null
+rocprofv3 --kernel-trace --output-format csv -d $O/c5_trace -o t -- python3 $R/bench.py --full --config c5 --steps 6 --warmup 3 --regions 1 --no-cpu > $O/c5_timeline_run.txt 2>/dev/null
 cd $R
 python3 - <<PY
 import csv, collections

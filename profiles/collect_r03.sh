@@ -5,13 +5,13 @@ TAG=r03
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O
 cd $R
 # 1. bench lines: the default command (headline + cpu_baseline + variants + extra configs), serial steps, a rank's share
-python3 bench.py > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench.err
-python3 bench.py --serial --no-cpu --no-extra > $O/${TAG}_bench_line_serial.json 2>> $O/${TAG}_bench.err
-python3 bench.py --hyps 131072 --no-cpu --no-variants --no-extra > $O/${TAG}_bench_rank8.json 2>> $O/${TAG}_bench.err
-python3 bench.py --hyps 131072 --serial --no-cpu --no-variants --no-extra > $O/${TAG}_bench_rank8_serial.json 2>> $O/${TAG}_bench.err
-python3 bench.py --config c4 --hyps 131072 --no-cpu --no-variants --no-extra > $O/${TAG}_bench_c4_rank8.json 2>> $O/${TAG}_bench.err
-python3 bench.py --config c3 --steps 200 --no-cpu --no-variants --no-extra > $O/${TAG}_bench_c3.json 2>> $O/${TAG}_bench.err
-python3 bench.py --config c4 --steps 30 --warmup 5 --no-cpu --no-variants --no-extra > $O/${TAG}_bench_c4.json 2>> $O/${TAG}_bench.err
+python3 bench.py --full > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench.err
+python3 bench.py --full --serial --no-cpu --no-extra > $O/${TAG}_bench_line_serial.json 2>> $O/${TAG}_bench.err
+python3 bench.py --full --hyps 131072 --no-cpu --no-variants --no-extra > $O/${TAG}_bench_rank8.json 2>> $O/${TAG}_bench.err
+python3 bench.py --full --hyps 131072 --serial --no-cpu --no-variants --no-extra > $O/${TAG}_bench_rank8_serial.json 2>> $O/${TAG}_bench.err
+python3 bench.py --full --config c4 --hyps 131072 --no-cpu --no-variants --no-extra > $O/${TAG}_bench_c4_rank8.json 2>> $O/${TAG}_bench.err
+python3 bench.py --full --config c3 --steps 200 --no-cpu --no-variants --no-extra > $O/${TAG}_bench_c3.json 2>> $O/${TAG}_bench.err
+python3 bench.py --full --config c4 --steps 30 --warmup 5 --no-cpu --no-variants --no-extra > $O/${TAG}_bench_c4.json 2>> $O/${TAG}_bench.err
 # 2. A/B on the same box: round-3 kernel against the round-2 kernel, static pass order, stand-alone prep
 sh profiles/pf_ab.sh $O/${TAG}_pf_ab.txt > /dev/null 2>&1
 python3 profiles/trace_probe.py > $O/${TAG}_trace.txt 2>/dev/null
@@ -28,11 +28,11 @@ python3 profiles/prefilter_soak.py 300 41 > $O/${TAG}_prefilter_soak.txt 2>/dev/
 cd /tmp && export TMPDIR=/tmp
 for cfg in "headline:" "c3:--config c3" "c4:--config c4 --steps 30 --warmup 5" "rank8:--hyps 131072"; do
   name=${cfg%%:*}; args=${cfg#*:}
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats_$name -o bench -- python3 $R/bench.py --serial --no-cpu --no-variants --no-extra $args > /dev/null 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats_$name -o bench -- python3 $R/bench.py --full --serial --no-cpu --no-variants --no-extra $args > /dev/null 2>&1
   cp $O/${TAG}_stats_$name/bench_kernel_stats.csv $O/${TAG}_bench_${name}_kernel_stats.csv
   rm -rf $O/${TAG}_stats_$name
 done
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats_pipe -o bench -- python3 $R/bench.py --no-cpu --no-variants --no-extra > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats_pipe -o bench -- python3 $R/bench.py --full --no-cpu --no-variants --no-extra > /dev/null 2>&1
 cp $O/${TAG}_stats_pipe/bench_kernel_stats.csv $O/${TAG}_bench_pipelined_kernel_stats.csv; rm -rf $O/${TAG}_stats_pipe
 # 5. counters (separate passes): headline, c4, the round-2 kernel on the headline
 cd $R

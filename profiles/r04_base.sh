@@ -5,7 +5,7 @@ OUT=${1:-$O/r04_base.txt}
 : > $OUT
 run() {  # label, args...
   L="$1"; shift
-  python3 bench.py --no-cpu --no-variants --no-extra "$@" 2>>$O/r04_base.err | python3 -c "
+  python3 bench.py --full --no-cpu --no-variants --no-extra "$@" 2>>$O/r04_base.err | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('%-36s ms_per_step %.4f score %.4f solve %.4f frac %.3f clock %4.0f best %s' % ('$L', d['ms_per_step'], r['avg_launch_ms'], r['solve_kernel_avg_ms'], r['frac'], r['shader_clock_mhz'], d['result']))" >> $OUT

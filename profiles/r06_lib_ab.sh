@@ -5,7 +5,7 @@ OUT=${1:-$O/r06_lib_ab.txt}
 : > $OUT
 run() {  # label, libdir, args...
   L="$1"; D="$2"; shift; shift
-  SFM_AMD_LIB_DIR=$D python3 bench.py --no-cpu --no-variants --no-extra --no-exchange-probe --regions 1 "$@" 2>>$O/r06_lib_ab.err | python3 -c "
+  SFM_AMD_LIB_DIR=$D python3 bench.py --full --no-cpu --no-variants --no-extra --no-exchange-probe --regions 1 "$@" 2>>$O/r06_lib_ab.err | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('%-34s ms_per_step %.4f score %.4f solve %.4f clock %4.0f kcycles %.1f best %s' % ('$L', d['ms_per_step'], r['avg_launch_ms'], r['solve_kernel_avg_ms'], r['shader_clock_mhz'], r['avg_launch_ms']*r['shader_clock_mhz'], d['result']['inliers']))" >> $OUT

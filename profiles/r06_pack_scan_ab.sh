@@ -1,6 +1,6 @@
 for r in "0 0 0 0" "0 0 0 6" "0 0 0 5" "0 0 0 0" "0 0 0 6" "0 0 0 5"; do
   echo "== reserved $r"
-  timeout 300 python bench.py --no-extra --no-variants --cpu-seconds 3 --reserved $r 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --no-extra --no-variants --cpu-seconds 3 --reserved $r 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

@@ -3,7 +3,7 @@
 # and round 5's alignbit scan (reserved[3] = 5): headline, serial, a rank's share, c3, c4 -- lab-bench library, one box
 run() {
   echo "== $*"
-  timeout 300 python bench.py --no-extra --no-variants --no-cpu --no-exchange-probe --regions 1 "$@" 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --no-extra --no-variants --no-cpu --no-exchange-probe --regions 1 "$@" 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

@@ -2,7 +2,7 @@
 # Round 6: 16-byte ring entries that cover four steps (reserved[1] = 13) against the product's 8-byte entries per two steps; lab-bench library, one box
 run() {
   echo "== $*"
-  timeout 300 python bench.py --no-extra --no-variants --no-exchange-probe --regions 1 --cpu-seconds 2 "$@" 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --no-extra --no-variants --no-exchange-probe --regions 1 --cpu-seconds 2 "$@" 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

@@ -72,7 +72,7 @@ def test_bench_multi_rank_flow_on_one_gpu(mode):
     ranks sharing the one GPU: the pipelined and the serial C exchange and the torch.distributed exchange; the line must say
     two ranks, the ranks must agree on winner, E and mask, and the winner must be the one-GPU winner of the same workload.
     (The numbers mean nothing here: two ranks time-share one GPU.)"""
-    rec = _run_bench_ranks(2, ["--steps", "3", "--warmup", "1", "--regions", "2", "--hyps", "65536", "--no-cpu", "--no-variants", "--no-extra"] + mode)
+    rec = _run_bench_ranks(2, ["--full", "--steps", "3", "--warmup", "1", "--regions", "2", "--hyps", "65536", "--no-cpu", "--no-variants", "--no-extra"] + mode)
     assert rec["n_gpus"] == 2 and rec["steps"] == 3 and rec["value"] > 0 and rec["unit"] == "hypotheses/s"
     mg = rec["result"]["multi_gpu"]
     assert mg["ranks_agree_on_winner_E_mask"] and mg["communicator_spans_all_ranks"] and len(mg["per_rank"]) == 2
@@ -92,11 +92,32 @@ def test_bench_multi_rank_flow_on_one_gpu(mode):
     assert rec["serial_ms_per_step"] > 0 and (mode != [] or rec["exchange_us"] > 0)
 
 
+def test_bench_plain_two_ranks_dump_the_one_gpu_result(tmp_path):
+    """A plain two-rank run (no --full): one timed region, and rank 0 dumps the winner, E and mask every rank holds after the exchange --
+    those of one estimateE of the same step on one GPU."""
+    out = tmp_path / "outputs"
+    rec = _run_bench_ranks(2, ["--steps", "3", "--warmup", "1", "--hyps", "65536", "--dump-outputs", str(out)])
+    assert rec["n_gpus"] == 2 and rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["ms_per_step_regions"]["regions"] == 1
+    import cuda_sfm_amd as S
+    from cuda_sfm_amd import synth
+    import numpy as np
+    import torch
+    dev = torch.device("cuda", 0)
+    ctx = S.Context(0, torch.cuda.current_stream().cuda_stream)
+    scene = synth.two_view_scene(4096)
+    pair = S.ImagePair(ctx, scene["K"], scene["Kinv"], 2, 4096)
+    pair.fillXU(torch.from_numpy(scene["sift"].view(np.uint8).reshape(4096, 576)).to(dev))
+    pair.estimateE(S.default_params(4096, num_hypotheses=65536, seed=rec["result"]["sampler_seed_of_this_result"]))
+    assert np.load(out / "best.npy").tolist() == list(pair.get_best())
+    assert np.array_equal(np.load(out / "E.npy").view(np.uint32), pair.get_E().view(np.uint32))
+    assert np.array_equal(np.load(out / "inlier_mask.npy"), pair.get_inlier_mask().astype(np.float32))
+
+
 def test_bench_c5_two_ranks_on_one_gpu():
     """configs[4] as the bench job, two ranks on one GPU through sfm_process_views_sharded: 36 dino views dealt over the ranks,
     the count-sized exchange, all 630 pairs; the records must be the one-rank records (the job checks them against the oracle
     chain on rank 0 when asked; here: every pair done, the exchange moved what exists)."""
-    rec = _run_bench_ranks(2, ["--config", "c5", "--steps", "1", "--warmup", "1", "--regions", "1", "--no-cpu", "--comm", "rccl"], timeout=1200)
+    rec = _run_bench_ranks(2, ["--full", "--config", "c5", "--steps", "1", "--warmup", "1", "--regions", "1", "--no-cpu", "--comm", "rccl"], timeout=1200)
     assert rec["n_gpus"] == 2 and rec["result"]["pairs_done"] == 630
     assert rec["config"]["nccl_ranks"] == 2
     ex = rec["exchange"]
@@ -111,7 +132,7 @@ def test_bench_under_torch_distributed_run_on_one_gpu(nproc):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, SFM_AMD_COMM_LIB=FAKE, SFM_BENCH_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "3", "--warmup", "1", "--regions", "1", "--hyps", "65536", "--no-variants"]
+           os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--full", "--steps", "3", "--warmup", "1", "--regions", "1", "--hyps", "65536", "--no-variants"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -129,7 +150,7 @@ def test_bench_own_launcher_on_one_gpu():
     env = dict(os.environ, SFM_AMD_COMM_LIB=FAKE, SFM_BENCH_DIST_BACKEND="gloo")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--regions", "1", "--hyps", "65536",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--regions", "1", "--hyps", "65536",
                         "--no-variants"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
