@@ -49,8 +49,8 @@ PREFILTER_PER_HYPOTHESIS, PREFILTER_PER_TILE = 2, 3      # sfm_ransac_last_prefi
 MATCH_AUTO, MATCH_EXACT, MATCH_PREFILTER, MATCH_FUSED = 0, 1, 2, 3
 POSE_REFERENCE, POSE_CORRECT = 0, 1
 (BUF_X0, BUF_X1, BUF_U0, BUF_U1, BUF_E, BUF_P, BUF_PINV, BUF_POINTS, BUF_COUNTS, BUF_MASK, BUF_KEY,
- BUF_ECAND, BUF_PIND, BUF_REFINED_POSE, BUF_REFINED_POINTS, BUF_REPROJ) = range(16)
-REFINE_CONVERGED, REFINE_MAX_ITER, REFINE_DEGENERATE = 0, 1, 2         # sfm_refine_report.status
+ BUF_ECAND, BUF_PIND, BUF_REFINED_POSE, BUF_REFINED_POINTS, BUF_REPROJ, BUF_VIEW_POSE, BUF_VIEW_COUNTS, BUF_VIEW_REPROJ) = range(19)
+REFINE_CONVERGED, REFINE_MAX_ITER, REFINE_DEGENERATE = 0, 1, 2         # sfm_refine_report.status, sfm_register_report.status
 
 SIFT_DTYPE = np.dtype([
     ("xpos", "<f4"), ("ypos", "<f4"), ("scale", "<f4"), ("sharpness", "<f4"),
@@ -74,6 +74,8 @@ EXPORTS = [
     "sfm_ransac_last_launch", "sfm_ransac_last_clock", "sfm_ransac_last_prefilter_rule", "sfm_process_pairs", "sfm_ctx_last_pairs_batched", "sfm_extract_views", "sfm_extract_views_u8",
     "sfm_refine_default_params", "sfm_refine_two_view", "sfm_get_refine_report", "sfm_get_refined_pose", "sfm_get_refined_points",
     "sfm_get_reprojection_errors",
+    "sfm_register_default_params", "sfm_register_view", "sfm_get_register_report", "sfm_get_view_pose", "sfm_get_view_errors",
+    "sfm_get_view_counts",
 ]
 AB_EXPORTS = ["sfm_ransac_last_phases", "sfm_ransac_last_trace", "sfm_prefilter_probe", "sfm_prefilter_band_probe"]      # include/sfm_amd_ab.h
 if AB:
@@ -100,6 +102,21 @@ class RefineReport(C.Structure):
     _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("accepted", C.c_int32), ("num_used", C.c_int32),
                 ("pose_index", C.c_int32), ("initial_rms_px", C.c_float), ("final_rms_px", C.c_float),
                 ("final_cost", C.c_float), ("lambda", C.c_float)]
+
+
+class RegisterParams(C.Structure):
+    """sfm_register_params (include/sfm_amd.h)."""
+    _fields_ = [("num_hypotheses", C.c_uint32), ("seed", C.c_uint32), ("threshold_px", C.c_float), ("min_score", C.c_float),
+                ("max_ambiguity", C.c_float), ("max_iterations", C.c_int32), ("huber_px", C.c_float),
+                ("min_rel_decrease", C.c_float), ("initial_lambda", C.c_float), ("d_points", C.c_void_p), ("d_valid", C.c_void_p),
+                ("reserved", C.c_int32 * 4)]
+
+
+class RegisterReport(C.Structure):
+    """sfm_register_report (include/sfm_amd.h)."""
+    _fields_ = [("status", C.c_int32), ("num_candidates", C.c_int32), ("ransac_inliers", C.c_int32), ("num_inliers", C.c_int32),
+                ("best_hypothesis", C.c_uint32), ("iterations", C.c_int32), ("accepted", C.c_int32),
+                ("initial_rms_px", C.c_float), ("final_rms_px", C.c_float), ("final_cost", C.c_float), ("lambda", C.c_float)]
 
 
 _vp = C.c_void_p
@@ -174,6 +191,13 @@ _lib.sfm_get_refine_report.argtypes = [_vp, C.POINTER(RefineReport)]
 _lib.sfm_get_refined_pose.argtypes = [_vp, _vp, _vp]
 _lib.sfm_get_refined_points.argtypes = [_vp, _vp]
 _lib.sfm_get_reprojection_errors.argtypes = [_vp, _vp, _vp]
+_lib.sfm_register_default_params.argtypes = [C.POINTER(RegisterParams)]
+_lib.sfm_register_default_params.restype = None
+_lib.sfm_register_view.argtypes = [_vp, _vp, C.POINTER(RegisterParams)]
+_lib.sfm_get_register_report.argtypes = [_vp, C.POINTER(RegisterReport)]
+_lib.sfm_get_view_pose.argtypes = [_vp, _vp, _vp]
+_lib.sfm_get_view_errors.argtypes = [_vp, _vp, _vp]
+_lib.sfm_get_view_counts.argtypes = [_vp, _vp]
 if AB:
     _lib.sfm_ransac_last_phases.argtypes = [_vp, C.POINTER(C.c_uint64)]
     _lib.sfm_ransac_last_trace.argtypes = [_vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_size_t)]
@@ -227,6 +251,24 @@ def refine_params(**kw):
     for k, v in kw.items():
         if k in ("mask", "d_mask"):
             p.d_mask = _ptr(v)
+        elif k == "reserved":
+            for i, x in enumerate(v):
+                p.reserved[i] = int(x)
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def register_params(**kw):
+    """sfm_register_params with the library's defaults (4096 hypotheses, 4 px, gate 0.85 / 0.95, 10 iterations, Huber 1 px,
+    1e-6, lambda 1e-3), fields overridden by kw (points / valid: device tensors / pointers)."""
+    p = RegisterParams()
+    _lib.sfm_register_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k in ("points", "d_points"):
+            p.d_points = _ptr(v)
+        elif k in ("valid", "d_valid"):
+            p.d_valid = _ptr(v)
         elif k == "reserved":
             for i, x in enumerate(v):
                 p.reserved[i] = int(x)
@@ -533,6 +575,41 @@ class ImagePair:
         err = np.empty(self.num_points, np.float32); used = np.empty(self.num_points, np.uint8)
         _check(_lib.sfm_get_reprojection_errors(self._h, err.ctypes.data_as(_vp), used.ctypes.data_as(_vp)), "sfm_get_reprojection_errors")
         return err, used
+
+    # -- registering a further view against the pair's 3-D points -----------------------------------------
+    def register_enqueue(self, d_sift, params):
+        """sfm_register_view with a RegisterParams (enqueue only)."""
+        _check(_lib.sfm_register_view(self._h, _ptr(d_sift), C.byref(params)), "sfm_register_view")
+
+    def register_view(self, d_sift, **kw):
+        """P3P RANSAC + pose LM of a further view: d_sift holds view 1's records re-matched against it (Context.match); kw are
+        RegisterParams fields (points / valid: device tensors; None = the refined points).  Returns the report (synchronises)."""
+        self.register_enqueue(d_sift, register_params(**kw))
+        return self.get_register_report()
+
+    def get_register_report(self):
+        r = RegisterReport()
+        _check(_lib.sfm_get_register_report(self._h, C.byref(r)), "sfm_get_register_report")
+        return {f: getattr(r, f) for f, _ in RegisterReport._fields_}
+
+    def get_view_pose(self):
+        """(refined P 4x4, RANSAC P 4x4), both [R3|t3; 0 0 0 1] with X3 = R3 X + t3."""
+        P = np.empty((4, 4), np.float32); Pr = np.empty((4, 4), np.float32)
+        _check(_lib.sfm_get_view_pose(self._h, P.ctypes.data_as(_vp), Pr.ctypes.data_as(_vp)), "sfm_get_view_pose")
+        return P, Pr
+
+    def get_view_errors(self):
+        """(err float32[num_points] px, +inf for non-candidates; inlier uint8[num_points])."""
+        err = np.empty(self.num_points, np.float32); inl = np.empty(self.num_points, np.uint8)
+        _check(_lib.sfm_get_view_errors(self._h, err.ctypes.data_as(_vp), inl.ctypes.data_as(_vp)), "sfm_get_view_errors")
+        return err, inl
+
+    def get_view_counts(self):
+        """Inlier count of every hypothesis of the last registration."""
+        _, nbytes = self.device_ptr(BUF_VIEW_COUNTS)
+        out = np.empty(nbytes // 4, np.int32)
+        _check(_lib.sfm_get_view_counts(self._h, out.ctypes.data_as(_vp)), "sfm_get_view_counts")
+        return out
 
     # -- accessors --------------------------------------------------------------------------------
     def device_ptr(self, which):

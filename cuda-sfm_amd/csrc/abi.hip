@@ -486,6 +486,7 @@ int sfm_pair_reset(sfm_pair *pair, int num_points)
     pair->ld = round_up(num_points, 128);
     pair->have_points = pair->have_E = pair->have_P = pair->have_pose = pair->have_points3d = false;
     pair->have_refined = false;
+    pair->have_view = false;
     pair->last_count = 0;
     return SFM_OK;
 }
@@ -497,7 +498,7 @@ int sfm_pair_destroy(sfm_pair *p)
     void *bufs[] = { p->d_K, p->d_Kinv, p->d_U[0], p->d_U[1], p->d_X[0], p->d_X[1], p->d_pts4, p->d_E, p->d_P, p->d_Pinv, p->d_Pind,
                      p->d_points, p->d_mask, p->d_key, p->d_best, p->d_counts, p->d_Ecand, p->d_clk, p->d_tick,
                      p->alt_counts, p->alt_Ecand, p->alt_tick, p->alt_key, p->d_pf, p->alt_pf, p->d_bound, p->d_cells, p->d_pts4s, p->d_tile_boxes, p->d_buckets,
-                     p->d_rstate, p->d_rpoints, p->d_rreproj, p->d_rwork };
+                     p->d_rstate, p->d_rpoints, p->d_rreproj, p->d_rwork, p->d_vstate, p->d_vreproj, p->d_vwork, p->d_vhyp, p->d_vcounts };
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (p->pipe_stream) { (void)hipStreamSynchronize(p->pipe_stream); (void)hipStreamDestroy(p->pipe_stream); }
     for (hipEvent_t e : p->pipe_final) if (e) (void)hipEventDestroy(e);
@@ -519,6 +520,7 @@ int sfm_fill_xu(sfm_pair *pair, const sfm_sift_point *d_data)
     if (rc == SFM_OK) {
         pair->have_points = true; pair->have_E = pair->have_P = pair->have_pose = pair->have_points3d = false; pair->last_count = 0;
         pair->have_refined = false;
+        pair->have_view = false;
         pair->key_clean = true;             // fill_xu_kernel zeroes d_key
         // X_z = fma(Kinv[8], 1, fma(Kinv[7], y, Kinv[6] * x)) is exactly 1 for finite pixel coordinates when
         // the last row of K^-1 is (0 0 1): the scoring kernel may then drop z (ransac_device.hpp)
@@ -535,7 +537,7 @@ int sfm_set_points(sfm_pair *pair, const float *d_X0, const float *d_X1)
     if (pair->pipe_pending) { const int rcf = sfm_pair_flush(pair); if (rcf != SFM_OK) return rcf; }
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
     int rc = launch_set_points(pair, d_X0, d_X1);
-    if (rc == SFM_OK) { pair->have_points = true; pair->have_E = pair->have_P = pair->have_pose = pair->have_points3d = false; pair->last_count = 0; pair->unit_z = false; pair->have_pts4 = false; pair->have_bound = false; pair->have_refined = false; }
+    if (rc == SFM_OK) { pair->have_points = true; pair->have_E = pair->have_P = pair->have_pose = pair->have_points3d = false; pair->last_count = 0; pair->unit_z = false; pair->have_pts4 = false; pair->have_bound = false; pair->have_refined = false; pair->have_view = false; }
     return rc;
 }
 
@@ -866,6 +868,104 @@ int sfm_get_reprojection_errors(sfm_pair *pair, float *h_err, uint8_t *h_used)
     return copy_out(pair, h_used, reinterpret_cast<const uint8_t *>(pair->d_rreproj + pair->n), (size_t)pair->n);
 }
 
+// ---- registering a further view (register.hip) ----------------------------------------------------
+void sfm_register_default_params(sfm_register_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->num_hypotheses = 4096;
+    p->seed = 0x5EED5F3Du;
+    p->threshold_px = 4.0f;
+    p->min_score = 0.85f;
+    p->max_ambiguity = 0.95f;
+    p->max_iterations = 10;
+    p->huber_px = 1.0f;
+    p->min_rel_decrease = 1e-6f;
+    p->initial_lambda = 1e-3f;
+}
+
+int sfm_register_view(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_register_params *p)
+{
+    SFM_REQUIRE(pair && d_sift && p, SFM_E_INVALID, "null argument");
+    if (pair->pipe_pending) { const int rcf = sfm_pair_flush(pair); if (rcf != SFM_OK) return rcf; }
+    SFM_REQUIRE(p->reserved[0] == 0 && p->reserved[1] == 0 && p->reserved[2] == 0 && p->reserved[3] == 0, SFM_E_INVALID,
+                "sfm_register_params.reserved[] must be zero");
+    SFM_REQUIRE(p->num_hypotheses >= 1 && p->num_hypotheses <= (1u << 20), SFM_E_INVALID, "num_hypotheses %u outside 1..2^20", p->num_hypotheses);
+    SFM_REQUIRE(isfinite(p->threshold_px) && p->threshold_px > 0.0f, SFM_E_INVALID, "threshold_px must be finite and > 0");
+    SFM_REQUIRE(isfinite(p->min_score) && isfinite(p->max_ambiguity), SFM_E_INVALID, "min_score / max_ambiguity must be finite");
+    SFM_REQUIRE(p->max_iterations >= 0 && p->max_iterations <= 200, SFM_E_INVALID, "max_iterations %d outside 0..200", p->max_iterations);
+    SFM_REQUIRE(p->huber_px >= 0.0f && isfinite(p->huber_px), SFM_E_INVALID, "huber_px must be finite and >= 0");
+    SFM_REQUIRE(isfinite(p->min_rel_decrease) && p->min_rel_decrease >= 0.0f, SFM_E_INVALID, "min_rel_decrease must be finite and >= 0");
+    SFM_REQUIRE(isfinite(p->initial_lambda) && p->initial_lambda >= 0.0f, SFM_E_INVALID, "initial_lambda must be finite and >= 0");
+    SFM_REQUIRE(p->d_points || !p->d_valid, SFM_E_INVALID, "d_valid needs d_points");
+    SFM_REQUIRE(pair->have_points, SFM_E_STATE, "register_view before fillXU / set_points");
+    SFM_REQUIRE(p->d_points || pair->have_refined, SFM_E_STATE, "register_view without d_points needs sfm_refine_two_view on the current points");
+    SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
+    if (!pair->d_vstate) {                              // sized to the creation-time count: sfm_pair_reset needs no reallocation
+        const size_t cap = (size_t)pair->cap_points;
+        int rc = SFM_OK;
+        auto A = [&](void **ptr, size_t bytes) { if (rc == SFM_OK) rc = dev_alloc(reinterpret_cast<char **>(ptr), bytes); };
+        A(reinterpret_cast<void **>(&pair->d_vstate), (size_t)register_state_words() * 4);
+        A(reinterpret_cast<void **>(&pair->d_vreproj), 5 * cap);
+        A(&pair->d_vwork, register_work_bytes(pair->cap_points));
+        if (rc != SFM_OK) {
+            for (void *b : { (void *)pair->d_vstate, (void *)pair->d_vreproj, pair->d_vwork }) if (b) (void)hipFree(b);
+            pair->d_vstate = nullptr; pair->d_vreproj = nullptr; pair->d_vwork = nullptr;
+            return rc;
+        }
+    }
+    if (p->num_hypotheses > pair->cap_vhyps) {          // grows with the largest num_hypotheses seen (the old buffers may be in use)
+        SFM_HIP_TRY(hipStreamSynchronize(pair->ctx->stream));
+        if (pair->d_vhyp) (void)hipFree(pair->d_vhyp);
+        if (pair->d_vcounts) (void)hipFree(pair->d_vcounts);
+        pair->d_vhyp = nullptr; pair->d_vcounts = nullptr; pair->cap_vhyps = 0; pair->have_view = false;
+        int rc = dev_alloc(reinterpret_cast<char **>(&pair->d_vhyp), register_hyp_bytes(p->num_hypotheses));
+        if (rc == SFM_OK) rc = dev_alloc(&pair->d_vcounts, (size_t)p->num_hypotheses);
+        if (rc != SFM_OK) return rc;
+        pair->cap_vhyps = p->num_hypotheses;
+    }
+    const float *d_points = p->d_points ? p->d_points : pair->d_rpoints;
+    const uint8_t *d_valid = p->d_points ? p->d_valid : reinterpret_cast<const uint8_t *>(pair->d_rreproj + pair->n);   // the used flags
+    const int rc = launch_register(pair, d_sift, *p, d_points, d_valid);
+    if (rc == SFM_OK) { pair->have_view = true; pair->view_hyps = p->num_hypotheses; }
+    return rc;
+}
+
+int sfm_get_register_report(sfm_pair *pair, sfm_register_report *r)
+{
+    SFM_REQUIRE(pair && r, SFM_E_INVALID, "null argument");
+    SFM_REQUIRE(pair->have_view, SFM_E_STATE, "no registration since the last fillXU / set_points / reset");
+    return copy_out(pair, r, pair->d_vstate + register_report_offset(), sizeof(*r));
+}
+
+int sfm_get_view_pose(sfm_pair *pair, float h_P[16], float h_P_ransac[16])
+{
+    SFM_REQUIRE(pair && (h_P || h_P_ransac), SFM_E_INVALID, "null argument");
+    SFM_REQUIRE(pair->have_view, SFM_E_STATE, "no registration since the last fillXU / set_points / reset");
+    float v[32];
+    const int rc = copy_out(pair, v, pair->d_vstate + register_pose_offset(), sizeof(v));
+    if (rc != SFM_OK) return rc;
+    if (h_P) memcpy(h_P, v, 16 * sizeof(float));
+    if (h_P_ransac) memcpy(h_P_ransac, v + 16, 16 * sizeof(float));
+    return SFM_OK;
+}
+
+int sfm_get_view_errors(sfm_pair *pair, float *h_err, uint8_t *h_inlier)
+{
+    SFM_REQUIRE(pair && h_err, SFM_E_INVALID, "null argument");
+    SFM_REQUIRE(pair->have_view, SFM_E_STATE, "no registration since the last fillXU / set_points / reset");
+    const int rc = copy_out(pair, h_err, pair->d_vreproj, (size_t)pair->n * 4);
+    if (rc != SFM_OK || !h_inlier) return rc;
+    return copy_out(pair, h_inlier, reinterpret_cast<const uint8_t *>(pair->d_vreproj + pair->n), (size_t)pair->n);
+}
+
+int sfm_get_view_counts(sfm_pair *pair, int32_t *h_counts)
+{
+    SFM_REQUIRE(pair && h_counts, SFM_E_INVALID, "null argument");
+    SFM_REQUIRE(pair->have_view, SFM_E_STATE, "no registration since the last fillXU / set_points / reset");
+    return copy_out(pair, h_counts, pair->d_vcounts, (size_t)pair->view_hyps * 4);
+}
+
 // ---- accessors ------------------------------------------------------------------------------------
 int sfm_pair_ld(const sfm_pair *pair) { return pair ? pair->ld : 0; }
 int sfm_pair_num_points(const sfm_pair *pair) { return pair ? pair->n : 0; }
@@ -892,6 +992,10 @@ int sfm_pair_device_ptr(sfm_pair *pair, int which, void **d_ptr, size_t *bytes)
     case SFM_BUF_REFINED_POSE: p = pair->have_refined ? pair->d_rstate + refine_pose_offset() : nullptr; b = p ? 25 * 4 : 0; break;
     case SFM_BUF_REFINED_POINTS: p = pair->have_refined ? pair->d_rpoints : nullptr; b = p ? (size_t)4 * pair->n * 4 : 0; break;
     case SFM_BUF_REPROJ: p = pair->have_refined ? pair->d_rreproj : nullptr; b = p ? (size_t)pair->n * 5 : 0; break;
+    // the registration's outputs: the same rule (sfm_register_view)
+    case SFM_BUF_VIEW_POSE: p = pair->have_view ? pair->d_vstate + register_pose_offset() : nullptr; b = p ? 32 * 4 : 0; break;
+    case SFM_BUF_VIEW_COUNTS: p = pair->have_view ? pair->d_vcounts : nullptr; b = p ? (size_t)pair->view_hyps * 4 : 0; break;
+    case SFM_BUF_VIEW_REPROJ: p = pair->have_view ? pair->d_vreproj : nullptr; b = p ? (size_t)pair->n * 5 : 0; break;
 #if SFM_AB
     // lab bench: what the pre-filter works from (profiles/fuzz_case.py): the per-hypothesis records of the last launch (64 bytes each; 16 with the
     // per-tile rule), the bound words (bound, -, eight box words), the cell table

@@ -197,6 +197,16 @@ struct sfm_pair {
     float *d_rreproj = nullptr;        // n errors, then n uint8 used flags
     void *d_rwork = nullptr;           // start points of the four candidates, compacted observations / points, index maps, votes
     bool have_refined = false;         // a refinement ran since the last fillXU / set_points / reset
+    // sfm_register_view: allocated at the first call (per-point buffers sized to cap_points, per-hypothesis buffers grown on
+    // demand) (register.hip)
+    float *d_vstate = nullptr;         // refined + RANSAC pose, report, key, candidate count
+    float *d_vreproj = nullptr;        // n errors, then n uint8 inlier flags
+    void *d_vwork = nullptr;           // candidates (X / W, observation), point -> candidate map, winner's inlier flags
+    void *d_vhyp = nullptr;            // per hypothesis: accumulator (uint64), pose (12 floats, SoA)
+    int *d_vcounts = nullptr;          // per hypothesis: inlier count
+    size_t cap_vhyps = 0;
+    uint32_t view_hyps = 0;            // num_hypotheses of the last registration
+    bool have_view = false;            // a registration ran since the last fillXU / set_points / reset
     int last_kernel = 0, last_grid = 0, last_block = 0, last_lds = 0;
 };
 
@@ -244,6 +254,14 @@ size_t refine_work_bytes(int cap_points);                         // bytes of pa
 int refine_state_words();                                         // floats of pair->d_rstate
 int refine_pose_offset();                                         // refined P + E inside d_rstate
 int refine_report_offset();                                       // sfm_refine_report inside d_rstate
+
+// register.hip
+int launch_register(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_register_params &p, const float *d_points, const uint8_t *d_valid);
+size_t register_work_bytes(int cap_points);                       // bytes of pair->d_vwork
+size_t register_hyp_bytes(size_t num_hypotheses);                 // bytes of pair->d_vhyp
+int register_state_words();                                       // floats of pair->d_vstate
+int register_pose_offset();                                       // refined pose, then the RANSAC pose, inside d_vstate
+int register_report_offset();                                     // sfm_register_report inside d_vstate
 
 // sift.hip
 void sift_layout(int width, int height, int num_octaves, int scale_up, sfm_sift_layout *L);

@@ -48,21 +48,22 @@ SFM_HD uint32_t mulhi32(uint32_t a, uint32_t b)
     return (uint32_t)(((uint64_t)a * (uint64_t)b) >> 32);
 }
 
-// 8 distinct point ids, a pure function of (seed, hyp, n): candidates cand(k) = mulhi(hash(base + k * phi), n), k = 0, 1, ..
-// (at most 256 of them), each kept unless it repeats an id already kept; if 256 candidates do not yield 8 ids, the rest are the
-// smallest integers not kept yet (unreachable for n >= 8 in practice).
-// Written slot by slot: slot i is compared with the i ids in front of it only (28 comparisons per sample in the usual case of no
-// repeat, not 8 per candidate against a partly filled array), the redraw loop runs only in lanes that met a repeat.  The
+// N distinct point ids, a pure function of (seed, hyp, n): candidates cand(k) = mulhi(hash(base + k * phi), n), k = 0, 1, ..
+// (at most 256 of them), each kept unless it repeats an id already kept; if 256 candidates do not yield N ids, the rest are the
+// smallest integers not kept yet (unreachable for n >= N in practice).
+// Written slot by slot: slot i is compared with the i ids in front of it only (28 comparisons per sample of 8 in the usual case of
+// no repeat, not 8 per candidate against a partly filled array), the redraw loop runs only in lanes that met a repeat.  The
 // sequence of candidates and the ids kept are exactly those of the plain loop (oracle/: orc_sample8).
-SFM_HD void sample8(uint32_t seed, uint32_t hyp, int n, int idx[8])
+template <int N>
+SFM_HD void sample_distinct(uint32_t seed, uint32_t hyp, int n, int idx[N])
 {
     const uint32_t base = hash32(hash32(seed) + hyp);
     uint32_t k = 0;
-    int got = 8;
+    int got = N;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) idx[i] = -1;
+    for (int i = 0; i < N; ++i) idx[i] = -1;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < N; ++i) {
         bool placed = false;
         while (k < 256u) {
             const int cand = (int)mulhi32(hash32(base + k * 0x9E3779B9U), (uint32_t)n);
@@ -74,17 +75,22 @@ SFM_HD void sample8(uint32_t seed, uint32_t hyp, int n, int idx[8])
         }
         if (!placed) { got = i; break; }          // (k == 256: no later slot can be placed either)
     }
-    for (int cand = 0; got < 8; ++cand) {          // unreachable for n >= 8 in practice
+    for (int cand = 0; got < N; ++cand) {          // unreachable for n >= N in practice
         bool dup = false;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) dup |= (j < got) & (idx[j] == cand);
+        for (int j = 0; j < N; ++j) dup |= (j < got) & (idx[j] == cand);
         if (!dup) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) if (j == got) idx[j] = cand % (n > 0 ? n : 1);
+            for (int j = 0; j < N; ++j) if (j == got) idx[j] = cand % (n > 0 ? n : 1);
             ++got;
         }
     }
 }
+
+// the 8-point sample of the essential-matrix RANSAC
+SFM_HD void sample8(uint32_t seed, uint32_t hyp, int n, int idx[8]) { sample_distinct<8>(seed, hyp, n, idx); }
+// the minimal sample of the view registration's P3P RANSAC (register_math.hpp): three points to solve, one to choose
+SFM_HD void sample4(uint32_t seed, uint32_t hyp, int n, int idx[4]) { sample_distinct<4>(seed, hyp, n, idx); }
 
 // ------------------------------------------------------------------------------------------
 // Lane-type abstraction.  The solver below is written once for T = float (one hypothesis per

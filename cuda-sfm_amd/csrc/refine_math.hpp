@@ -87,9 +87,11 @@ SFM_HD float refine_huber(float rx, float ry, float h, float &rho)
     return 1.0f;
 }
 
-// packed upper triangle of a symmetric 5 x 5 (row-major: 00 01 02 03 04 11 12 13 14 22 23 24 33 34 44) and 3 x 3 (00 01 02 11 12 22)
-SFM_HD constexpr int sym5(int i, int j) { return i <= j ? i * 5 - i * (i - 1) / 2 + (j - i) : j * 5 - j * (j - 1) / 2 + (i - j); }
-SFM_HD constexpr int sym3(int i, int j) { return i <= j ? i * 3 - i * (i - 1) / 2 + (j - i) : j * 3 - j * (j - 1) / 2 + (i - j); }
+// packed upper triangle of a symmetric N x N, row-major (N = 5: 00 01 02 03 04 11 12 13 14 22 23 24 33 34 44; N = 3: 00 01 02 11 12 22)
+template <int N>
+SFM_HD constexpr int symn(int i, int j) { return i <= j ? i * N - i * (i - 1) / 2 + (j - i) : j * N - j * (j - 1) / 2 + (i - j); }
+SFM_HD constexpr int sym5(int i, int j) { return symn<5>(i, j); }
+SFM_HD constexpr int sym3(int i, int j) { return symn<3>(i, j); }
 
 // The point block of the damped normal equations: Vi = (V + lambda diag V)^-1 (packed 3 x 3), Wm = Jc^T W Jp (5 x 3 row-major),
 // gp = Jp^T W r (3).  w1, w2: the per-view weights.
@@ -183,39 +185,43 @@ SFM_HD void refine_expso3(const double w[3], double E[9])
     E[6] = -A * w[1] + B * w[2] * w[0]; E[7] = A * w[0] + B * w[2] * w[1]; E[8] = 1.0 + B * (w[2] * w[2] - th2);
 }
 
-// Solves the damped 5 x 5 system S x = rhs in fp64 by Cholesky, in place: S (packed) becomes L, rhs becomes x.
-// False if S is not positive definite.
-SFM_HD bool refine_solve5(double S[15], double x[5])
+// Solves the damped N x N system S x = rhs in fp64 by Cholesky, in place: S (packed, symn<N>) becomes L, rhs becomes x.
+// False if S is not positive definite.  N = 5: the reduced camera system of the two-view refinement; N = 6: the pose-only
+// refinement of a registered view (register.hip).
+template <int N>
+SFM_HD bool refine_cholesky(double S[N * (N + 1) / 2], double x[N])
 {
 #pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        double d = S[sym5(j, j)];
+    for (int j = 0; j < N; ++j) {
+        double d = S[symn<N>(j, j)];
 #pragma unroll
-        for (int k = 0; k < j; ++k) d -= S[sym5(j, k)] * S[sym5(j, k)];
+        for (int k = 0; k < j; ++k) d -= S[symn<N>(j, k)] * S[symn<N>(j, k)];
         if (!(d > 0.0)) return false;
         d = sqrt(d);
-        S[sym5(j, j)] = d;
+        S[symn<N>(j, j)] = d;
 #pragma unroll
-        for (int i = j + 1; i < 5; ++i) {
-            double s = S[sym5(i, j)];
+        for (int i = j + 1; i < N; ++i) {
+            double s = S[symn<N>(i, j)];
 #pragma unroll
-            for (int k = 0; k < j; ++k) s -= S[sym5(i, k)] * S[sym5(j, k)];
-            S[sym5(i, j)] = s / d;
+            for (int k = 0; k < j; ++k) s -= S[symn<N>(i, k)] * S[symn<N>(j, k)];
+            S[symn<N>(i, j)] = s / d;
         }
     }
 #pragma unroll
-    for (int i = 0; i < 5; ++i) {
+    for (int i = 0; i < N; ++i) {
 #pragma unroll
-        for (int k = 0; k < i; ++k) x[i] -= S[sym5(i, k)] * x[k];
-        x[i] /= S[sym5(i, i)];
+        for (int k = 0; k < i; ++k) x[i] -= S[symn<N>(i, k)] * x[k];
+        x[i] /= S[symn<N>(i, i)];
     }
 #pragma unroll
-    for (int i = 4; i >= 0; --i) {
+    for (int i = N - 1; i >= 0; --i) {
 #pragma unroll
-        for (int k = i + 1; k < 5; ++k) x[i] -= S[sym5(k, i)] * x[k];
-        x[i] /= S[sym5(i, i)];
+        for (int k = i + 1; k < N; ++k) x[i] -= S[symn<N>(k, i)] * x[k];
+        x[i] /= S[symn<N>(i, i)];
     }
     return true;
 }
+
+SFM_HD bool refine_solve5(double S[15], double x[5]) { return refine_cholesky<5>(S, x); }
 
 } // namespace sfm

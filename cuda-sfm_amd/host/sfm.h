@@ -126,6 +126,27 @@ public:
         SFM_FACADE_CALL(sfm_get_reprojection_errors(pair_, e.data(), used ? used->data() : nullptr));
         return e;
     }
+    // registers a further view against the refined points (sfm_register_view): data = image 1's records re-matched against
+    // it (MatchSiftData(image 1, view)); P3P RANSAC, then the pose LM; returns the report (synchronises)
+    sfm_register_report registerView(SiftPoint *data, int max_iterations = 10, float threshold_px = 4.0f)
+    {
+        sfm_register_params p;
+        sfm_register_default_params(&p);
+        p.max_iterations = max_iterations;
+        p.threshold_px = threshold_px;
+        SFM_FACADE_CALL(sfm_register_view(pair_, reinterpret_cast<const sfm_sift_point *>(data), &p));
+        sfm_register_report r;
+        SFM_FACADE_CALL(sfm_get_register_report(pair_, &r));
+        return r;
+    }
+    void getViewPose(float P[16], float P_ransac[16] = nullptr) { SFM_FACADE_CALL(sfm_get_view_pose(pair_, P, P_ransac)); }   // [R3|t3; 0 0 0 1]
+    std::vector<float> getViewErrors(std::vector<uint8_t> *inlier = nullptr)     // px per point (+inf: no candidate); mask on request
+    {
+        std::vector<float> e((size_t)num_points_);
+        if (inlier) inlier->resize((size_t)num_points_);
+        SFM_FACADE_CALL(sfm_get_view_errors(pair_, e.data(), inlier ? inlier->data() : nullptr));
+        return e;
+    }
     std::vector<float> getX(int image)      // 3 x N normalised coordinates of image 0 / 1
     {
         std::vector<float> x((size_t)3 * num_points_);

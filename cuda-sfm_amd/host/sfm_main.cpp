@@ -3,11 +3,14 @@
 // estimateE -> computePosecandidates -> choosePose -> linear_triangulation.  The GL viewer that follows
 // in the reference (main.cpp:308-340) is replaced by a PLY file.
 //     sfm_main <img1.pgm|ppm> <img2.pgm|ppm> <cloud.ply> [result.bin] [num_hypotheses] [pose_mode] [thresh] [initBlur] [focal]
-//              [refine_iterations]
+//              [refine_iterations] [img3.pgm|ppm]
 // refine_iterations > 0 (default 0: nothing changes): two-view bundle adjustment after the pose chain; the PLY then holds the
 // refined points of the correspondences the refinement used, and one more line is printed.
+// img3 (with refine_iterations > 0): a third view of the same size, registered against the refined points (image 1 matched
+// against it, P3P RANSAC + pose LM); one more line: inliers / candidates, rms before -> after, |C3| = |-R3^T t3|.
 // result.bin (optional, for tests): int n, float E[9], int pose, uint hyp, uint count, float P[16] (chosen), float pts[4n], u8 mask[n]
 // Plain C++: facade headers + libsfm_amd.so only (no OpenCV, no GL).
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -21,7 +24,7 @@
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s img1 img2 cloud.ply [result.bin] [num_hypotheses] [pose_mode] [thresh] [initBlur] [focal] [refine_iterations]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s img1 img2 cloud.ply [result.bin] [num_hypotheses] [pose_mode] [thresh] [initBlur] [focal] [refine_iterations] [img3]\n", argv[0]);
         return 2;
     }
     std::vector<float> limg, rimg;
@@ -87,6 +90,34 @@ int main(int argc, char **argv)
                 sfm.getPoseIndex(), written, argv[3]);
     if (refine_iterations > 0)
         std::printf("refine: %d points, rms %.4f -> %.4f px, %d iterations\n", rep.num_used, rep.initial_rms_px, rep.final_rms_px, rep.iterations);
+    if (refine_iterations > 0 && argc > 11 && argv[11][0]) {
+        std::vector<float> img;
+        int w3 = 0, h3 = 0;
+        if (!ReadPNM(argv[11], img, w3, h3) || w3 != wi || h3 != hi) {
+            std::fprintf(stderr, "cannot read %s as an image of the size of the other two\n", argv[11]);
+            return 2;
+        }
+        CudaImage img3;
+        img3.Allocate(w, h, iAlignUp(w, 128), false, NULL, img.data());
+        img3.Download();
+        SiftData siftData3;
+        InitSiftData(siftData3, 32768, true, true);
+        float *tmp = AllocSiftTempMemory(w, h, 5, false);
+        ExtractSift(siftData3, img3, 5, initBlur, thresh, 0.0f, false, tmp);
+        FreeSiftTempMemory(tmp);
+        MatchSiftData(siftData1, siftData3);                                        // rewrites image 1's match fields only
+        const sfm_register_report vr = sfm.registerView(siftData1.d_data);
+        float P3[16];
+        sfm.getViewPose(P3);
+        double c3[3], nc = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            c3[a] = -((double)P3[a] * P3[3] + (double)P3[4 + a] * P3[7] + (double)P3[8 + a] * P3[11]);
+            nc += c3[a] * c3[a];
+        }
+        std::printf("view3: %d/%d inliers, rms %.4f -> %.4f px, |C3| %.4f\n", vr.num_inliers, vr.num_candidates, vr.initial_rms_px,
+                    vr.final_rms_px, std::sqrt(nc));
+        FreeSiftData(siftData3);
+    }
     if (argc > 4 && argv[4][0]) {
         float E[9], P[64];
         sfm.getE(E); sfm.getPoseCandidates(P);

@@ -325,6 +325,61 @@ int sfm_get_refined_points(sfm_pair *pair, float *h_points);
  * h_used (optional) uint8[num_points]: 1 for the points the solve used */
 int sfm_get_reprojection_errors(sfm_pair *pair, float *h_err, uint8_t *h_used);
 
+/* ---- registering a further view against the pair's 3-D points ------------------------------------
+ * One more view gets a pose X3 = R3 X + t3 in the pair's gauge (camera 1 = [I|0], the pair's |t| = 1 fixes the scale: |t3| is
+ * NOT normalised) from 2-D / 3-D correspondences: P3P RANSAC (Lambda Twist on a 4-point sample, one hypothesis per lane), then
+ * Levenberg-Marquardt over the 6 pose parameters on the winner's inliers, Huber loss on the pixel residual.  Every view shares
+ * the pair's K.
+ * Correspondences: the pair's point i is feature record i of view 1 (as in fillXU); d_sift holds view 1's records re-matched
+ * against the new view (sfm_match(ctx, d_sift1, n1, d_sift3, n3)).  Record i is a candidate when match >= 0,
+ * score > min_score, ambiguity < max_ambiguity and point i is usable (finite, W != 0, Z / W > 0, and its valid flag set); its
+ * observation is K^-1 (match_xpos, match_ypos, 1), dehomogenised.
+ * 3-D points: d_points NULL = the pair's refined points where the refinement's used flag is 1 (SFM_E_STATE unless
+ * sfm_refine_two_view ran on the current points); else the caller's DEVICE 4 x num_points (camera-1 frame) and optional
+ * uint8 d_valid[num_points].
+ * Inlier test, shared by the scoring kernel and the final mask: Y = R3 X + t3 in fp32, (x, y) the observation, inlier iff Y.z > 0
+ * and (fx (Y.x - x Y.z) + s (Y.y - y Y.z))^2 + (fy (Y.y - y Y.z))^2 < (threshold_px Y.z)^2, no division, no contraction.
+ * Fewer than 4 candidates or a winner with fewer than 6 inliers: status SFM_REFINE_DEGENERATE (not an error), the winner's pose
+ * unrefined ([I|0] if no sample gave one), zero masks.  sfm_register_view only enqueues (flushes the pair first); the getters
+ * synchronise.  Nothing estimateE, the pose stages or the refinement wrote changes. */
+typedef struct sfm_register_params {
+    uint32_t num_hypotheses;    /* 1..2^20, default 4096                                                               */
+    uint32_t seed;              /* sampler seed (sample4: the hash sampler of sample8), default 0x5EED5F3D              */
+    float    threshold_px;      /* inlier iff the pixel reprojection error is below this (test above), default 4.0      */
+    float    min_score, max_ambiguity;      /* candidate gate, defaults 0.85 / 0.95 (sfm_find_homography's)             */
+    int32_t  max_iterations;    /* pose LM, accepted + rejected, 0..200 (0 = RANSAC winner only), default 10           */
+    float    huber_px;          /* Huber threshold on the 2-D pixel residual; 0 = plain LS; default 1.0               */
+    float    min_rel_decrease;  /* stop when (cost_prev - cost) / cost_prev < this; default 1e-6                         */
+    float    initial_lambda;    /* Marquardt damping, diagonal scaled by (1 + lambda); default 1e-3                      */
+    const float   *d_points;    /* optional DEVICE 4 x num_points; NULL = refined points + the refinement's used flags   */
+    const uint8_t *d_valid;     /* optional DEVICE uint8[num_points] with d_points (NULL: every point)                   */
+    int32_t  reserved[4];       /* must be zero (else SFM_E_INVALID)                                                    */
+} sfm_register_params;
+void sfm_register_default_params(sfm_register_params *p);
+
+typedef struct sfm_register_report {
+    int32_t  status;            /* SFM_REFINE_CONVERGED / _MAX_ITER / _DEGENERATE                                      */
+    int32_t  num_candidates;    /* records that passed the gate                                                        */
+    int32_t  ransac_inliers;    /* the winner's count: the points the LM runs over                                     */
+    int32_t  num_inliers;       /* final mask: candidates that pass the inlier test under the refined pose             */
+    uint32_t best_hypothesis;   /* first maximum of the counts                                                         */
+    int32_t  iterations, accepted;
+    float    initial_rms_px, final_rms_px;  /* sqrt(sum of squared pixel residuals / (2 ransac_inliers)) over the winner's
+                                               inliers, at the winner's and at the refined pose; no Huber weighting      */
+    float    final_cost;        /* robust cost at the end                                                              */
+    float    lambda;
+} sfm_register_report;
+
+int sfm_register_view(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_register_params *p);   /* enqueue only */
+int sfm_get_register_report(sfm_pair *pair, sfm_register_report *r);                               /* synchronises */
+/* refined [R3|t3; 0 0 0 1] and the RANSAC winner's, row-major; either pointer may be NULL */
+int sfm_get_view_pose(sfm_pair *pair, float h_P[16], float h_P_ransac[16]);
+/* h_err[num_points]: pixel error under the refined pose, +inf for non-candidates and behind the camera; h_inlier (optional)
+ * uint8[num_points]: the final inlier mask */
+int sfm_get_view_errors(sfm_pair *pair, float *h_err, uint8_t *h_inlier);
+/* the inlier count of every hypothesis of the last registration (num_hypotheses int32) */
+int sfm_get_view_counts(sfm_pair *pair, int32_t *h_counts);
+
 /* ---- accessors (the reference keeps these private; needed for parity checks) ------------------ */
 #define SFM_BUF_X0      0   /* float 3 x ld   normalised coords image 1 (ld = sfm_pair_ld)   */
 #define SFM_BUF_X1      1
@@ -342,8 +397,11 @@ int sfm_get_reprojection_errors(sfm_pair *pair, float *h_err, uint8_t *h_used);
 #define SFM_BUF_REFINED_POSE   13  /* float 16 + 9  refined [R|t; 0 0 0 1], then E (sfm_refine_two_view)   */
 #define SFM_BUF_REFINED_POINTS 14  /* float 4 x num_points                                          */
 #define SFM_BUF_REPROJ         15  /* float num_points errors (px), then uint8 num_points used flags  */
+#define SFM_BUF_VIEW_POSE      16  /* float 16 + 16  refined [R3|t3; 0 0 0 1], then the RANSAC winner's (sfm_register_view) */
+#define SFM_BUF_VIEW_COUNTS    17  /* int32 num_hypotheses: per-hypothesis inlier counts             */
+#define SFM_BUF_VIEW_REPROJ    18  /* float num_points errors (px), then uint8 num_points inlier flags */
 /* SFM_BUF_REFINED_*, SFM_BUF_REPROJ: NULL and 0 bytes until sfm_refine_two_view has run on the current points (after a
- * fillXU, set_points or reset, as the getters' SFM_E_STATE) */
+ * fillXU, set_points or reset, as the getters' SFM_E_STATE); SFM_BUF_VIEW_* likewise until sfm_register_view has run */
 int sfm_pair_device_ptr(sfm_pair *pair, int which, void **d_ptr, size_t *bytes);
 int sfm_pair_ld(const sfm_pair *pair);                 /* padded leading dimension of X/U rows */
 int sfm_pair_num_points(const sfm_pair *pair);
