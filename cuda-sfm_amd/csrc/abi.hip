@@ -11,6 +11,7 @@
 #include <thread>
 #include <mutex>
 #include <vector>
+#include <initializer_list>
 
 namespace sfm {
 
@@ -34,7 +35,7 @@ static int dev_alloc(T **p, size_t count)
 static int resolve_shard(const sfm_pair *pair, const sfm_ransac_params *p, uint32_t *h0, uint32_t *count)
 {
     SFM_REQUIRE(pair && p, SFM_E_INVALID, "null pair/params");
-    SFM_REQUIRE(pair->have_points, SFM_E_STATE, "estimateE before fillXU / set_points");
+    SFM_NEED(pair, kPoints);
     SFM_REQUIRE(pair->n >= 8, SFM_E_INVALID, "the 8-point solver needs at least 8 correspondences (have %d)", pair->n);
     SFM_REQUIRE(p->num_hypotheses > 0, SFM_E_INVALID, "num_hypotheses must be > 0");
     SFM_REQUIRE(p->hyp_begin <= p->num_hypotheses, SFM_E_INVALID, "hyp_begin %u beyond num_hypotheses %u", p->hyp_begin, p->num_hypotheses);
@@ -53,9 +54,38 @@ static int resolve_shard(const sfm_pair *pair, const sfm_ransac_params *p, uint3
     return SFM_OK;
 }
 
+// the last row of K^-1 is (0 0 1): every normalised z is exactly 1
+static bool unit_z_Kinv(const float h_Kinv[9]) { return h_Kinv[6] == 0.0f && h_Kinv[7] == 0.0f && h_Kinv[8] == 1.0f; }
+
+// buffers that are allocated together on first use: all of them or none
+struct BufSpec { void **ptr; size_t bytes; };
+static int alloc_group(std::initializer_list<BufSpec> bufs)
+{
+    int rc = SFM_OK;
+    for (const BufSpec &b : bufs) if (rc == SFM_OK) rc = dev_alloc(reinterpret_cast<char **>(b.ptr), b.bytes);
+    if (rc != SFM_OK) for (const BufSpec &b : bufs) { if (*b.ptr) (void)hipFree(*b.ptr); *b.ptr = nullptr; }
+    return rc;
+}
+
+// d_rreproj / d_vreproj: one float error per point, then one uint8 flag per point (used / inlier)
+static size_t reproj_bytes(size_t points) { return points * 5; }
+static const uint8_t *reproj_flags(const sfm_pair *pair, const float *reproj) { return reinterpret_cast<const uint8_t *>(reproj + pair->n); }
+
+// the Levenberg-Marquardt fields sfm_refine_params and sfm_register_params share
+template <typename Params>
+static int check_lm_params(const Params &p, const char *name)
+{
+    SFM_REQUIRE(p.reserved[0] == 0 && p.reserved[1] == 0 && p.reserved[2] == 0 && p.reserved[3] == 0, SFM_E_INVALID, "%s.reserved[] must be zero", name);
+    SFM_REQUIRE(p.max_iterations >= 0 && p.max_iterations <= 200, SFM_E_INVALID, "max_iterations %d outside 0..200", p.max_iterations);
+    SFM_REQUIRE(p.huber_px >= 0.0f && isfinite(p.huber_px), SFM_E_INVALID, "huber_px must be finite and >= 0");
+    SFM_REQUIRE(isfinite(p.min_rel_decrease) && p.min_rel_decrease >= 0.0f, SFM_E_INVALID, "min_rel_decrease must be finite and >= 0");
+    SFM_REQUIRE(isfinite(p.initial_lambda) && p.initial_lambda >= 0.0f, SFM_E_INVALID, "initial_lambda must be finite and >= 0");
+    return SFM_OK;
+}
+
 static int copy_out(sfm_pair *pair, void *h_dst, const void *d_src, size_t bytes)
 {
-    if (pair->pipe_pending) { int rcf = sfm_pair_flush(pair); if (rcf != SFM_OK) return rcf; }
+    SFM_FLUSH(pair);
     SFM_HIP_TRY(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, pair->ctx->stream));
     SFM_HIP_TRY(hipStreamSynchronize(pair->ctx->stream));
     return SFM_OK;
@@ -465,7 +495,7 @@ int sfm_pair_create(sfm_ctx *ctx, const float h_K[9], const float h_Kinv[9], int
     hipError_t e = hipMemcpyAsync(p->d_K, h_K, 9 * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(p->d_Kinv, h_Kinv, 9 * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(p->d_key, 0, 2 * sizeof(unsigned long long), ctx->stream);
-    p->key_clean = true;
+    p->state.key_clean = true;
     if (e == hipSuccess) e = hipMemsetAsync(p->d_best, 0, 2 * sizeof(uint32_t), ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(p->d_bound, 0, 10 * sizeof(unsigned long long), ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(p->d_clk, 0, kClkWords * sizeof(unsigned long long), ctx->stream);
@@ -479,15 +509,12 @@ int sfm_pair_create(sfm_ctx *ctx, const float h_K[9], const float h_Kinv[9], int
 int sfm_pair_reset(sfm_pair *pair, int num_points)
 {
     SFM_REQUIRE(pair, SFM_E_INVALID, "null pair");
-    if (pair->pipe_pending) { const int rcf = sfm_pair_flush(pair); if (rcf != SFM_OK) return rcf; }
+    SFM_FLUSH(pair);
     SFM_REQUIRE(num_points > 0 && num_points <= pair->cap_points, SFM_E_INVALID,
                 "num_points %d outside (0, %d] (the size the pair was created with)", num_points, pair->cap_points);
     pair->n = num_points;
     pair->ld = round_up(num_points, 128);
-    pair->have_points = pair->have_E = pair->have_P = pair->have_pose = pair->have_points3d = false;
-    pair->have_refined = false;
-    pair->have_view = false;
-    pair->last_count = 0;
+    pair->state.reset();
     return SFM_OK;
 }
 
@@ -514,30 +541,22 @@ int sfm_pair_destroy(sfm_pair *p)
 int sfm_fill_xu(sfm_pair *pair, const sfm_sift_point *d_data)
 {
     SFM_REQUIRE(pair && d_data, SFM_E_INVALID, "null argument");
-    if (pair->pipe_pending) { const int rcf = sfm_pair_flush(pair); if (rcf != SFM_OK) return rcf; }
+    SFM_FLUSH(pair);
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
-    int rc = launch_fill_xu(pair, d_data);
-    if (rc == SFM_OK) {
-        pair->have_points = true; pair->have_E = pair->have_P = pair->have_pose = pair->have_points3d = false; pair->last_count = 0;
-        pair->have_refined = false;
-        pair->have_view = false;
-        pair->key_clean = true;             // fill_xu_kernel zeroes d_key
-        // X_z = fma(Kinv[8], 1, fma(Kinv[7], y, Kinv[6] * x)) is exactly 1 for finite pixel coordinates when
-        // the last row of K^-1 is (0 0 1): the scoring kernel may then drop z (ransac_device.hpp)
-        pair->unit_z = pair->h_Kinv[6] == 0.0f && pair->h_Kinv[7] == 0.0f && pair->h_Kinv[8] == 1.0f;
-        pair->have_pts4 = pair->unit_z;     // fill_xu_kernel wrote the (x1x, x1y, x2x, x2y) records; they stand for the points when every z is 1
-        pair->have_bound = true;            // ... and the bound over all points (the pre-filter kernel's B)
-    }
+    const int rc = launch_fill_xu(pair, d_data);
+    // X_z = fma(Kinv[8], 1, fma(Kinv[7], y, Kinv[6] * x)) is exactly 1 for finite pixel coordinates when
+    // the last row of K^-1 is (0 0 1): the scoring kernel may then drop z (ransac_device.hpp)
+    if (rc == SFM_OK) pair->state.points_filled(unit_z_Kinv(pair->h_Kinv));
     return rc;
 }
 
 int sfm_set_points(sfm_pair *pair, const float *d_X0, const float *d_X1)
 {
     SFM_REQUIRE(pair && d_X0 && d_X1, SFM_E_INVALID, "null argument");
-    if (pair->pipe_pending) { const int rcf = sfm_pair_flush(pair); if (rcf != SFM_OK) return rcf; }
+    SFM_FLUSH(pair);
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
-    int rc = launch_set_points(pair, d_X0, d_X1);
-    if (rc == SFM_OK) { pair->have_points = true; pair->have_E = pair->have_P = pair->have_pose = pair->have_points3d = false; pair->last_count = 0; pair->unit_z = false; pair->have_pts4 = false; pair->have_bound = false; pair->have_refined = false; pair->have_view = false; }
+    const int rc = launch_set_points(pair, d_X0, d_X1);
+    if (rc == SFM_OK) pair->state.points_set();
     return rc;
 }
 
@@ -560,36 +579,29 @@ int sfm_ransac_permutation_indices(sfm_ctx *ctx, int num_points, uint32_t seed, 
     return launch_permutation_indices(ctx, num_points, seed, d_indices);
 }
 
-int sfm_ransac_score(sfm_pair *pair, const sfm_ransac_params *p)
+// the three plain scoring calls: the shard on the context's stream, behind a pending burst
+static int score_shard(sfm_pair *pair, const sfm_ransac_params *p, uint64_t *d_key_out, const float *d_E)
 {
     uint32_t h0, count;
     int rc = resolve_shard(pair, p, &h0, &count);
     if (rc != SFM_OK) return rc;
-    if (pair->pipe_pending) { const int rcf = sfm_pair_flush(pair); if (rcf != SFM_OK) return rcf; }
+    SFM_FLUSH(pair);
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
-    return launch_ransac_score(pair, *p, h0, count);
+    return launch_ransac_score(pair, *p, h0, count, reinterpret_cast<unsigned long long *>(d_key_out), d_E);
 }
+
+int sfm_ransac_score(sfm_pair *pair, const sfm_ransac_params *p) { return score_shard(pair, p, nullptr, nullptr); }
 
 int sfm_ransac_score_candidates(sfm_pair *pair, const sfm_ransac_params *p, const float *d_E)
 {
     SFM_REQUIRE(d_E, SFM_E_INVALID, "null candidate pointer");
-    uint32_t h0, count;
-    int rc = resolve_shard(pair, p, &h0, &count);
-    if (rc != SFM_OK) return rc;
-    if (pair->pipe_pending) { const int rcf = sfm_pair_flush(pair); if (rcf != SFM_OK) return rcf; }
-    SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
-    return launch_ransac_score(pair, *p, h0, count, nullptr, d_E);
+    return score_shard(pair, p, nullptr, d_E);
 }
 
 int sfm_ransac_score_into(sfm_pair *pair, const sfm_ransac_params *p, uint64_t *d_key_out)
 {
     SFM_REQUIRE(d_key_out, SFM_E_INVALID, "null key pointer");
-    uint32_t h0, count;
-    int rc = resolve_shard(pair, p, &h0, &count);
-    if (rc != SFM_OK) return rc;
-    if (pair->pipe_pending) { const int rcf = sfm_pair_flush(pair); if (rcf != SFM_OK) return rcf; }
-    SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
-    return launch_ransac_score(pair, *p, h0, count, reinterpret_cast<unsigned long long *>(d_key_out));
+    return score_shard(pair, p, d_key_out, nullptr);
 }
 
 int sfm_ransac_score_into_slot(sfm_pair *pair, const sfm_ransac_params *p, uint64_t *d_key_out, int slot, void *hip_stream)
@@ -614,7 +626,7 @@ int sfm_ransac_score_into_slot(sfm_pair *pair, const sfm_ransac_params *p, uint6
         std::swap(pair->d_counts, pair->alt_counts); std::swap(pair->d_tick, pair->alt_tick);
         std::swap(pair->d_Ecand, pair->alt_Ecand); std::swap(pair->cap_hyps, pair->alt_cap_hyps);
         std::swap(pair->d_pf, pair->alt_pf);
-        pair->key_clean = false;            // (the flag describes the pair's own key buffer, not the slot's)
+        pair->state.key_clean = false;      // (the flag describes the pair's own key buffer, not the slot's)
         std::swap(pair->d_key, pair->alt_key);
     };
     hipStream_t keep = pair->ctx->stream;
@@ -623,7 +635,7 @@ int sfm_ransac_score_into_slot(sfm_pair *pair, const sfm_ransac_params *p, uint6
     rc = launch_ransac_score(pair, *p, h0, count, reinterpret_cast<unsigned long long *>(d_key_out));
     pair->ctx->stream = keep;
     if (slot == 1) swap_slot();
-    pair->last_count = 0;                         // the candidates / counts of a slot are not what the plain getters describe
+    pair->state.last_count = 0;                   // the candidates / counts of a slot are not what the plain getters describe
     return rc;
 }
 
@@ -660,7 +672,7 @@ int sfm_estimate_E_pipelined(sfm_pair *pair, const sfm_ransac_params *p)
     SFM_HIP_TRY(hipEventRecord(pair->pipe_final[slot], st));
     pair->pipe_step++;
     pair->pipe_pending = true;
-    pair->have_E = true; pair->have_P = pair->have_pose = pair->have_points3d = false;
+    pair->state.E_finalized();
     return SFM_OK;
 }
 
@@ -679,11 +691,11 @@ int sfm_ransac_finalize(sfm_pair *pair, const sfm_ransac_params *p, uint32_t hyp
     uint32_t h0, count;
     int rc = resolve_shard(pair, p, &h0, &count);
     if (rc != SFM_OK) return rc;
-    if (pair->pipe_pending) { const int rcf = sfm_pair_flush(pair); if (rcf != SFM_OK) return rcf; }
+    SFM_FLUSH(pair);
     SFM_REQUIRE(hyp < p->num_hypotheses, SFM_E_INVALID, "hypothesis id %u out of range", hyp);
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
     rc = launch_ransac_finalize(pair, *p, nullptr, hyp, false);
-    if (rc == SFM_OK) { pair->have_E = true; pair->have_P = pair->have_pose = pair->have_points3d = false; }
+    if (rc == SFM_OK) pair->state.E_finalized();
     return rc;
 }
 
@@ -700,11 +712,11 @@ int sfm_ransac_finalize_key(sfm_pair *pair, const sfm_ransac_params *p, const ui
     uint32_t h0, count;
     int rc = resolve_shard(pair, p, &h0, &count);
     if (rc != SFM_OK) return rc;
-    if (pair->pipe_pending) { const int rcf = sfm_pair_flush(pair); if (rcf != SFM_OK) return rcf; }
+    SFM_FLUSH(pair);
     SFM_REQUIRE(d_key, SFM_E_INVALID, "null key pointer");
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
     rc = launch_ransac_finalize(pair, *p, reinterpret_cast<const unsigned long long *>(d_key), 0, true);
-    if (rc == SFM_OK) { pair->have_E = true; pair->have_P = pair->have_pose = pair->have_points3d = false; }
+    if (rc == SFM_OK) pair->state.E_finalized();
     return rc;
 }
 
@@ -717,7 +729,7 @@ int sfm_ransac_finalize_key_on(sfm_pair *pair, const sfm_ransac_params *p, const
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
     rc = launch_ransac_finalize(pair, *p, reinterpret_cast<const unsigned long long *>(d_key), 0, true,
                                 static_cast<hipStream_t>(hip_stream), true);
-    if (rc == SFM_OK) { pair->have_E = true; pair->have_P = pair->have_pose = pair->have_points3d = false; }
+    if (rc == SFM_OK) pair->state.E_finalized();
     return rc;
 }
 
@@ -726,25 +738,25 @@ int sfm_estimate_E(sfm_pair *pair, const sfm_ransac_params *p)
     uint32_t h0, count;
     int rc = resolve_shard(pair, p, &h0, &count);
     if (rc != SFM_OK) return rc;
-    if (pair->pipe_pending) { const int rcf = sfm_pair_flush(pair); if (rcf != SFM_OK) return rcf; }
+    SFM_FLUSH(pair);
     SFM_REQUIRE(count > 0, SFM_E_INVALID, "empty hypothesis range");
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
     rc = launch_ransac_score(pair, *p, h0, count);
     if (rc != SFM_OK) return rc;
     rc = launch_ransac_finalize(pair, *p, pair->d_key, 0, true);     // arg-max stays on the device
-    if (rc == SFM_OK) { pair->have_E = true; pair->have_P = pair->have_pose = pair->have_points3d = false; }
+    if (rc == SFM_OK) pair->state.E_finalized();
     return rc;
 }
 
 int sfm_pose_candidates(sfm_pair *pair, int mode)
 {
     SFM_REQUIRE(pair, SFM_E_INVALID, "null pair");
-    if (pair->pipe_pending) { const int rcf = sfm_pair_flush(pair); if (rcf != SFM_OK) return rcf; }
+    SFM_FLUSH(pair);
     SFM_REQUIRE(mode == SFM_POSE_REFERENCE || mode == SFM_POSE_CORRECT, SFM_E_INVALID, "unknown pose mode %d", mode);
-    SFM_REQUIRE(pair->have_E, SFM_E_STATE, "computePosecandidates before estimateE");
+    SFM_NEED(pair, kE);
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
     int rc = launch_pose_candidates(pair, mode);
-    if (rc == SFM_OK) { pair->have_P = true; pair->have_pose = pair->have_points3d = false; pair->pose_mode = mode; }
+    if (rc == SFM_OK) { pair->state.candidates_done(); pair->pose_mode = mode; }
     return rc;
 }
 
@@ -752,10 +764,10 @@ int sfm_choose_pose(sfm_pair *pair, int mode)
 {
     SFM_REQUIRE(pair, SFM_E_INVALID, "null pair");
     SFM_REQUIRE(mode == SFM_POSE_REFERENCE || mode == SFM_POSE_CORRECT, SFM_E_INVALID, "unknown pose mode %d", mode);
-    SFM_REQUIRE(pair->have_P, SFM_E_STATE, "choosePose before computePosecandidates");
+    SFM_NEED(pair, kP);
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
     int rc = launch_choose_pose(pair, mode);
-    if (rc == SFM_OK) { pair->have_pose = true; pair->have_points3d = false; }
+    if (rc == SFM_OK) pair->state.pose_chosen();
     return rc;
 }
 
@@ -763,19 +775,19 @@ int sfm_triangulate(sfm_pair *pair, int mode)
 {
     SFM_REQUIRE(pair, SFM_E_INVALID, "null pair");
     SFM_REQUIRE(mode == SFM_POSE_REFERENCE || mode == SFM_POSE_CORRECT, SFM_E_INVALID, "unknown pose mode %d", mode);
-    SFM_REQUIRE(pair->have_pose, SFM_E_STATE, "linear_triangulation before choosePose");
+    SFM_NEED(pair, kPose);
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
     int rc = launch_triangulate(pair, mode);
-    if (rc == SFM_OK) pair->have_points3d = true;
+    if (rc == SFM_OK) pair->state.triangulated();
     return rc;
 }
 
 static int pose_chain(sfm_pair *pair, int mode, float *d_record)
 {
     SFM_REQUIRE(pair, SFM_E_INVALID, "null pair");
-    if (pair->pipe_pending) { const int rcf = sfm_pair_flush(pair); if (rcf != SFM_OK) return rcf; }
+    SFM_FLUSH(pair);
     SFM_REQUIRE(mode == SFM_POSE_REFERENCE || mode == SFM_POSE_CORRECT, SFM_E_INVALID, "unknown pose mode %d", mode);
-    SFM_REQUIRE(pair->have_E, SFM_E_STATE, "computePosecandidates before estimateE");
+    SFM_NEED(pair, kE);
     if (mode == SFM_POSE_CORRECT) {               // the majority vote needs every point before the choice: three launches
         int rc = sfm_pose_candidates(pair, mode);
         if (rc == SFM_OK) rc = sfm_choose_pose(pair, mode);
@@ -785,7 +797,7 @@ static int pose_chain(sfm_pair *pair, int mode, float *d_record)
     }
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
     const int rc = launch_pose_chain(pair, d_record);
-    if (rc == SFM_OK) { pair->have_P = pair->have_pose = pair->have_points3d = true; pair->pose_mode = mode; }
+    if (rc == SFM_OK) { pair->state.chain_done(); pair->pose_mode = mode; }
     return rc;
 }
 
@@ -805,45 +817,35 @@ void sfm_refine_default_params(sfm_refine_params *p)
 int sfm_refine_two_view(sfm_pair *pair, const sfm_refine_params *p)
 {
     SFM_REQUIRE(pair && p, SFM_E_INVALID, "null argument");
-    if (pair->pipe_pending) { const int rcf = sfm_pair_flush(pair); if (rcf != SFM_OK) return rcf; }
-    SFM_REQUIRE(pair->have_E, SFM_E_STATE, "refine before estimateE");
-    SFM_REQUIRE(p->reserved[0] == 0 && p->reserved[1] == 0 && p->reserved[2] == 0 && p->reserved[3] == 0, SFM_E_INVALID,
-                "sfm_refine_params.reserved[] must be zero");
-    SFM_REQUIRE(p->max_iterations >= 0 && p->max_iterations <= 200, SFM_E_INVALID, "max_iterations %d outside 0..200", p->max_iterations);
-    SFM_REQUIRE(p->huber_px >= 0.0f && isfinite(p->huber_px), SFM_E_INVALID, "huber_px must be finite and >= 0");
-    SFM_REQUIRE(isfinite(p->min_rel_decrease) && p->min_rel_decrease >= 0.0f, SFM_E_INVALID, "min_rel_decrease must be finite and >= 0");
-    SFM_REQUIRE(isfinite(p->initial_lambda) && p->initial_lambda >= 0.0f, SFM_E_INVALID, "initial_lambda must be finite and >= 0");
+    SFM_FLUSH(pair);
+    SFM_NEED(pair, kE);
+    int rc = check_lm_params(*p, "sfm_refine_params");
+    if (rc != SFM_OK) return rc;
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
     if (!pair->d_rstate) {                              // sized to the creation-time count: sfm_pair_reset needs no reallocation
         const size_t cap = (size_t)pair->cap_points;
-        int rc = SFM_OK;
-        auto A = [&](void **ptr, size_t bytes) { if (rc == SFM_OK) rc = dev_alloc(reinterpret_cast<char **>(ptr), bytes); };
-        A(reinterpret_cast<void **>(&pair->d_rstate), (size_t)refine_state_words() * 4);
-        A(reinterpret_cast<void **>(&pair->d_rpoints), 4 * cap * 4);
-        A(reinterpret_cast<void **>(&pair->d_rreproj), 5 * cap);
-        A(&pair->d_rwork, refine_work_bytes(pair->cap_points));
-        if (rc != SFM_OK) {
-            for (void *b : { (void *)pair->d_rstate, (void *)pair->d_rpoints, (void *)pair->d_rreproj, pair->d_rwork }) if (b) (void)hipFree(b);
-            pair->d_rstate = nullptr; pair->d_rpoints = nullptr; pair->d_rreproj = nullptr; pair->d_rwork = nullptr;
-            return rc;
-        }
+        rc = alloc_group({ { reinterpret_cast<void **>(&pair->d_rstate), (size_t)refine_state_words() * 4 },
+                           { reinterpret_cast<void **>(&pair->d_rpoints), 4 * cap * 4 },
+                           { reinterpret_cast<void **>(&pair->d_rreproj), reproj_bytes(cap) },
+                           { &pair->d_rwork, refine_work_bytes(pair->cap_points) } });
+        if (rc != SFM_OK) return rc;
     }
-    const int rc = launch_refine(pair, *p);
-    if (rc == SFM_OK) pair->have_refined = true;
+    rc = launch_refine(pair, *p);
+    if (rc == SFM_OK) pair->state.refined();
     return rc;
 }
 
 int sfm_get_refine_report(sfm_pair *pair, sfm_refine_report *r)
 {
     SFM_REQUIRE(pair && r, SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(pair->have_refined, SFM_E_STATE, "no refinement since the last fillXU / set_points / reset");
+    SFM_NEED(pair, kRefined);
     return copy_out(pair, r, pair->d_rstate + refine_report_offset(), sizeof(*r));
 }
 
 int sfm_get_refined_pose(sfm_pair *pair, float h_P[16], float h_E[9])
 {
     SFM_REQUIRE(pair && (h_P || h_E), SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(pair->have_refined, SFM_E_STATE, "no refinement since the last fillXU / set_points / reset");
+    SFM_NEED(pair, kRefined);
     float v[25];
     const int rc = copy_out(pair, v, pair->d_rstate + refine_pose_offset(), sizeof(v));
     if (rc != SFM_OK) return rc;
@@ -855,17 +857,17 @@ int sfm_get_refined_pose(sfm_pair *pair, float h_P[16], float h_E[9])
 int sfm_get_refined_points(sfm_pair *pair, float *h_points)
 {
     SFM_REQUIRE(pair && h_points, SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(pair->have_refined, SFM_E_STATE, "no refinement since the last fillXU / set_points / reset");
+    SFM_NEED(pair, kRefined);
     return copy_out(pair, h_points, pair->d_rpoints, (size_t)4 * pair->n * 4);
 }
 
 int sfm_get_reprojection_errors(sfm_pair *pair, float *h_err, uint8_t *h_used)
 {
     SFM_REQUIRE(pair && h_err, SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(pair->have_refined, SFM_E_STATE, "no refinement since the last fillXU / set_points / reset");
+    SFM_NEED(pair, kRefined);
     const int rc = copy_out(pair, h_err, pair->d_rreproj, (size_t)pair->n * 4);
     if (rc != SFM_OK || !h_used) return rc;
-    return copy_out(pair, h_used, reinterpret_cast<const uint8_t *>(pair->d_rreproj + pair->n), (size_t)pair->n);
+    return copy_out(pair, h_used, reproj_flags(pair, pair->d_rreproj), (size_t)pair->n);
 }
 
 // ---- registering a further view (register.hip) ----------------------------------------------------
@@ -887,61 +889,47 @@ void sfm_register_default_params(sfm_register_params *p)
 int sfm_register_view(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_register_params *p)
 {
     SFM_REQUIRE(pair && d_sift && p, SFM_E_INVALID, "null argument");
-    if (pair->pipe_pending) { const int rcf = sfm_pair_flush(pair); if (rcf != SFM_OK) return rcf; }
-    SFM_REQUIRE(p->reserved[0] == 0 && p->reserved[1] == 0 && p->reserved[2] == 0 && p->reserved[3] == 0, SFM_E_INVALID,
-                "sfm_register_params.reserved[] must be zero");
+    SFM_FLUSH(pair);
+    int rc = check_lm_params(*p, "sfm_register_params");
+    if (rc != SFM_OK) return rc;
     SFM_REQUIRE(p->num_hypotheses >= 1 && p->num_hypotheses <= (1u << 20), SFM_E_INVALID, "num_hypotheses %u outside 1..2^20", p->num_hypotheses);
     SFM_REQUIRE(isfinite(p->threshold_px) && p->threshold_px > 0.0f, SFM_E_INVALID, "threshold_px must be finite and > 0");
     SFM_REQUIRE(isfinite(p->min_score) && isfinite(p->max_ambiguity), SFM_E_INVALID, "min_score / max_ambiguity must be finite");
-    SFM_REQUIRE(p->max_iterations >= 0 && p->max_iterations <= 200, SFM_E_INVALID, "max_iterations %d outside 0..200", p->max_iterations);
-    SFM_REQUIRE(p->huber_px >= 0.0f && isfinite(p->huber_px), SFM_E_INVALID, "huber_px must be finite and >= 0");
-    SFM_REQUIRE(isfinite(p->min_rel_decrease) && p->min_rel_decrease >= 0.0f, SFM_E_INVALID, "min_rel_decrease must be finite and >= 0");
-    SFM_REQUIRE(isfinite(p->initial_lambda) && p->initial_lambda >= 0.0f, SFM_E_INVALID, "initial_lambda must be finite and >= 0");
     SFM_REQUIRE(p->d_points || !p->d_valid, SFM_E_INVALID, "d_valid needs d_points");
-    SFM_REQUIRE(pair->have_points, SFM_E_STATE, "register_view before fillXU / set_points");
-    SFM_REQUIRE(p->d_points || pair->have_refined, SFM_E_STATE, "register_view without d_points needs sfm_refine_two_view on the current points");
+    SFM_NEED(pair, p->d_points ? kPoints : kPoints | kRefined);       // without d_points: the refined points, on the current points
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
     if (!pair->d_vstate) {                              // sized to the creation-time count: sfm_pair_reset needs no reallocation
-        const size_t cap = (size_t)pair->cap_points;
-        int rc = SFM_OK;
-        auto A = [&](void **ptr, size_t bytes) { if (rc == SFM_OK) rc = dev_alloc(reinterpret_cast<char **>(ptr), bytes); };
-        A(reinterpret_cast<void **>(&pair->d_vstate), (size_t)register_state_words() * 4);
-        A(reinterpret_cast<void **>(&pair->d_vreproj), 5 * cap);
-        A(&pair->d_vwork, register_work_bytes(pair->cap_points));
-        if (rc != SFM_OK) {
-            for (void *b : { (void *)pair->d_vstate, (void *)pair->d_vreproj, pair->d_vwork }) if (b) (void)hipFree(b);
-            pair->d_vstate = nullptr; pair->d_vreproj = nullptr; pair->d_vwork = nullptr;
-            return rc;
-        }
+        rc = alloc_group({ { reinterpret_cast<void **>(&pair->d_vstate), (size_t)register_state_words() * 4 },
+                           { reinterpret_cast<void **>(&pair->d_vreproj), reproj_bytes((size_t)pair->cap_points) },
+                           { &pair->d_vwork, register_work_bytes(pair->cap_points) } });
+        if (rc != SFM_OK) return rc;
     }
     if (p->num_hypotheses > pair->cap_vhyps) {          // grows with the largest num_hypotheses seen (the old buffers may be in use)
-        SFM_HIP_TRY(hipStreamSynchronize(pair->ctx->stream));
-        if (pair->d_vhyp) (void)hipFree(pair->d_vhyp);
-        if (pair->d_vcounts) (void)hipFree(pair->d_vcounts);
-        pair->d_vhyp = nullptr; pair->d_vcounts = nullptr; pair->cap_vhyps = 0; pair->have_view = false;
-        int rc = dev_alloc(reinterpret_cast<char **>(&pair->d_vhyp), register_hyp_bytes(p->num_hypotheses));
-        if (rc == SFM_OK) rc = dev_alloc(&pair->d_vcounts, (size_t)p->num_hypotheses);
+        pair->state.view_dropped();
+        pair->cap_vhyps = 0;                            // ... until BOTH buffers exist again (d_vhyp has no size of its own)
+        size_t hyp_bytes = 0;
+        rc = grow(&pair->d_vhyp, &hyp_bytes, register_hyp_bytes(p->num_hypotheses), pair->ctx->stream);
+        if (rc == SFM_OK) rc = grow(&pair->d_vcounts, &pair->cap_vhyps, p->num_hypotheses, pair->ctx->stream);
         if (rc != SFM_OK) return rc;
-        pair->cap_vhyps = p->num_hypotheses;
     }
     const float *d_points = p->d_points ? p->d_points : pair->d_rpoints;
-    const uint8_t *d_valid = p->d_points ? p->d_valid : reinterpret_cast<const uint8_t *>(pair->d_rreproj + pair->n);   // the used flags
-    const int rc = launch_register(pair, d_sift, *p, d_points, d_valid);
-    if (rc == SFM_OK) { pair->have_view = true; pair->view_hyps = p->num_hypotheses; }
+    const uint8_t *d_valid = p->d_points ? p->d_valid : reproj_flags(pair, pair->d_rreproj);   // the used flags
+    rc = launch_register(pair, d_sift, *p, d_points, d_valid);
+    if (rc == SFM_OK) { pair->state.view_registered(); pair->view_hyps = p->num_hypotheses; }
     return rc;
 }
 
 int sfm_get_register_report(sfm_pair *pair, sfm_register_report *r)
 {
     SFM_REQUIRE(pair && r, SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(pair->have_view, SFM_E_STATE, "no registration since the last fillXU / set_points / reset");
+    SFM_NEED(pair, kView);
     return copy_out(pair, r, pair->d_vstate + register_report_offset(), sizeof(*r));
 }
 
 int sfm_get_view_pose(sfm_pair *pair, float h_P[16], float h_P_ransac[16])
 {
     SFM_REQUIRE(pair && (h_P || h_P_ransac), SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(pair->have_view, SFM_E_STATE, "no registration since the last fillXU / set_points / reset");
+    SFM_NEED(pair, kView);
     float v[32];
     const int rc = copy_out(pair, v, pair->d_vstate + register_pose_offset(), sizeof(v));
     if (rc != SFM_OK) return rc;
@@ -953,16 +941,16 @@ int sfm_get_view_pose(sfm_pair *pair, float h_P[16], float h_P_ransac[16])
 int sfm_get_view_errors(sfm_pair *pair, float *h_err, uint8_t *h_inlier)
 {
     SFM_REQUIRE(pair && h_err, SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(pair->have_view, SFM_E_STATE, "no registration since the last fillXU / set_points / reset");
+    SFM_NEED(pair, kView);
     const int rc = copy_out(pair, h_err, pair->d_vreproj, (size_t)pair->n * 4);
     if (rc != SFM_OK || !h_inlier) return rc;
-    return copy_out(pair, h_inlier, reinterpret_cast<const uint8_t *>(pair->d_vreproj + pair->n), (size_t)pair->n);
+    return copy_out(pair, h_inlier, reproj_flags(pair, pair->d_vreproj), (size_t)pair->n);
 }
 
 int sfm_get_view_counts(sfm_pair *pair, int32_t *h_counts)
 {
     SFM_REQUIRE(pair && h_counts, SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(pair->have_view, SFM_E_STATE, "no registration since the last fillXU / set_points / reset");
+    SFM_NEED(pair, kView);
     return copy_out(pair, h_counts, pair->d_vcounts, (size_t)pair->view_hyps * 4);
 }
 
@@ -970,10 +958,23 @@ int sfm_get_view_counts(sfm_pair *pair, int32_t *h_counts)
 int sfm_pair_ld(const sfm_pair *pair) { return pair ? pair->ld : 0; }
 int sfm_pair_num_points(const sfm_pair *pair) { return pair ? pair->n : 0; }
 
+// The stage a buffer id's contents belong to: without it sfm_pair_device_ptr answers (NULL, 0) where the getters answer SFM_E_STATE.
+static uint32_t buffer_stage(int which)
+{
+    switch (which) {
+    case SFM_BUF_REFINED_POSE: case SFM_BUF_REFINED_POINTS: case SFM_BUF_REPROJ: return kRefined;
+    case SFM_BUF_VIEW_POSE: case SFM_BUF_VIEW_COUNTS: case SFM_BUF_VIEW_REPROJ: return kView;
+    default: return 0;
+    }
+}
+
 int sfm_pair_device_ptr(sfm_pair *pair, int which, void **d_ptr, size_t *bytes)
 {
     SFM_REQUIRE(pair && d_ptr, SFM_E_INVALID, "null argument");
     void *p = nullptr; size_t b = 0;
+    *d_ptr = nullptr;
+    if (bytes) *bytes = 0;
+    if (!pair->state.has(buffer_stage(which))) return SFM_OK;
     switch (which) {
     case SFM_BUF_X0: p = pair->d_X[0]; b = (size_t)3 * pair->ld * 4; break;
     case SFM_BUF_X1: p = pair->d_X[1]; b = (size_t)3 * pair->ld * 4; break;
@@ -983,23 +984,23 @@ int sfm_pair_device_ptr(sfm_pair *pair, int which, void **d_ptr, size_t *bytes)
     case SFM_BUF_P: p = pair->d_P; b = 256; break;
     case SFM_BUF_PINV: p = pair->d_Pinv; b = 256; break;
     case SFM_BUF_POINTS: p = pair->d_points; b = (size_t)4 * pair->n * 4; break;
-    case SFM_BUF_COUNTS: p = pair->d_counts; b = (size_t)pair->last_count * 4; break;
+    case SFM_BUF_COUNTS: p = pair->d_counts; b = (size_t)pair->state.last_count * 4; break;
     case SFM_BUF_MASK: p = pair->d_mask; b = (size_t)pair->n; break;
     case SFM_BUF_KEY: p = pair->d_key; b = 8; break;
-    case SFM_BUF_ECAND: p = pair->d_Ecand; b = (size_t)pair->last_count * 36; break;
+    case SFM_BUF_ECAND: p = pair->d_Ecand; b = (size_t)pair->state.last_count * 36; break;
     case SFM_BUF_PIND: p = pair->d_Pind; b = 4; break;
-    // the refinement's outputs: NULL / 0 bytes unless they describe the current points (as the getters' SFM_E_STATE)
-    case SFM_BUF_REFINED_POSE: p = pair->have_refined ? pair->d_rstate + refine_pose_offset() : nullptr; b = p ? 25 * 4 : 0; break;
-    case SFM_BUF_REFINED_POINTS: p = pair->have_refined ? pair->d_rpoints : nullptr; b = p ? (size_t)4 * pair->n * 4 : 0; break;
-    case SFM_BUF_REPROJ: p = pair->have_refined ? pair->d_rreproj : nullptr; b = p ? (size_t)pair->n * 5 : 0; break;
+    // the refinement's outputs (buffer_stage: NULL / 0 bytes unless they describe the current points)
+    case SFM_BUF_REFINED_POSE: p = pair->d_rstate + refine_pose_offset(); b = 25 * 4; break;
+    case SFM_BUF_REFINED_POINTS: p = pair->d_rpoints; b = (size_t)4 * pair->n * 4; break;
+    case SFM_BUF_REPROJ: p = pair->d_rreproj; b = reproj_bytes((size_t)pair->n); break;
     // the registration's outputs: the same rule (sfm_register_view)
-    case SFM_BUF_VIEW_POSE: p = pair->have_view ? pair->d_vstate + register_pose_offset() : nullptr; b = p ? 32 * 4 : 0; break;
-    case SFM_BUF_VIEW_COUNTS: p = pair->have_view ? pair->d_vcounts : nullptr; b = p ? (size_t)pair->view_hyps * 4 : 0; break;
-    case SFM_BUF_VIEW_REPROJ: p = pair->have_view ? pair->d_vreproj : nullptr; b = p ? (size_t)pair->n * 5 : 0; break;
+    case SFM_BUF_VIEW_POSE: p = pair->d_vstate + register_pose_offset(); b = 32 * 4; break;
+    case SFM_BUF_VIEW_COUNTS: p = pair->d_vcounts; b = (size_t)pair->view_hyps * 4; break;
+    case SFM_BUF_VIEW_REPROJ: p = pair->d_vreproj; b = reproj_bytes((size_t)pair->n); break;
 #if SFM_AB
     // lab bench: what the pre-filter works from (profiles/fuzz_case.py): the per-hypothesis records of the last launch (64 bytes each; 16 with the
     // per-tile rule), the bound words (bound, -, eight box words), the cell table
-    case SFM_AB_BUF_PF_RECORDS: p = pair->d_pf; b = (size_t)pair->last_count * 64; break;
+    case SFM_AB_BUF_PF_RECORDS: p = pair->d_pf; b = (size_t)pair->state.last_count * 64; break;
     case SFM_AB_BUF_BOUND_WORDS: p = pair->d_bound; b = 10 * sizeof(unsigned long long); break;
     case SFM_AB_BUF_CELLS: p = pair->d_cells; b = pair->d_cells ? ((size_t)pair->cells_mask + 1) * sizeof(uint32_t) : 0; break;
 #endif
@@ -1025,14 +1026,14 @@ int sfm_get_XU(sfm_pair *pair, int which, float *h_out)
 int sfm_get_E(sfm_pair *pair, float h_E[9])
 {
     SFM_REQUIRE(pair && h_E, SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(pair->have_E, SFM_E_STATE, "no E yet");
+    SFM_NEED(pair, kE);
     return copy_out(pair, h_E, pair->d_E, 36);
 }
 
 int sfm_get_best(sfm_pair *pair, uint32_t *hyp, uint32_t *count)
 {
     SFM_REQUIRE(pair, SFM_E_INVALID, "null pair");
-    SFM_REQUIRE(pair->have_E, SFM_E_STATE, "no finalized hypothesis yet");
+    SFM_NEED(pair, kE);
     uint32_t b[2];
     int rc = copy_out(pair, b, pair->d_best, sizeof(b));
     if (rc != SFM_OK) return rc;
@@ -1051,44 +1052,44 @@ int sfm_get_key(sfm_pair *pair, uint64_t *key)
 int sfm_get_inlier_counts(sfm_pair *pair, int32_t *h_counts, size_t capacity)
 {
     SFM_REQUIRE(pair && h_counts, SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(capacity >= pair->last_count, SFM_E_INVALID, "capacity %zu < %u hypotheses", capacity, pair->last_count);
-    if (pair->last_count == 0) return SFM_OK;
-    return copy_out(pair, h_counts, pair->d_counts, (size_t)pair->last_count * 4);
+    SFM_REQUIRE(capacity >= pair->state.last_count, SFM_E_INVALID, "capacity %zu < %u hypotheses", capacity, pair->state.last_count);
+    if (pair->state.last_count == 0) return SFM_OK;
+    return copy_out(pair, h_counts, pair->d_counts, (size_t)pair->state.last_count * 4);
 }
 
 int sfm_get_E_candidates(sfm_pair *pair, float *h_E, size_t capacity_hyps)
 {
     SFM_REQUIRE(pair && h_E, SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(capacity_hyps >= pair->last_count, SFM_E_INVALID, "capacity too small");
-    if (pair->last_count == 0) return SFM_OK;
-    return copy_out(pair, h_E, pair->d_Ecand, (size_t)pair->last_count * 36);
+    SFM_REQUIRE(capacity_hyps >= pair->state.last_count, SFM_E_INVALID, "capacity too small");
+    if (pair->state.last_count == 0) return SFM_OK;
+    return copy_out(pair, h_E, pair->d_Ecand, (size_t)pair->state.last_count * 36);
 }
 
 int sfm_get_inlier_mask(sfm_pair *pair, uint8_t *h_mask)
 {
     SFM_REQUIRE(pair && h_mask, SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(pair->have_E, SFM_E_STATE, "no finalized hypothesis yet");
+    SFM_NEED(pair, kE);
     return copy_out(pair, h_mask, pair->d_mask, (size_t)pair->n);
 }
 
 int sfm_get_pose_candidates(sfm_pair *pair, float h_P[64])
 {
     SFM_REQUIRE(pair && h_P, SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(pair->have_P, SFM_E_STATE, "no pose candidates yet");
+    SFM_NEED(pair, kP);
     return copy_out(pair, h_P, pair->d_P, 256);
 }
 
 int sfm_get_pose_inverses(sfm_pair *pair, float h_Pinv[64])
 {
     SFM_REQUIRE(pair && h_Pinv, SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(pair->have_pose, SFM_E_STATE, "choosePose has not run");
+    SFM_NEED(pair, kPose);
     return copy_out(pair, h_Pinv, pair->d_Pinv, 256);
 }
 
 int sfm_get_pose_index(sfm_pair *pair, int *index)
 {
     SFM_REQUIRE(pair && index, SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(pair->have_pose, SFM_E_STATE, "choosePose has not run");
+    SFM_NEED(pair, kPose);
     int v[8];
     int rc = copy_out(pair, v, pair->d_Pind, sizeof(v));
     if (rc != SFM_OK) return rc;
@@ -1100,7 +1101,7 @@ int sfm_get_pose_index(sfm_pair *pair, int *index)
 int sfm_get_result(sfm_pair *pair, float h_record[28])
 {
     SFM_REQUIRE(pair && h_record, SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(pair->have_E && pair->have_pose, SFM_E_STATE, "estimateE / choosePose have not run");
+    SFM_NEED(pair, kE | kPose);
     float P[64]; int v[8]; uint32_t b[2];
     hipStream_t st = pair->ctx->stream;
     SFM_HIP_TRY(hipMemcpyAsync(h_record, pair->d_E, 9 * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -1119,17 +1120,58 @@ int sfm_get_result(sfm_pair *pair, float h_record[28])
 int sfm_get_points(sfm_pair *pair, float *h_points)
 {
     SFM_REQUIRE(pair && h_points, SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(pair->have_points3d, SFM_E_STATE, "linear_triangulation has not run");
+    SFM_NEED(pair, kPoints3d);
     return copy_out(pair, h_points, pair->d_points, (size_t)4 * pair->n * 4);
 }
 
 int sfm_copy_points_to_vbo(sfm_pair *pair, float *d_positions, float *d_velocities, float scale)
 {
     SFM_REQUIRE(pair, SFM_E_INVALID, "null pair");
-    SFM_REQUIRE(pair->have_points3d, SFM_E_STATE, "linear_triangulation has not run");
+    SFM_NEED(pair, kPoints3d);
     SFM_REQUIRE((((uintptr_t)d_positions | (uintptr_t)d_velocities) & 15u) == 0, SFM_E_INVALID, "vertex buffers must be 16-byte aligned");
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
     return launch_points_to_vbo(pair, d_positions, d_velocities, scale);
+}
+
+// ---- lanes: the caller's context + auxiliary contexts with streams of their own (sfm_extract_views, sfm_process_pairs) ----
+// out[0] = ctx, out[1 .. n) = the first n - 1 lane contexts, created on first use; every call hands them the caller's matcher
+// choice and SFM_QUIRK_* flags (every pair of one call honours the same ones)
+static int lane_contexts(sfm_ctx *ctx, int n, sfm_ctx **out)
+{
+    out[0] = ctx;
+    for (int l = 1; l < n; ++l) {
+        if (!ctx->lane[l - 1]) {
+            int rc = sfm_ctx_create(ctx->device, &ctx->lane[l - 1]);
+            if (rc == SFM_OK) rc = sfm_ctx_own_stream(ctx->lane[l - 1]);
+            if (rc != SFM_OK) return rc;
+        }
+        out[l] = ctx->lane[l - 1];
+        out[l]->match_kernel = ctx->match_kernel;
+        out[l]->quirks = ctx->quirks;
+    }
+    return SFM_OK;
+}
+
+// the caller's stream waits for lanes 1 .. n - 1; the first failure is kept in *rc (an earlier one is not overwritten)
+static void join_lanes(sfm_ctx *ctx, sfm_ctx *const *lanes, int n, int *rc)
+{
+    for (int l = 1; l < n; ++l) {
+        const hipError_t e1 = hipEventRecord(ctx->lane_ev[l], lanes[l]->stream);
+        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(ctx->stream, ctx->lane_ev[l], 0) : e1;
+        if (e2 != hipSuccess && *rc == SFM_OK) { set_error("lane join failed: %s", hipGetErrorString(e2)); *rc = SFM_E_HIP; }
+    }
+}
+
+// a pair sfm_process_pairs can work on: enough features for the 8-point solver, a second view (if given) that is not empty
+static bool usable(const sfm_pair_desc &d) { return d.n1 >= 8 && (!d.d_sift2 || d.n2 >= 1); }
+
+// Pairs that share their FIRST view stay on one lane in list order: the k-th distinct first view goes to lane k % nlanes.
+static sfm_ctx *lane_of_first_view(std::vector<const void *> &first_views, const void *sift1, sfm_ctx *const *lanes, int nlanes)
+{
+    size_t v = 0;
+    while (v < first_views.size() && first_views[v] != sift1) ++v;
+    if (v == first_views.size()) first_views.push_back(sift1);
+    return lanes[v % (size_t)nlanes];
 }
 
 // ---- many views: ExtractSift for a rank's share of the images --------------------------------------------------------
@@ -1139,12 +1181,9 @@ static int views_buffers(sfm_ctx *c, size_t floats)
     if (c->views_floats >= floats) return SFM_OK;
     SFM_HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->views_pinned) (void)hipHostFree(c->views_pinned);
-    if (c->views_image) (void)hipFree(c->views_image);
-    c->views_pinned = nullptr; c->views_image = nullptr; c->views_floats = 0;
+    c->views_pinned = nullptr; c->views_floats = 0;     // (the size counts for both: the device image grows last)
     SFM_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->views_pinned), floats * sizeof(float), hipHostMallocDefault));
-    SFM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->views_image), floats * sizeof(float)));
-    c->views_floats = floats;
-    return SFM_OK;
+    return grow(&c->views_image, &c->views_floats, floats, c->stream);
 }
 
 // 8-bit grey values -> float (exact), four pixels per thread; count is a multiple of four (the pitch is a multiple of 128)
@@ -1176,17 +1215,9 @@ static int extract_views_impl(sfm_ctx *ctx, const void *const *h_images, int byt
     constexpr int NC = sfm_ctx::kViewLanes;           // contexts
     constexpr int NR = 2 * NC;                        // pinned staging buffers (two per context)
     constexpr int NT = 3;                             // helper threads that fill them
-    sfm_ctx *cs[NC] = { ctx };
-    for (int l = 1; l < NC; ++l) {
-        if (!ctx->lane[l - 1]) {
-            int rc = sfm_ctx_create(ctx->device, &ctx->lane[l - 1]);
-            if (rc == SFM_OK) rc = sfm_ctx_own_stream(ctx->lane[l - 1]);
-            if (rc != SFM_OK) return rc;
-            ctx->lane[l - 1]->match_kernel = ctx->match_kernel;
-            ctx->lane[l - 1]->quirks = ctx->quirks;
-        }
-        cs[l] = ctx->lane[l - 1];
-    }
+    sfm_ctx *cs[NC];
+    const int rcl = lane_contexts(ctx, NC, cs);
+    if (rcl != SFM_OK) return rcl;
     const int pitch = round_up(width, 128);
     const size_t floats = (size_t)pitch * height;
     // device image per context; pinned staging buffers filled by helper threads that run ahead of the enqueueing thread:
@@ -1331,18 +1362,10 @@ int sfm_process_pairs(sfm_ctx *ctx, const float h_K[9], const float h_Kinv[9], c
     // stay on one lane in list order (MatchSiftData writes that view's match fields, fillXU reads them); everything else
     // of a record is only read, so different lanes may work on pairs that share views.
     const int nlanes = owned >= 8 ? sfm_ctx::kPairLanes : 1;
-    sfm_ctx *lanes[sfm_ctx::kPairLanes] = { ctx, nullptr, nullptr, nullptr };
-    static_assert(sfm_ctx::kPairLanes == 4 && sfm_ctx::kViewLanes >= sfm_ctx::kPairLanes, "the lane contexts are shared with sfm_extract_views");
-    for (int l = 1; l < nlanes; ++l) {
-        if (!ctx->lane[l - 1]) {
-            rc = sfm_ctx_create(ctx->device, &ctx->lane[l - 1]);
-            if (rc == SFM_OK) rc = sfm_ctx_own_stream(ctx->lane[l - 1]);
-            if (rc != SFM_OK) return rc;
-        }
-        lanes[l] = ctx->lane[l - 1];
-        lanes[l]->match_kernel = ctx->match_kernel;
-        lanes[l]->quirks = ctx->quirks;                     // every pair of one call honours the same SFM_QUIRK_* flags
-    }
+    sfm_ctx *lanes[sfm_ctx::kPairLanes] = {};
+    static_assert(sfm_ctx::kViewLanes >= sfm_ctx::kPairLanes, "the lane contexts are shared with sfm_extract_views");
+    rc = lane_contexts(ctx, nlanes, lanes);
+    if (rc != SFM_OK) return rc;
     for (int l = 0; l < nlanes; ++l)
         if (!ctx->lane_ev[l]) SFM_HIP_TRY(hipEventCreateWithFlags(&ctx->lane_ev[l], hipEventDisableTiming));
     // ONE pooled Image_pair per lane at the largest size (the reference constructs one per pair: ~20 cudaMalloc / cudaFree each)
@@ -1361,13 +1384,8 @@ int sfm_process_pairs(sfm_ctx *ctx, const float h_K[9], const float h_Kinv[9], c
             }
         }
     }
-    if (ctx->pool_records_cap < (size_t)owned) {
-        SFM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->pool_records) (void)hipFree(ctx->pool_records);
-        ctx->pool_records = nullptr; ctx->pool_records_cap = 0;
-        SFM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->pool_records), (size_t)owned * SFM_RECORD_FLOATS * sizeof(float)));
-        ctx->pool_records_cap = (size_t)owned;
-    }
+    rc = grow(&ctx->pool_records, &ctx->pool_records_cap, (size_t)owned * SFM_RECORD_FLOATS, ctx->stream);
+    if (rc != SFM_OK) return rc;
     // the auxiliary streams start after everything already enqueued on the caller's stream (the features, typically)
     if (nlanes > 1) {
         SFM_HIP_TRY(hipEventRecord(ctx->lane_ev[0], ctx->stream));
@@ -1381,12 +1399,11 @@ int sfm_process_pairs(sfm_ctx *ctx, const float h_K[9], const float h_Kinv[9], c
     bool batched_done = false;
     int slot = 0;
     const bool unbatched_env = getenv("SFM_PAIRS_UNBATCHED") != nullptr;      // A/B and tests: read on EVERY call (sfm_ctx_last_pairs_batched says what ran)
-    const bool unit_z = h_Kinv[6] == 0.0f && h_Kinv[7] == 0.0f && h_Kinv[8] == 1.0f;
-    bool batch = pose_mode == SFM_POSE_REFERENCE && unit_z && owned >= 4 && !unbatched_env;
+    bool batch = pose_mode == SFM_POSE_REFERENCE && unit_z_Kinv(h_Kinv) && owned >= 4 && !unbatched_env;
     ctx->last_pairs_batched = 0;
     uint32_t max_H = 0;
     for (int i = first; i < num_pairs && batch; i += stride) {
-        if (pairs[i].n1 < 8 || (pairs[i].d_sift2 && pairs[i].n2 < 1)) continue;
+        if (!usable(pairs[i])) continue;
         // already matched pairs (no second view given) read match_xpos / match_ypos of the records: not supported by the batch
         // kernels -- such lists take the per-pair loop, decided HERE, before anything has been launched for them
         if (!pairs[i].d_sift2) { batch = false; break; }
@@ -1405,9 +1422,8 @@ int sfm_process_pairs(sfm_ctx *ctx, const float h_K[9], const float h_Kinv[9], c
         int slot_b = 0, max_ld = 0, max_nn = 0;
         for (int i = first; i < num_pairs; i += stride, ++slot_b) {
             const sfm_pair_desc &d = pairs[i];
-            const bool usable = d.n1 >= 8 && (!d.d_sift2 || d.n2 >= 1);
-            if (h_status) h_status[slot_b] = usable ? SFM_OK : SFM_E_INVALID;
-            if (!usable) continue;
+            if (h_status) h_status[slot_b] = usable(d) ? SFM_OK : SFM_E_INVALID;
+            if (!usable(d)) continue;
             PairJob j{};
             j.s1 = d.d_sift1; j.s2 = d.d_sift2; j.n = d.n1; j.ld = round_up(d.n1, 128);
             j.H = num_hypotheses ? num_hypotheses : (uint32_t)(d.n1 / 8);
@@ -1431,13 +1447,8 @@ int sfm_process_pairs(sfm_ctx *ctx, const float h_K[9], const float h_Kinv[9], c
             jobs.push_back(j); job_slot.push_back(slot_b);
         }
         const size_t jobs_bytes = up(jobs.size() * sizeof(PairJob));
-        if (ctx->batch_ws_bytes < bytes + jobs_bytes) {
-            SFM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-            if (ctx->batch_ws) (void)hipFree(ctx->batch_ws);
-            ctx->batch_ws = nullptr; ctx->batch_ws_bytes = 0;
-            SFM_HIP_TRY(hipMalloc(&ctx->batch_ws, bytes + jobs_bytes));
-            ctx->batch_ws_bytes = bytes + jobs_bytes;
-        }
+        rc = grow(&ctx->batch_ws, &ctx->batch_ws_bytes, bytes + jobs_bytes, ctx->stream);
+        if (rc != SFM_OK) return rc;
         char *base = static_cast<char *>(ctx->batch_ws) + jobs_bytes;
         for (PairJob &j : jobs) {
             auto fix = [&](auto *&ptr) { ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(base + reinterpret_cast<size_t>(ptr)); };
@@ -1458,10 +1469,7 @@ int sfm_process_pairs(sfm_ctx *ctx, const float h_K[9], const float h_Kinv[9], c
         for (size_t k = 0; k < jobs.size() && rc == SFM_OK; ) {
             PairJob &j = jobs[k];
             if (!j.s2) { ++k; continue; }
-            size_t v = 0;
-            while (v < first_views.size() && first_views[v] != j.s1) ++v;
-            if (v == first_views.size()) first_views.push_back(j.s1);
-            sfm_ctx *c = lanes[v % (size_t)nlanes];
+            sfm_ctx *c = lane_of_first_view(first_views, j.s1, lanes, nlanes);
             const bool tail = (c->quirks & SFM_QUIRK_MATCH_TAIL) != 0;            // matching.cu:325 (as sfm_match)
             size_t k1 = k;                                                        // the run [k, k1) of pairs with this first view
             std::vector<MatchJob> mj;
@@ -1506,11 +1514,7 @@ int sfm_process_pairs(sfm_ctx *ctx, const float h_K[9], const float h_Kinv[9], c
             }
             ++k;
         }
-        for (int l = 1; l < nlanes; ++l) {
-            const hipError_t e1 = hipEventRecord(ctx->lane_ev[l], lanes[l]->stream);
-            const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(ctx->stream, ctx->lane_ev[l], 0) : e1;
-            if (e2 != hipSuccess && rc == SFM_OK) { set_error("lane join failed: %s", hipGetErrorString(e2)); rc = SFM_E_HIP; }
-        }
+        join_lanes(ctx, lanes, nlanes, &rc);
         if (rc != SFM_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
         {
             // the rest of the chain for ALL pairs of the call: fill_xu_pairs | ransac_pairs_solve + ransac_fused_pairs |
@@ -1532,13 +1536,9 @@ int sfm_process_pairs(sfm_ctx *ctx, const float h_K[9], const float h_Kinv[9], c
     slot = 0;
     for (int i = first; i < num_pairs; i += stride, ++slot) {
         const sfm_pair_desc &d = pairs[i];
-        const bool usable = d.n1 >= 8 && (!d.d_sift2 || d.n2 >= 1);
-        if (h_status) h_status[slot] = usable ? SFM_OK : SFM_E_INVALID;
-        if (!usable) continue;
-        size_t v = 0;
-        while (v < first_views.size() && first_views[v] != d.d_sift1) ++v;
-        if (v == first_views.size()) first_views.push_back(d.d_sift1);
-        sfm_ctx *c = lanes[v % (size_t)nlanes];
+        if (h_status) h_status[slot] = usable(d) ? SFM_OK : SFM_E_INVALID;
+        if (!usable(d)) continue;
+        sfm_ctx *c = lane_of_first_view(first_views, d.d_sift1, lanes, nlanes);
         sfm_pair *ip = c->pool_pair;
         if (d.d_sift2) { rc = sfm_match(c, d.d_sift1, d.n1, d.d_sift2, d.n2); if (rc != SFM_OK) break; }
         rc = sfm_pair_reset(ip, d.n1);                                  if (rc != SFM_OK) break;
@@ -1552,11 +1552,7 @@ int sfm_process_pairs(sfm_ctx *ctx, const float h_K[9], const float h_Kinv[9], c
         if (rc != SFM_OK) break;
     }
     // join the lanes -- also when an enqueue failed: what the lanes already hold must not outlive this call's view of the buffers
-    for (int l = 1; l < nlanes; ++l) {
-        const hipError_t e1 = hipEventRecord(ctx->lane_ev[l], lanes[l]->stream);
-        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(ctx->stream, ctx->lane_ev[l], 0) : e1;
-        if (e2 != hipSuccess && rc == SFM_OK) { set_error("lane join failed: %s", hipGetErrorString(e2)); rc = SFM_E_HIP; }
-    }
+    join_lanes(ctx, lanes, nlanes, &rc);
     if (rc != SFM_OK) {
         (void)hipStreamSynchronize(ctx->stream);
         return rc;
@@ -1570,8 +1566,7 @@ int sfm_process_pairs(sfm_ctx *ctx, const float h_K[9], const float h_Kinv[9], c
     int worst = SFM_OK;
     for (int i = first; i < num_pairs; i += stride, ++slot) {
         float *out = h_records + (size_t)slot * 28;
-        const bool usable = pairs[i].n1 >= 8 && (!pairs[i].d_sift2 || pairs[i].n2 >= 1);
-        if (!usable) { for (int k = 0; k < 28; ++k) out[k] = -1.0f; continue; }
+        if (!usable(pairs[i])) { for (int k = 0; k < 28; ++k) out[k] = -1.0f; continue; }
         memcpy(out, rec.data() + (size_t)slot * SFM_RECORD_FLOATS, 28 * sizeof(float));
         if (rec[(size_t)slot * SFM_RECORD_FLOATS + 28] != 0.0f) {
             if (h_status) h_status[slot] = SFM_E_SINGULAR;

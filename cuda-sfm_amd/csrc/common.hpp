@@ -5,7 +5,9 @@
 #include <stddef.h>
 #include <string>
 #include <atomic>
+#include <type_traits>
 #include "../../include/sfm_amd.h"
+#include "pair_state.hpp"
 #if SFM_AB
 #include "../../include/sfm_amd_ab.h"
 #endif
@@ -37,10 +39,32 @@ void set_error(const char *fmt, ...);
         if (!(cond)) { ::sfm::set_error(__VA_ARGS__); return (code); }                         \
     } while (0)
 
+// a pending pipelined burst (sfm_estimate_E_pipelined) is ordered in front of whatever the entry point enqueues on the context's stream
+#define SFM_FLUSH(pair)                                                                        \
+    do { if ((pair)->pipe_pending) { const int rcf__ = sfm_pair_flush(pair); if (rcf__ != SFM_OK) return rcf__; } } while (0)
+
+// the pair's results the call reads must describe its current points (pair_state.hpp)
+#define SFM_NEED(pair, stages)                                                                 \
+    SFM_REQUIRE((pair)->state.has(stages), SFM_E_STATE, "%s", ::sfm::pair_stage_hint((pair)->state.missing(stages)))
+
 constexpr int kTraceBlocks = 1024;     // blocks of a scoring launch whose start / end stamps are kept (sfm_ransac_last_trace)
 constexpr int kTraceWords = 20;        // per block: start, end of wavefront 0, (XCC id << 32 | hardware id), tile << 32 | column, 16 wavefront ends (100 MHz ticks)
 constexpr int kClkWords = 8 + kTraceBlocks * kTraceWords;
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// Grows a scratch buffer to at least `need` elements (bytes for a void *), contents lost.  What is already enqueued on `st` may
+// still use the old one: wait for it before freeing.
+template <typename T, typename N>
+inline int grow(T **buf, N *have, size_t need, hipStream_t st)
+{
+    if (need <= (size_t)*have) return SFM_OK;
+    SFM_HIP_TRY(hipStreamSynchronize(st));
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr; *have = 0;
+    SFM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(buf), need * sizeof(std::conditional_t<std::is_void<T>::value, char, T>)));
+    *have = (N)need;
+    return SFM_OK;
+}
 
 } // namespace sfm
 
@@ -97,7 +121,7 @@ struct sfm_ctx {
     hipEvent_t views_ev = nullptr;
     float pool_K[9] = {}, pool_Kinv[9] = {};
     float *pool_records = nullptr;
-    size_t pool_records_cap = 0;
+    size_t pool_records_cap = 0;       // floats
     void *batch_ws = nullptr;          // sfm_process_pairs, batched path: the PairJob array + every pair's buffers (pairs_batch.hpp)
     size_t batch_ws_bytes = 0;
     void *sift_job = nullptr;          // the extraction in flight (sift.hip: SiftJob), sfm_extract_sift_begin .. _end
@@ -132,14 +156,13 @@ struct sfm_pair {
     float *d_U[2] = { nullptr, nullptr };
     float *d_X[2] = { nullptr, nullptr };
     float4 *d_pts4 = nullptr;          // (x1x, x1y, x2x, x2y) per correspondence, written by fillXU: ONE 16-byte gather per sampled point
-    bool have_pts4 = false;            // d_pts4 describes the current points (fillXU with the unit-z layout)
     uint32_t sorted_epoch = 0;         // the fillXU epoch d_pts4s was built for
     uint32_t pf_seen_epoch = 0;        // the fillXU epoch of the last pre-filter launch (the first launch of an epoch runs per-hypothesis records)
     int pf_rule = 0;                   // the rule of the launch being issued (prefilter_pick_rule)
     uint32_t *d_buckets = nullptr;     // scratch of the bucket ordering: per-block histograms + bucket bases (pf_bucket_*_kernel)
     size_t bucket_words = 0;
     uint32_t *d_tile_boxes = nullptr;  // eight words per scoring tile of d_pts4s: ordered bits of its coordinate maxima (pf_bucket_scatter_kernel)
-    int boxes_cap = 0, boxes_tile = 0; // tiles allocated / the tile size the boxes were computed for
+    int boxes_words = 0, boxes_tile = 0;   // words allocated / the tile size the boxes were computed for
     float4 *d_pts4s = nullptr;         // the same records in Morton order of the first view's position (pre-filter scoring: tiles with small
                                        // bounding boxes, ransac_prefilter.hip: pf_bucket_*_kernel); built by the second scoring launch after a fillXU (launch_pf_cells)
     float *d_E = nullptr;              // 9
@@ -149,7 +172,6 @@ struct sfm_pair {
     float *d_points = nullptr;         // 4 x n
     uint8_t *d_mask = nullptr;         // n
     unsigned long long *d_key = nullptr;   // [0] packed best of last score, [1] scratch
-    bool key_clean = false;                // d_key is known to be zero (pair creation, fillXU): the next score launch needs no memset
     uint32_t *d_best = nullptr;        // [0] hyp, [1] count of the finalized hypothesis
     // [8 ...]: trace of the last pre-filter scoring launch, kTraceWords per block (sfm_ransac_last_trace)
     unsigned long long *d_clk = nullptr;   // [0] shader-clock ticks, [1] 100 MHz ticks over block 0 of the last ransac_score_waves launch
@@ -161,13 +183,11 @@ struct sfm_pair {
     unsigned long long *d_bound = nullptr; // (fillXU epoch << 32) | bits of the largest |coordinate| <= 48 over all points: atomicMax, never reset;
                                            // words 2..9: the same for the coordinate ranges of the two views (pf_cells_build_kernel; prefilter_math.hpp: pf_box_from_words)
     uint32_t bound_epoch = 0;
-    bool have_bound = false;           // d_bound describes the current points (fillXU)
     uint32_t *d_cells = nullptr;       // pre-filter: open-addressing table of the occupied zero-divisor grid cells of ALL points (launch_pf_cells)
     hipEvent_t cells_ev = nullptr;     // recorded behind the build: launches on ANOTHER stream (two-slot pipelining) wait for it
     hipStream_t cells_stream = nullptr;
     uint32_t cells_cap = 0, cells_mask = 0, cells_epoch = 0;   // slots allocated / in use - 1 / the fillXU epoch the table was built for
     size_t cap_hyps = 0;
-    uint32_t last_count = 0;           // hyp_count of the last score call
     uint32_t cand_h0 = 0, cand_seed = 0;   // what d_Ecand currently holds: shard start, sampler settings
     const int32_t *cand_indices = nullptr;
     int cand_sweeps = 0;
@@ -186,9 +206,7 @@ struct sfm_pair {
     unsigned long long pipe_step = 0;
     bool pipe_pending = false;
     bool holds_ctx_ref = false;        // this pair counts in ctx->refs (every pair but the context's own pooled one)
-    bool have_points = false, have_E = false, have_P = false, have_pose = false;
-    bool have_points3d = false;        // linear_triangulation ran for the current pose (sfm_get_points / VBO export need it)
-    bool unit_z = false;               // every X z-coordinate is exactly 1 (fillXU with K^-1 last row (0 0 1))
+    sfm::PairState state;              // which results are current + what was derived from the points (pair_state.hpp)
     float h_Kinv[9] = {};
     int pose_mode = SFM_POSE_REFERENCE;
     // sfm_refine_two_view: allocated at the first call, sized to cap_points (refine.hip)
@@ -196,7 +214,6 @@ struct sfm_pair {
     float *d_rpoints = nullptr;        // 4 x n refined / re-triangulated points
     float *d_rreproj = nullptr;        // n errors, then n uint8 used flags
     void *d_rwork = nullptr;           // start points of the four candidates, compacted observations / points, index maps, votes
-    bool have_refined = false;         // a refinement ran since the last fillXU / set_points / reset
     // sfm_register_view: allocated at the first call (per-point buffers sized to cap_points, per-hypothesis buffers grown on
     // demand) (register.hip)
     float *d_vstate = nullptr;         // refined + RANSAC pose, report, key, candidate count
@@ -206,7 +223,6 @@ struct sfm_pair {
     int *d_vcounts = nullptr;          // per hypothesis: inlier count
     size_t cap_vhyps = 0;
     uint32_t view_hyps = 0;            // num_hypotheses of the last registration
-    bool have_view = false;            // a registration ran since the last fillXU / set_points / reset
     int last_kernel = 0, last_grid = 0, last_block = 0, last_lds = 0;
 };
 

@@ -324,13 +324,8 @@ int launch_homography(sfm_ctx *ctx, const sfm_sift_point *d_sift, int n, const i
     hipStream_t st = ctx->stream;
     const int ld = round_up(n, 64);
     const size_t need = (size_t)4 * ld * 4 + (size_t)4 * L * 4 + (size_t)8 * L * 4 + (size_t)L * 4 + (size_t)ld * 4 + 64;
-    if (need > ctx->homo_ws_bytes) {
-        SFM_HIP_TRY(hipStreamSynchronize(st));
-        if (ctx->homo_ws) (void)hipFree(ctx->homo_ws);
-        ctx->homo_ws = nullptr; ctx->homo_ws_bytes = 0;
-        SFM_HIP_TRY(hipMalloc(&ctx->homo_ws, need));
-        ctx->homo_ws_bytes = need;
-    }
+    const int rcg = grow(&ctx->homo_ws, &ctx->homo_ws_bytes, need, st);
+    if (rcg != SFM_OK) return rcg;
     char *base = static_cast<char *>(ctx->homo_ws);
     unsigned long long *d_key = reinterpret_cast<unsigned long long *>(base);
     float *d_out = reinterpret_cast<float *>(base + 16);                 // 10 words

@@ -512,13 +512,8 @@ int match_jobs_workspace(sfm_ctx *ctx, int n1, int qblocks, int rows_unit, int r
         j.ws_second = reinterpret_cast<float *>(need);               need += (size_t)round_up(nsplit * n1 * 4, 256);
         j.ws_idx = reinterpret_cast<int *>(need);                    need += (size_t)round_up(nsplit * n1 * 4, 256);
     }
-    if (need > ctx->match_jobs_ws_bytes) {
-        SFM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->match_jobs_ws) (void)hipFree(ctx->match_jobs_ws);
-        ctx->match_jobs_ws = nullptr; ctx->match_jobs_ws_bytes = 0;
-        SFM_HIP_TRY(hipMalloc(&ctx->match_jobs_ws, need));
-        ctx->match_jobs_ws_bytes = need;
-    }
+    const int rcg = grow(&ctx->match_jobs_ws, &ctx->match_jobs_ws_bytes, need, ctx->stream);
+    if (rcg != SFM_OK) return rcg;
     char *base = static_cast<char *>(ctx->match_jobs_ws);
     for (int k = 0; k < njobs; ++k) {
         MatchJob &j = h_jobs[k];
@@ -623,13 +618,10 @@ int launch_match(sfm_ctx *ctx, const float *d1, int n1, int ld1, const float *d2
     // never used, the epoch only grows: a word carries the current epoch only if THIS launch wrote it.
     if (poll) {
         const size_t pneed = (size_t)nsplit * n1 * 24;
-        if (pneed > ctx->match_poll_ws_bytes) {
-            SFM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-            if (ctx->match_poll_ws) (void)hipFree(ctx->match_poll_ws);
-            ctx->match_poll_ws = nullptr; ctx->match_poll_ws_bytes = 0;
-            SFM_HIP_TRY(hipMalloc(&ctx->match_poll_ws, pneed));
+        if (pneed > ctx->match_poll_ws_bytes) {              // a new buffer starts with no epoch in it
+            const int rcg = grow(&ctx->match_poll_ws, &ctx->match_poll_ws_bytes, pneed, ctx->stream);
+            if (rcg != SFM_OK) return rcg;
             SFM_HIP_TRY(hipMemsetAsync(ctx->match_poll_ws, 0, pneed, ctx->stream));
-            ctx->match_poll_ws_bytes = pneed;
         }
         if (++ctx->match_epoch == 0u) {                      // (2^32 launches later: a stale word could carry the new epoch)
             SFM_HIP_TRY(hipMemsetAsync(ctx->match_poll_ws, 0, ctx->match_poll_ws_bytes, ctx->stream));

@@ -370,13 +370,7 @@ void match_pf_exact(const float *__restrict__ q, int nq, int ldq, const float *_
 
 static int match_pf_workspace(sfm_ctx *ctx, size_t need)
 {
-    if (need <= ctx->match_pf_ws_bytes) return SFM_OK;
-    SFM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->match_pf_ws) (void)hipFree(ctx->match_pf_ws);
-    ctx->match_pf_ws = nullptr; ctx->match_pf_ws_bytes = 0;
-    SFM_HIP_TRY(hipMalloc(&ctx->match_pf_ws, need));
-    ctx->match_pf_ws_bytes = need;
-    return SFM_OK;
+    return grow(&ctx->match_pf_ws, &ctx->match_pf_ws_bytes, need, ctx->stream);
 }
 
 template <int CT, int kMpWaves>

@@ -363,11 +363,11 @@ int launch_ransac_score(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0,
     if (d_E_given && family == SFM_KERNEL_FUSED) family = SFM_KERNEL_SPLIT;      // the fused kernel solves its own candidates
     const bool self_clearing = !d_E_given && count > 0 && (family == SFM_KERNEL_SPLIT || family == SFM_KERNEL_PREFILTER);
     if (!self_clearing) {
-        if (!pair->key_clean) SFM_HIP_TRY(hipMemsetAsync(pair->d_key, 0, 2 * sizeof(unsigned long long), ctx->stream));    // (fillXU leaves it cleared)
+        if (!pair->state.key_clean) SFM_HIP_TRY(hipMemsetAsync(pair->d_key, 0, 2 * sizeof(unsigned long long), ctx->stream));    // (fillXU leaves it cleared)
         if (key2) SFM_HIP_TRY(hipMemsetAsync(key2, 0, sizeof(unsigned long long), ctx->stream));
     }
-    pair->key_clean = false;
-    pair->last_count = count;
+    pair->state.key_clean = false;
+    pair->state.last_count = count;
     pair->cand_h0 = h0; pair->cand_seed = p.seed; pair->cand_indices = p.d_indices; pair->cand_sweeps = p.jacobi_sweeps;
     pair->cand_given = d_E_given != nullptr;
     if (count == 0) return SFM_OK;
@@ -417,7 +417,7 @@ int launch_ransac_score(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0,
     if (timed) SFM_HIP_TRY(hipEventRecord(tev[0], ctx->stream));
     const bool pf_tickets = prefilter && (SFM_SW(p, 3) == 2 || SFM_SW(p, 3) == 17);      // (AB build: kernels that sum into counts[] and draw tickets)
     int *zero_counts = (grid2d || pf_tickets) ? pair->d_counts : nullptr;
-    const float4 *pts4 = (pair->have_pts4 && SFM_SW(p, 0) != 4) ? pair->d_pts4 : nullptr;      // (AB build, reserved[0] == 4: scattered gathers)
+    const float4 *pts4 = (pair->state.have_pts4 && SFM_SW(p, 0) != 4) ? pair->d_pts4 : nullptr;      // (AB build, reserved[0] == 4: scattered gathers)
     // pre-filter kernel: one 64-bit accumulator per hypothesis (count | tiles arrived; round 3: a ticket per 32 hypotheses next to
     // zeroed counts), cleared by the solve kernel (or by a memset when there is none); its per-hypothesis records come from the
     // lane-solve kernel itself on the default path, from pf_prep_kernel otherwise
@@ -482,7 +482,7 @@ int launch_ransac_score(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0,
     if (timed) SFM_HIP_TRY(hipEventRecord(tev[1], ctx->stream));
 
     // unit-z layout: fixed 64 KiB (two arrays of kTileMax/2 pair records); generic: 24 B per point
-    const bool uz = pair->unit_z;
+    const bool uz = pair->state.unit_z;
     const size_t lds = (uz ? (size_t)2 * kUnitZSecond : (size_t)6 * tile * sizeof(float)) + 16 * sizeof(unsigned long long);   // tile + bound / per-wave maxima
     // blocks: at least as many as are co-resident (LDS and the 2048-thread CU limit); with plenty of work 16 per CU, each
     // still running >= 8 batches over its staged tile -- finer grains let the dispatcher even out the tail (measured on

@@ -407,7 +407,7 @@ int launch_ransac_fused(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0,
     while (wpb > 4 && (count + wpb - 1) / wpb < (uint32_t)ctx->num_cus) wpb >>= 1;
     const uint32_t nbatch = (count + wpb - 1) / wpb;
     const int grid = (int)(nbatch < (uint32_t)ctx->num_cus ? nbatch : (uint32_t)ctx->num_cus);
-    const bool uz = pair->unit_z;
+    const bool uz = pair->state.unit_z;
     const size_t lds = (uz ? (size_t)2 * kUnitZSecond : (size_t)6 * tile * sizeof(float)) + (size_t)wpb * kWaveScratch * sizeof(float) +
                        9 * 64 * sizeof(uint2);                                                          // tile + wave scratches + Jacobi schedule
     const bool timed = ctx->timing && ctx->tcount < sfm_ctx::kTimingSlots;
@@ -427,12 +427,12 @@ int launch_finalize_block(sfm_pair *pair, const sfm_ransac_params &p, const unsi
 {
     // Ecand is only trusted when it was produced by a score call with the same sampler settings (and when the caller
     // does not overlap this finalize with the next score call, which rewrites it: rederive)
-    const bool cand_ok = !rederive && pair->last_count > 0 && pair->cand_seed == p.seed && pair->cand_indices == p.d_indices &&
+    const bool cand_ok = !rederive && pair->state.last_count > 0 && pair->cand_seed == p.seed && pair->cand_indices == p.d_indices &&
                          pair->cand_sweeps == p.jacobi_sweeps;
     hipLaunchKernelGGL(ransac_finalize_block, dim3(1), dim3(1024), 0, stream,
                        pair->d_X[0], pair->d_X[1], pair->ld, pair->n, p.d_indices, p.seed, p.jacobi_sweeps,
                        d_key, hyp_host, from_key ? 1 : 0,
-                       cand_ok ? pair->d_Ecand : nullptr, pair->cand_h0, pair->last_count, p.num_hypotheses,
+                       cand_ok ? pair->d_Ecand : nullptr, pair->cand_h0, pair->state.last_count, p.num_hypotheses,
                        p.threshold, pair->d_E, pair->d_mask, pair->d_best);
     SFM_HIP_TRY(hipGetLastError());
     return SFM_OK;

@@ -989,13 +989,8 @@ int launch_pf_cells(sfm_pair *pair, bool want_sorted, int tile)
     if (!cells_ok) {
         uint32_t slots = 4096;
         while (slots < 8u * (uint32_t)pair->n) slots <<= 1;                              // two keys per point, load factor <= 1/4
-        if (slots > pair->cells_cap) {
-            SFM_HIP_TRY(hipStreamSynchronize(st));
-            if (pair->d_cells) (void)hipFree(pair->d_cells);
-            pair->d_cells = nullptr; pair->cells_cap = 0;
-            SFM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pair->d_cells), (size_t)slots * sizeof(uint32_t)));
-            pair->cells_cap = slots;
-        }
+        const int rcg = grow(&pair->d_cells, &pair->cells_cap, slots, st);
+        if (rcg != SFM_OK) return rcg;
         pair->cells_mask = slots - 1u;
         SFM_HIP_TRY(hipMemsetAsync(pair->d_cells, 0, (size_t)slots * sizeof(uint32_t), st));
     }
@@ -1004,21 +999,12 @@ int launch_pf_cells(sfm_pair *pair, bool want_sorted, int tile)
     const int ntiles = want_sorted ? (pair->ld + tile - 1) / tile : 0;
     if (!order_ok) {                                                                 // scratch of the bucket ordering, the ordered copy, the tiles' boxes
         const size_t words = (size_t)(nblk + 1) * kPfBuckets;
-        if (words > pair->bucket_words || ntiles > pair->boxes_cap || !pair->d_pts4s) {
+        int rcg = grow(&pair->d_buckets, &pair->bucket_words, words, st);
+        if (rcg == SFM_OK) rcg = grow(&pair->d_tile_boxes, &pair->boxes_words, (size_t)ntiles * 8, st);
+        if (rcg != SFM_OK) return rcg;
+        if (!pair->d_pts4s) {
             SFM_HIP_TRY(hipStreamSynchronize(st));
-            if (words > pair->bucket_words) {
-                if (pair->d_buckets) (void)hipFree(pair->d_buckets);
-                pair->d_buckets = nullptr; pair->bucket_words = 0;
-                SFM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pair->d_buckets), words * sizeof(uint32_t)));
-                pair->bucket_words = words;
-            }
-            if (ntiles > pair->boxes_cap) {
-                if (pair->d_tile_boxes) (void)hipFree(pair->d_tile_boxes);
-                pair->d_tile_boxes = nullptr; pair->boxes_cap = 0;
-                SFM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pair->d_tile_boxes), (size_t)ntiles * 8 * sizeof(uint32_t)));
-                pair->boxes_cap = ntiles;
-            }
-            if (!pair->d_pts4s) SFM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pair->d_pts4s), (size_t)pair->ld * sizeof(float4)));
+            SFM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pair->d_pts4s), (size_t)pair->ld * sizeof(float4)));
         }
         hist = pair->d_buckets; base = pair->d_buckets + (size_t)nblk * kPfBuckets;
     }
@@ -1288,7 +1274,7 @@ bool prefilter_usable(const sfm_pair *pair, const sfm_ransac_params &p, uint32_t
 {
     PfScales sc;
     // (enough work: 2^27 pairs -- 131072 block passes of 32 hypotheses x 1024 points in the geometry the crossover was measured with)
-    return pair->unit_z && pair->have_bound && count >= 16384u && (uint64_t)count * (uint64_t)pair->ld >= (1ull << 27) && prefilter_scales(p.threshold, sc);
+    return pair->state.unit_z && pair->state.have_bound && count >= 16384u && (uint64_t)count * (uint64_t)pair->ld >= (1ull << 27) && prefilter_scales(p.threshold, sc);
 }
 
 // points per tile of a launch on this pair (AB build, reserved[1] == 7: up to 1536 points with the band rule)

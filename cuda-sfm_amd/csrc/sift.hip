@@ -779,17 +779,6 @@ static void laplace_taps(int num_octaves, float init_blur, LapTaps *tables /* in
     }
 }
 
-static int grow(void **buf, size_t *have, size_t need, hipStream_t st)
-{
-    if (need <= *have) return SFM_OK;
-    SFM_HIP_TRY(hipStreamSynchronize(st));
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr; *have = 0;
-    SFM_HIP_TRY(hipMalloc(buf, need));
-    *have = need;
-    return SFM_OK;
-}
-
 // One extraction in flight per context (sfm_extract_sift_begin .. sfm_extract_sift_end): everything the second half needs.
 struct SiftJob {
     bool pending = false;
