@@ -17,6 +17,7 @@
 // (order-independent, so the result is deterministic); the wavefront that adds the last tile of a hypothesis group folds its
 // keys into the shard's arg-max key.
 #include "ransac_device.hpp"
+#include "block_ops.hpp"
 #include "prefilter_math.hpp"
 
 namespace sfm {
@@ -357,11 +358,7 @@ void ransac_score_prefilter_r2(const float *__restrict__ X0, const float *__rest
                 const int c = __hip_atomic_load(&counts[h_first + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 k = pack_key((uint32_t)c, h0 + h_first + (uint32_t)lane);
             }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const unsigned long long o = __shfl_xor(k, off);
-                k = o > k ? o : k;
-            }
+            k = wave_max(k);
             if (lane == 0 && k) {
                 atomicMax(best_key, k);
                 if (best_key2) atomicMax(best_key2, k);

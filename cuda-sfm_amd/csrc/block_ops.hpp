@@ -1,0 +1,71 @@
+// block_ops.hpp -- the wavefront and block primitives the kernels share (device code only; wavefronts of 64 lanes).
+// Each exists once, so that where the barriers sit and in which order a sum is taken is decided in one place.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace sfm {
+
+// A wavefront-uniform value moved into a scalar register: what every lane reads alike (a pose, K, a step) stays out of the
+// vector registers.
+__device__ __forceinline__ float uniform(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
+
+// Maximum over the wavefront, in every lane: folds packed arg-max keys (pack_key: count << 32 | ~id, so the first maximum wins).
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long k)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(k, off);
+        k = o > k ? o : k;
+    }
+    return k;
+}
+
+// Sum of N doubles over a block of WAVES wavefronts in a fixed order -- wave butterflies, then the wave partials in wave
+// order -- so the result is the same bit for bit on every run.  s_part: LDS [WAVES * N]; every thread returns with the
+// totals in s_out (LDS [N]).  Both may be reused as soon as the totals have been read: the call ends with a barrier, and a
+// later call writes s_out only behind its first one.
+template <int WAVES, int N>
+__device__ __forceinline__ void block_sum(double (&v)[N], double *s_part, double *s_out)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        double x = v[q];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+        if (lane == 0) s_part[wave * N + q] = x;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < N) {
+        double s = s_part[threadIdx.x];
+        for (int w = 1; w < WAVES; ++w) s += s_part[w * N + threadIdx.x];
+        s_out[threadIdx.x] = s;
+    }
+    __syncthreads();
+}
+
+// Exclusive scan of one value per thread over a block of WAVES wavefronts: returns the sum of the lower threads' values and
+// leaves the total in wsum[WAVES] (wsum: LDS [WAVES + 1]).  Two barriers, none in front: a caller that scans again with the
+// same wsum puts a __syncthreads() between its last read of wsum and the next call.
+template <int WAVES, class T>
+__device__ __forceinline__ T block_scan(T v, T *wsum)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const T u = __shfl_up(inc, d);
+        if (lane >= d) inc += u;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        T acc = 0;
+        for (int i = 0; i < WAVES; ++i) { const T t = wsum[i]; wsum[i] = acc; acc += t; }
+        wsum[WAVES] = acc;
+    }
+    __syncthreads();
+    return wsum[wave] + inc - v;
+}
+
+} // namespace sfm

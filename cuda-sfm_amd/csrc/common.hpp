@@ -66,6 +66,20 @@ inline int grow(T **buf, N *have, size_t need, hipStream_t st)
     return SFM_OK;
 }
 
+// Consecutive arrays carved out of one device buffer.  A buffer's layout is ONE function that takes its arrays from a Carver
+// and returns used: run over the buffer it yields the pointers, run over a null base the size to allocate.
+struct Carver {
+    uintptr_t base;
+    size_t used = 0;
+    explicit Carver(void *buffer) : base(reinterpret_cast<uintptr_t>(buffer)) {}
+    template <typename T> T *take(size_t count)
+    {
+        T *p = reinterpret_cast<T *>(base + used);
+        used += count * sizeof(T);
+        return p;
+    }
+};
+
 } // namespace sfm
 
 struct sfm_ctx {

@@ -11,6 +11,7 @@
 //   - arg-max and the winner's 3x3 stay on the device until one 36-byte copy.
 #include "common.hpp"
 #include "device_math.hpp"
+#include "block_ops.hpp"
 
 namespace sfm {
 
@@ -37,23 +38,8 @@ void homo_gate_kernel(const sfm_sift_point *__restrict__ s, int n, float min_sco
     const int lo = min(n, (int)threadIdx.x * per), hi = min(n, lo + per);
     unsigned int mine = 0;
     for (int i = lo; i < hi; ++i) mine += (s[i].score > min_score && s[i].ambiguity < max_ambiguity) ? 1u : 0u;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned int inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned int u = __shfl_up(inc, d);
-        if (lane >= d) inc += u;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned int acc = 0;
-        for (int i = 0; i < 16; ++i) { const unsigned int t = wsum[i]; wsum[i] = acc; acc += t; }
-        wsum[16] = acc;
-        *nv_out = acc;
-    }
-    __syncthreads();
-    unsigned int run = wsum[wave] + inc - mine;
+    unsigned int run = block_scan<16>(mine, wsum);
+    if (threadIdx.x == 0) *nv_out = wsum[16];
     for (int i = lo; i < hi; ++i)
         if (s[i].score > min_score && s[i].ambiguity < max_ambiguity) valid[run++] = i;
 }
@@ -264,11 +250,10 @@ void homo_score_kernel(const float *__restrict__ coord, int ld, int n, const flo
         for (int batch = blockIdx.x; batch < nbatch; batch += gridDim.x) {
             const int l = __builtin_amdgcn_readfirstlane(batch * WPB + wave);
             if (l >= L) continue;
-            auto sreg = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
             float a[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) a[k] = sreg(homo[k * L + l]);
-            const float th = sreg(thresh2);
+            for (int k = 0; k < 8; ++k) a[k] = uniform(homo[k * L + l]);
+            const float th = uniform(thresh2);
             int cnt = 0;
             for (int i0 = 0; i0 < len; i0 += 64) {
                 const int i = i0 + lane;

@@ -19,6 +19,7 @@
 //
 // Work per (hypothesis, point): 38 FLOP; per hypothesis: 720 FLOP (A^T A) + solver.
 #include "ransac_device.hpp"
+#include "block_ops.hpp"
 #include "prefilter_record.hpp"
 
 namespace sfm {
@@ -210,13 +211,12 @@ void ransac_score_waves(const float *__restrict__ X0, const float *__restrict__ 
             const uint32_t i = __builtin_amdgcn_readfirstlane((batch * WPB + wave) * NH);
             if (i >= count) continue;
             const int nh = (int)min((uint32_t)NH, count - i);                 // wave-uniform: 1 only at the very end of the range
-            auto sreg = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
             Ess E[NH];
             bool e_tame = true;
 #pragma unroll
             for (int h = 0; h < NH; ++h) {
                 const float *e = Ecand + 9 * (size_t)(i + (h < nh ? h : 0));
-                E[h] = Ess{ sreg(e[0]), sreg(e[1]), sreg(e[2]), sreg(e[3]), sreg(e[4]), sreg(e[5]), sreg(e[6]), sreg(e[7]), sreg(e[8]) };
+                E[h] = Ess{ uniform(e[0]), uniform(e[1]), uniform(e[2]), uniform(e[3]), uniform(e[4]), uniform(e[5]), uniform(e[6]), uniform(e[7]), uniform(e[8]) };
                 // a normalised E has entries <= 1; anything else (degenerate sample -> NaN / inf) keeps the full range tracking
                 e_tame = e_tame && fabsf(E[h].e0) <= 2.0f && fabsf(E[h].e1) <= 2.0f && fabsf(E[h].e2) <= 2.0f && fabsf(E[h].e3) <= 2.0f &&
                          fabsf(E[h].e4) <= 2.0f && fabsf(E[h].e5) <= 2.0f && fabsf(E[h].e6) <= 2.0f && fabsf(E[h].e7) <= 2.0f && fabsf(E[h].e8) <= 2.0f;
@@ -288,11 +288,7 @@ void ransac_argmax_counts(const int *__restrict__ counts, uint32_t h0, uint32_t 
         const unsigned long long key = pack_key((uint32_t)counts[i], h0 + i);
         b = key > b ? key : b;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(b, off);
-        b = o > b ? o : b;
-    }
+    b = wave_max(b);
     if ((threadIdx.x & 63) == 0) sbest[threadIdx.x >> 6] = b;
     __syncthreads();
     if (threadIdx.x == 0) {

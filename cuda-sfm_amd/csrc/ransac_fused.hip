@@ -17,6 +17,7 @@
 // hypothesis is latency-bound, and 63 short rounds on one wavefront beat one lane grinding through
 // the fully unrolled 44k-instruction solver.
 #include "ransac_device.hpp"
+#include "block_ops.hpp"
 #include "pairs_batch.hpp"
 
 namespace sfm {
@@ -226,8 +227,7 @@ __device__ __forceinline__ void fused_body(float *lds, const float *__restrict__
             }
         }
         // every lane holds the same E: move it to scalar registers (the scoring loop reads E as SGPR operands)
-        auto sreg = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-        const Ess E{ sreg(e[0]), sreg(e[1]), sreg(e[2]), sreg(e[3]), sreg(e[4]), sreg(e[5]), sreg(e[6]), sreg(e[7]), sreg(e[8]) };
+        const Ess E{ uniform(e[0]), uniform(e[1]), uniform(e[2]), uniform(e[3]), uniform(e[4]), uniform(e[5]), uniform(e[6]), uniform(e[7]), uniform(e[8]) };
         int cnt = 0;
         for (int t = 0; t < ntiles; ++t) {
             if (ntiles > 1 || !staged) {

@@ -22,6 +22,7 @@
 //   * partial counts reach counts[] through integer atomics (order-independent, so the result is deterministic); the
 //     wavefront that adds the last tile of a 32-hypothesis group folds its keys into the shard's arg-max key.
 #include "ransac_device.hpp"
+#include "block_ops.hpp"
 #include "prefilter_math.hpp"
 #include "prefilter_record.hpp"
 
@@ -373,7 +374,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
     if (kTile) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) bw[k] = (uint32_t)__builtin_amdgcn_readlane((int)bw_lane, k);
-        pf_B = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(pf_B)));
+        pf_B = uniform(pf_B);
         tbox = pf_box_from_bits(bw, pf_B);
         if (have) build_operands(e_row, key0);
     }
@@ -732,11 +733,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
                 const int c = __hip_atomic_load(&counts[h_first + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 k = pack_key((uint32_t)c, h0 + h_first + (uint32_t)lane);
             }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const unsigned long long o = __shfl_xor(k, off);
-                k = o > k ? o : k;
-            }
+            k = wave_max(k);
             if (lane == 0 && k) {
                 atomicMax(best_key, k);
                 if (best_key2) atomicMax(best_key2, k);
@@ -775,11 +772,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
         // the shard's key is only touched when this one beats what it was seen to hold (a stale, i.e. smaller, value read
         // there costs an atomic, never a result: the key only grows)
         if (__ballot(k != 0ull) != 0ull) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const unsigned long long o = __shfl_xor(k, off);
-                k = o > k ? o : k;
-            }
+            k = wave_max(k);
             if (lane == 0 && k > __hip_atomic_load(best_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
                 atomicMax(best_key, k);
                 if (best_key2) atomicMax(best_key2, k);
@@ -851,23 +844,7 @@ void pf_bucket_scan_kernel(uint32_t *__restrict__ hist, int nblocks, uint32_t *_
     __syncthreads();
     // exclusive scan of the 1024 Morton buckets' totals over the block (one per thread), the two special buckets behind them
     __shared__ uint32_t wsum[17];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t mine = total[threadIdx.x];
-    uint32_t v = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(v, off);
-        if (lane >= off) v += t;
-    }
-    if (lane == 63) wsum[wave] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t run = 0u;
-        for (int w = 0; w < 16; ++w) { const uint32_t c = wsum[w]; wsum[w] = run; run += c; }
-        wsum[16] = run;
-    }
-    __syncthreads();
-    base[threadIdx.x] = wsum[wave] + v - mine;
+    base[threadIdx.x] = block_scan<16>(total[threadIdx.x], wsum);
     if (threadIdx.x == 0) { base[1024] = wsum[16]; base[1025] = wsum[16] + total[1024]; }
 }
 static_assert(kPfBuckets == 1026, "pf_bucket_scan_kernel: 1024 Morton buckets scanned by 1024 threads + two special ones");

@@ -10,10 +10,14 @@
 //                         Cholesky on one lane, the back substitution and the cost of the tentative step -- and writes the
 //                         refined pose, E and the report.
 //   refine_finish_kernel  grid over points: refined point or DLT against the refined pose, reprojection errors, used flags.
-// Reductions: per-thread fp64 sums in a fixed point order, wave butterflies, then the wave partials in wave order -- no float
-// atomics, so the result is the same bit for bit on every run.
+// Reductions: per-thread fp64 sums in a fixed point order, then block_sum (block_ops.hpp: wave butterflies, the wave partials in
+// wave order) -- no float atomics, so the result is the same bit for bit on every run.
+// The damping schedule, the accept test, the stop rules and the report's bookkeeping are LmControl's (refine_math.hpp), which
+// register.hip's pose-only LM drives too; the rotation update and the 4 x 4 pose store are shared the same way.  The system,
+// its solve, the translation update and the commit are this kernel's own.
 #include "common.hpp"
 #include "device_math.hpp"
+#include "block_ops.hpp"
 #include "refine_math.hpp"
 
 namespace sfm {
@@ -82,31 +86,6 @@ void refine_start_kernel(RefineArgs a)
         for (int k = 0; k < 64; ++k) a.state[kStP + k] = p[k];
     }
 }
-
-// Sum of N doubles over the block, in a fixed order; every thread returns with the totals in s_out.
-template <int N>
-__device__ __forceinline__ void block_sum(double (&v)[N], double *s_part, double *s_out)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-        double x = v[q];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-        if (lane == 0) s_part[wave * N + q] = x;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < N) {
-        double s = s_part[threadIdx.x];
-        for (int w = 1; w < kRefineWaves; ++w) s += s_part[w * N + threadIdx.x];
-        s_out[threadIdx.x] = s;
-    }
-    __syncthreads();
-}
-
-// A block-uniform value read from LDS, moved into a scalar register: the pose, K and the step stay out of the 128 VGPRs the
-// 1024-thread block allows (the per-thread fp64 sums of the reduced system alone take 50).
-__device__ __forceinline__ float uniform(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
 
 __device__ __forceinline__ void load_pose(const float *s, RefinePose &P)
 {
@@ -212,17 +191,14 @@ void refine_solve_kernel(RefineArgs a)
             v[0] += (double)rho1 + (double)rho2;
             v[1] += (double)(r[0] * r[0] + r[1] * r[1]) + (double)(r[2] * r[2] + r[3] * r[3]);
         }
-        block_sum<2>(v, s_part, s_tot);
+        block_sum<kRefineWaves>(v, s_part, s_tot);
     }
-    double cost = s_tot[0], sq = s_tot[1];
-    const float initial_rms = m > 0 ? (float)sqrt(sq / (4.0 * m)) : 0.0f;
-    double lambda = a.lambda0;
-    int iters = 0, accepted = 0, status = SFM_REFINE_MAX_ITER;
+    LmControl lm(a.lambda0, s_tot[0], s_tot[1], m < kRefineMinPoints);
+    const float initial_rms = m > 0 ? (float)sqrt(lm.sq / (4.0 * m)) : 0.0f;
     int cur = 0;                                          // Xa (0) or Xb (1) holds the committed points
-    if (m < kRefineMinPoints) status = SFM_REFINE_DEGENERATE;
 
-    while (status != SFM_REFINE_DEGENERATE && iters < a.max_iter) {
-        const float lam = uniform((float)lambda);
+    while (lm.running(a.max_iter)) {
+        const float lam = uniform((float)lm.lambda);
         const float4 *Xc = cur ? a.Xb : a.Xa;
         float4 *Xn = cur ? a.Xa : a.Xb;
         // ---- pass A: the reduced camera system ----
@@ -239,24 +215,22 @@ void refine_solve_kernel(RefineArgs a)
             refine_point_block(J, w1, w2, lam, Vi, Wm, gp);
             refine_schur(J, w2, Vi, Wm, gp, [&](int q, float v) { sys[q] += (double)v; });
         }
-        block_sum<kSysValues>(sys, s_part, s_tot);
+        block_sum<kRefineWaves>(sys, s_part, s_tot);
         // ---- the pose step on one lane ----
         if (tid == 0) {
             double Sd[15], dc[5];
 #pragma unroll
             for (int q = 0; q < 15; ++q) Sd[q] = s_tot[q];
 #pragma unroll
-            for (int q = 0; q < 5; ++q) { Sd[sym5(q, q)] += lambda * s_tot[20 + q]; dc[q] = -s_tot[15 + q]; }
+            for (int q = 0; q < 5; ++q) { Sd[sym5(q, q)] += lm.lambda * s_tot[20 + q]; dc[q] = -s_tot[15 + q]; }
             const bool ok = refine_solve5(Sd, dc);
             s_go = ok ? 1 : 0;
             if (ok) {
-                double E[9], t[3], nn = 0.0;
-                refine_expso3(dc, E);
+                double t[3], nn = 0.0;
+                float Rn[9];
+                refine_rotate(dc, s_pose, Rn);
 #pragma unroll
-                for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c)
-                        s_try[3 * r + c] = (float)(E[3 * r] * (double)s_pose[c] + E[3 * r + 1] * (double)s_pose[3 + c] + E[3 * r + 2] * (double)s_pose[6 + c]);
+                for (int q = 0; q < 9; ++q) s_try[q] = Rn[q];
 #pragma unroll
                 for (int q = 0; q < 3; ++q) { t[q] = (double)s_pose[9 + q] + (double)s_pose[12 + q] * dc[3] + (double)s_pose[15 + q] * dc[4]; nn += t[q] * t[q]; }
                 nn = sqrt(nn);
@@ -268,10 +242,8 @@ void refine_solve_kernel(RefineArgs a)
             }
         }
         __syncthreads();
-        ++iters;
         if (!s_go) {                                      // not positive definite: more damping
-            lambda *= 10.0;
-            if (lambda > 1e16) break;
+            if (!lm.solve_failed()) break;
             continue;
         }
         // ---- pass B: point steps and the cost of the tentative state ----
@@ -297,47 +269,34 @@ void refine_solve_kernel(RefineArgs a)
             v[0] += (double)rho1 + (double)rho2;
             v[1] += (double)(r[0] * r[0] + r[1] * r[1]) + (double)(r[2] * r[2] + r[3] * r[3]);
         }
-        block_sum<2>(v, s_part, s_tot);
-        const double nc = s_tot[0];
-        if (nc < cost) {                                  // accept: commit pose and points, less damping
-            const double rel = (cost - nc) / cost;
-            cost = nc; sq = s_tot[1];
+        block_sum<kRefineWaves>(v, s_part, s_tot);
+        bool stop;
+        if (lm.tentative(s_tot[0], s_tot[1], (double)a.min_rel, stop)) {     // accepted: commit pose and points
             cur ^= 1;
-            ++accepted;
-            lambda /= 10.0;
             P = Pt;
             __syncthreads();                              // every lane has read s_pose / s_try for this iteration
             if (tid < 18) s_pose[tid] = s_try[tid];
             __syncthreads();
-            if (!(rel >= (double)a.min_rel)) { status = SFM_REFINE_CONVERGED; break; }
-        } else {
-            lambda *= 10.0;
-            if (lambda > 1e16) break;
         }
+        if (stop) break;
     }
 
     // ---- refined pose, E = [t]x R, report; the used points into slot order for the finish kernel ----
     if (tid == 0) {
         float *Po = a.state + kStPose;
         const float *R = s_pose, *t = s_pose + 9;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) Po[4 * r + c] = R[3 * r + c];
-            Po[4 * r + 3] = t[r];
-        }
-        Po[12] = 0.0f; Po[13] = 0.0f; Po[14] = 0.0f; Po[15] = 1.0f;
+        refine_store_pose(s_pose, Po);
         const float tx[9] = { 0.0f, -t[2], t[1], t[2], 0.0f, -t[0], -t[1], t[0], 0.0f };
 #pragma unroll
         for (int r = 0; r < 3; ++r)
 #pragma unroll
             for (int c = 0; c < 3; ++c) Po[16 + 3 * r + c] = tx[3 * r] * R[c] + tx[3 * r + 1] * R[3 + c] + tx[3 * r + 2] * R[6 + c];
         sfm_refine_report rep;
-        rep.status = status; rep.iterations = iters; rep.accepted = accepted; rep.num_used = m; rep.pose_index = pi;
+        rep.status = lm.status; rep.iterations = lm.iters; rep.accepted = lm.accepted; rep.num_used = m; rep.pose_index = pi;
         rep.initial_rms_px = initial_rms;
-        rep.final_rms_px = m > 0 ? (float)sqrt(sq / (4.0 * m)) : 0.0f;
-        rep.final_cost = (float)cost;
-        rep.lambda = (float)lambda;
+        rep.final_rms_px = m > 0 ? (float)sqrt(lm.sq / (4.0 * m)) : 0.0f;
+        rep.final_cost = (float)lm.cost;
+        rep.lambda = (float)lm.lambda;
         *reinterpret_cast<sfm_refine_report *>(a.state + kStReport) = rep;
         s_cur = cur;
     }
@@ -384,6 +343,21 @@ void refine_finish_kernel(RefineArgs a)
     reinterpret_cast<uint8_t *>(a.reproj + a.n)[j] = k >= 0 ? 1 : 0;
 }
 
+// pair->d_rwork for cap_points points: the arrays of `a` inside it; returns its size in bytes
+static size_t refine_work_layout(void *buffer, int cap_points, RefineArgs &a)
+{
+    const size_t cap = (size_t)cap_points;
+    Carver w(buffer);
+    a.cand = w.take<float4>(4 * cap);
+    a.obs = w.take<float4>(cap);
+    a.Xa = w.take<float4>(cap);
+    a.Xb = w.take<float4>(cap);
+    a.votes = w.take<int>(4 * (size_t)((cap_points + kStartPoints - 1) / kStartPoints));
+    a.idx = w.take<int>(cap);
+    a.slot = w.take<int>(cap);
+    return w.used;
+}
+
 int launch_refine(sfm_pair *pair, const sfm_refine_params &p)
 {
     RefineArgs a;
@@ -393,15 +367,7 @@ int launch_refine(sfm_pair *pair, const sfm_refine_params &p)
     a.huber = p.huber_px; a.min_rel = p.min_rel_decrease; a.lambda0 = p.initial_lambda; a.max_iter = p.max_iterations;
     a.state = pair->d_rstate;
     a.points = pair->d_rpoints; a.reproj = pair->d_rreproj;
-    const size_t cap = (size_t)pair->cap_points;
-    char *w = static_cast<char *>(pair->d_rwork);
-    a.cand = reinterpret_cast<float4 *>(w);  w += 4 * cap * sizeof(float4);
-    a.obs = reinterpret_cast<float4 *>(w);   w += cap * sizeof(float4);
-    a.Xa = reinterpret_cast<float4 *>(w);    w += cap * sizeof(float4);
-    a.Xb = reinterpret_cast<float4 *>(w);    w += cap * sizeof(float4);
-    a.votes = reinterpret_cast<int *>(w);    w += 4 * sizeof(int) * (size_t)((pair->cap_points + kStartPoints - 1) / kStartPoints);
-    a.idx = reinterpret_cast<int *>(w);      w += cap * sizeof(int);
-    a.slot = reinterpret_cast<int *>(w);
+    refine_work_layout(pair->d_rwork, pair->cap_points, a);
     hipStream_t st = pair->ctx->stream;
     const int nb = (pair->n + kStartPoints - 1) / kStartPoints;
     hipLaunchKernelGGL(refine_start_kernel, dim3(nb), dim3(256), 0, st, a);
@@ -415,8 +381,8 @@ int launch_refine(sfm_pair *pair, const sfm_refine_params &p)
 
 size_t refine_work_bytes(int cap_points)
 {
-    const size_t cap = (size_t)cap_points;
-    return 7 * cap * sizeof(float4) + 2 * cap * sizeof(int) + 4 * sizeof(int) * (size_t)((cap_points + kStartPoints - 1) / kStartPoints);
+    RefineArgs a;
+    return refine_work_layout(nullptr, cap_points, a);
 }
 
 int refine_state_words() { return kStWords; }

@@ -4,9 +4,12 @@
 // frame); shared: the pose increment dc = (omega (3), dt (2)) with R <- exp([omega]x) R and t <- normalize(t + b1 dt0 + b2 dt1),
 // where b1, b2 span the tangent plane of the unit sphere at t.  Residuals are pixels: K2x2 (pi(Y) - x / z) per view with
 // K2x2 = [[fx, s], [0, fy]] (the exact pixel error for any upper-triangular K).  Everything here is fp32; refine.hip sums the
-// per-point terms in fp64.  Compiled as HIP host code by tests/hostcheck/refinecheck.hip for the CPU tests.
+// per-point terms in fp64.  At the end: what the one-block LM kernels (refine.hip, register.hip) share beyond the per-point terms --
+// LmControl (damping schedule, accept test, stop rules, bookkeeping), the rotation update and the pose store.
+// Compiled as HIP host code by tests/hostcheck/refinecheck.hip and lmcheck.hip for the CPU tests.
 #pragma once
 #include "device_math.hpp"
+#include "../../include/sfm_amd.h"
 
 namespace sfm {
 
@@ -223,5 +226,69 @@ SFM_HD bool refine_cholesky(double S[N * (N + 1) / 2], double x[N])
 }
 
 SFM_HD bool refine_solve5(double S[15], double x[5]) { return refine_cholesky<5>(S, x); }
+
+// The control of a Levenberg-Marquardt chain, the same for every solver here: ten times the damping after a failed solve or a
+// rejected step, a tenth after an accepted one; a step is accepted when it lowers the cost; the chain ends after max_iterations,
+// when an accepted step lowered the cost by less than min_rel of it (CONVERGED), or when lambda has passed 1e16.  Every lane of
+// the block keeps its own copy and feeds it the same block-uniform values; the report is filled from lane 0's.  No device
+// intrinsics: tests/test_lm_control_host.py replays event sequences through the host build.
+struct LmControl {
+    double lambda, cost, sq;              // damping; cost and sum of squared residuals of the committed state
+    int iters, accepted, status;          // status: SFM_REFINE_*
+
+    SFM_HD LmControl(double lambda0, double cost0, double sq0, bool degenerate)
+        : lambda(lambda0), cost(cost0), sq(sq0), iters(0), accepted(0), status(degenerate ? SFM_REFINE_DEGENERATE : SFM_REFINE_MAX_ITER) {}
+
+    SFM_HD bool running(int max_iterations) const { return status != SFM_REFINE_DEGENERATE && iters < max_iterations; }
+
+    // false: lambda has passed 1e16, the chain gives up
+    SFM_HD bool more_damping() { lambda *= 10.0; return !(lambda > 1e16); }
+
+    // this iteration's system was not positive definite; false: stop
+    SFM_HD bool solve_failed() { ++iters; return more_damping(); }
+
+    // this iteration's tentative state has cost nc and squared sum nsq; returns whether the caller commits it, stop: the chain ends
+    // (after the commit)
+    SFM_HD bool tentative(double nc, double nsq, double min_rel, bool &stop)
+    {
+        ++iters;
+        if (nc < cost) {
+            const double rel = (cost - nc) / cost;
+            cost = nc; sq = nsq;
+            ++accepted;
+            lambda /= 10.0;
+            stop = !(rel >= min_rel);
+            if (stop) status = SFM_REFINE_CONVERGED;
+            return true;
+        }
+        stop = !more_damping();
+        return false;
+    }
+};
+
+// one lane: Rn = exp([w]x) R, the product in fp64 (R, Rn row-major 3 x 3).  Rn is a local array that the kernels copy to LDS
+// themselves: with the stores to LDS in here, refine_solve_kernel (239 of its 256 VGPRs) came out with 52 bytes of scratch.
+SFM_HD void refine_rotate(const double w[3], const float R[9], float Rn[9])
+{
+    double E[9];
+    refine_expso3(w, E);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            Rn[3 * r + c] = (float)(E[3 * r] * (double)R[c] + E[3 * r + 1] * (double)R[3 + c] + E[3 * r + 2] * (double)R[6 + c]);
+}
+
+// [R|t] (R 9 row-major, then t 3) -> 4 x 4 row-major
+SFM_HD void refine_store_pose(const float *P, float *o)
+{
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[4 * r + c] = P[3 * r + c];
+        o[4 * r + 3] = P[9 + r];
+    }
+    o[12] = 0.0f; o[13] = 0.0f; o[14] = 0.0f; o[15] = 1.0f;
+}
 
 } // namespace sfm

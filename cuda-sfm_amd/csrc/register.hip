@@ -3,8 +3,8 @@
 //
 // Four launches on the pair's stream, no host synchronisation:
 //   register_gate_kernel    ONE block of 1024 threads: the candidates (matched, gated, usable 3-D point) compacted in point
-//                           order -- a contiguous range of points per thread and a block prefix scan, homo_gate_kernel's
-//                           pattern, so the order does not depend on scheduling -- as X / W (float4) and the normalised
+//                           order -- a contiguous range of points per thread and block_scan (block_ops.hpp), as in
+//                           homo_gate_kernel, so the order does not depend on scheduling -- as X / W (float4) and the normalised
 //                           observation (float2), the point -> candidate map and the candidate count.
 //   register_solve_kernel   one lane per hypothesis: sample4, Lambda Twist on three samples, the 4th chooses; the 12-float pose
 //                           into a per-hypothesis array (zero for a degenerate sample); the lane also clears the hypothesis'
@@ -17,11 +17,13 @@
 //                           count, stores it and folds (count << 32) | (0xFFFFFFFF - hyp) into the key (first maximum wins).
 //                           Integer atomics only: the counts do not depend on the split or on the order of arrival.
 //   register_refine_kernel  ONE block of 256 threads: the winner's pose and inliers, the 6-parameter LM chain (fp32 per-point
-//                           terms, fp64 sums in a fixed order, Cholesky on one lane), then every point's error and final flag
-//                           and the report.  The candidate set of a view is at most the pair's points (thousands): one block
+//                           terms, fp64 sums in a fixed order by block_sum, Cholesky on one lane; damping, accept test and
+//                           stop rules are LmControl's, refine_math.hpp, as in refine.hip), then every point's error and
+//                           final flag and the report.  The candidate set of a view is at most the pair's points (thousands): one block
 //                           runs an iteration in a few microseconds, less than a grid launch per iteration would cost.
 #include "common.hpp"
 #include "device_math.hpp"
+#include "block_ops.hpp"
 #include "register_math.hpp"
 
 namespace sfm {
@@ -79,22 +81,8 @@ void register_gate_kernel(RegisterArgs a)
     const int lo = min(a.n, (int)threadIdx.x * per), hi = min(a.n, lo + per);
     int mine = 0;
     for (int j = lo; j < hi; ++j) mine += register_gate(a, j) ? 1 : 0;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int u = __shfl_up(inc, d);
-        if (lane >= d) inc += u;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int acc = 0;
-        for (int i = 0; i < kRegGateThreads / 64; ++i) { const int t = wsum[i]; wsum[i] = acc; acc += t; }
-        reinterpret_cast<int *>(a.state)[kVsCount] = acc;
-    }
-    __syncthreads();
-    int k = wsum[wave] + inc - mine;
+    int k = block_scan<kRegGateThreads / 64>(mine, wsum);
+    if (threadIdx.x == 0) reinterpret_cast<int *>(a.state)[kVsCount] = wsum[kRegGateThreads / 64];
     const float *ki = a.Kinv;
     for (int j = lo; j < hi; ++j) {
         if (!register_gate(a, j)) { a.slot[j] = -1; continue; }
@@ -160,53 +148,9 @@ void register_score_kernel(RegisterArgs a)
             key = pack_key(total, h);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(key, off);
-        key = o > key ? o : key;
-    }
+    key = wave_max(key);
     if ((threadIdx.x & 63) == 0 && key) atomicMax(reinterpret_cast<unsigned long long *>(a.state + kVsKey), key);
 }
-
-namespace {
-
-// Sum of N doubles over the block in a fixed order (wave butterflies, then the wave partials in wave order); every thread
-// returns with the totals in s_out.
-template <int N>
-__device__ __forceinline__ void reg_block_sum(double (&v)[N], double *s_part, double *s_out)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-        double x = v[q];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-        if (lane == 0) s_part[wave * N + q] = x;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < N) {
-        double s = s_part[threadIdx.x];
-        for (int w = 1; w < kRegWaves; ++w) s += s_part[w * N + threadIdx.x];
-        s_out[threadIdx.x] = s;
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ float reg_uniform(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
-
-// [R|t] (12) -> 4 x 4 row-major
-__device__ void reg_store_pose(const float *P, float *o)
-{
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o[4 * r + c] = P[3 * r + c];
-        o[4 * r + 3] = P[9 + r];
-    }
-    o[12] = 0.0f; o[13] = 0.0f; o[14] = 0.0f; o[15] = 1.0f;
-}
-
-} // namespace
 
 __global__ __launch_bounds__(kRegThreads)
 void register_refine_kernel(RegisterArgs a)
@@ -216,7 +160,7 @@ void register_refine_kernel(RegisterArgs a)
     __shared__ float s_pose[12], s_try[12];
     __shared__ int s_go, s_degen, s_cnt[kRegWaves];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const RefineCam K = { reg_uniform(a.K[0]), reg_uniform(a.K[1]), reg_uniform(a.K[4]) };
+    const RefineCam K = { uniform(a.K[0]), uniform(a.K[1]), uniform(a.K[4]) };
     const int m = reinterpret_cast<const int *>(a.state)[kVsCount];
     const unsigned long long key = *reinterpret_cast<const unsigned long long *>(a.state + kVsKey);
     const uint32_t best = 0xFFFFFFFFu - (uint32_t)key;
@@ -234,14 +178,14 @@ void register_refine_kernel(RegisterArgs a)
         }
 #pragma unroll
         for (int q = 0; q < 12; ++q) s_pose[q] = P[q];
-        reg_store_pose(P, a.state + kVsPose + 16);
+        refine_store_pose(P, a.state + kVsPose + 16);
         s_degen = (m < 4 || wcount < kRegMinInliers) ? 1 : 0;
     }
     __syncthreads();
     const bool degen = s_degen != 0;
     float P[12];
 #pragma unroll
-    for (int q = 0; q < 12; ++q) P[q] = reg_uniform(s_pose[q]);
+    for (int q = 0; q < 12; ++q) P[q] = uniform(s_pose[q]);
 
     // ---- the winner's inliers: the points the LM runs over ----
     for (int k = tid; k < m; k += kRegThreads) {
@@ -266,19 +210,16 @@ void register_refine_kernel(RegisterArgs a)
             v[1] += (double)(r[0] * r[0] + r[1] * r[1]);
         }
     };
-    double cost = 0.0, sq = 0.0;
     {
         double v[2];
         cost_at(P, v);
-        reg_block_sum<2>(v, s_part, s_tot);
-        cost = s_tot[0]; sq = s_tot[1];
+        block_sum<kRegWaves>(v, s_part, s_tot);
     }
+    LmControl lm(a.lambda0, s_tot[0], s_tot[1], degen);
     const int nin = degen ? 0 : wcount;
-    const float initial_rms = nin > 0 ? (float)sqrt(sq / (2.0 * nin)) : 0.0f;
-    double lambda = a.lambda0;
-    int iters = 0, accepted = 0, status = degen ? SFM_REFINE_DEGENERATE : SFM_REFINE_MAX_ITER;
+    const float initial_rms = nin > 0 ? (float)sqrt(lm.sq / (2.0 * nin)) : 0.0f;
 
-    while (!degen && iters < a.max_iter) {
+    while (lm.running(a.max_iter)) {
         // ---- the weighted normal equations at P ----
         double sys[kRegSysValues];
 #pragma unroll
@@ -293,58 +234,46 @@ void register_refine_kernel(RegisterArgs a)
             const float w = refine_huber(r[0], r[1], huber, rho);
             register_terms(r, J, w, [&](int q, float v) { sys[q] += (double)v; });
         }
-        reg_block_sum<kRegSysValues>(sys, s_part, s_tot);
+        block_sum<kRegWaves>(sys, s_part, s_tot);
         // ---- the step on one lane: (H + lambda diag H) d = -g, R <- exp([w]x) R, t <- t + dt ----
         if (tid == 0) {
             double S[21], d[6];
 #pragma unroll
             for (int q = 0; q < 21; ++q) S[q] = s_tot[q];
 #pragma unroll
-            for (int q = 0; q < 6; ++q) { S[symn<6>(q, q)] += lambda * s_tot[symn<6>(q, q)]; d[q] = -s_tot[21 + q]; }
+            for (int q = 0; q < 6; ++q) { S[symn<6>(q, q)] += lm.lambda * s_tot[symn<6>(q, q)]; d[q] = -s_tot[21 + q]; }
             const bool ok = refine_cholesky<6>(S, d);
             s_go = ok ? 1 : 0;
             if (ok) {
-                double E[9];
-                refine_expso3(d, E);
+                float Rn[9];
+                refine_rotate(d, s_pose, Rn);
 #pragma unroll
-                for (int r = 0; r < 3; ++r) {
+                for (int q = 0; q < 9; ++q) s_try[q] = Rn[q];
 #pragma unroll
-                    for (int c = 0; c < 3; ++c)
-                        s_try[3 * r + c] = (float)(E[3 * r] * (double)s_pose[c] + E[3 * r + 1] * (double)s_pose[3 + c] + E[3 * r + 2] * (double)s_pose[6 + c]);
-                    s_try[9 + r] = (float)((double)s_pose[9 + r] + d[3 + r]);
-                }
+                for (int r = 0; r < 3; ++r) s_try[9 + r] = (float)((double)s_pose[9 + r] + d[3 + r]);
             }
         }
         __syncthreads();
-        ++iters;
         if (!s_go) {                                      // not positive definite: more damping
-            lambda *= 10.0;
-            if (lambda > 1e16) break;
+            if (!lm.solve_failed()) break;
             continue;
         }
         // ---- the cost of the tentative pose ----
         float Pt[12];
 #pragma unroll
-        for (int q = 0; q < 12; ++q) Pt[q] = reg_uniform(s_try[q]);
+        for (int q = 0; q < 12; ++q) Pt[q] = uniform(s_try[q]);
         double v[2];
         cost_at(Pt, v);
-        reg_block_sum<2>(v, s_part, s_tot);
-        const double nc = s_tot[0];
-        if (nc < cost) {                                  // accept, less damping
-            const double rel = (cost - nc) / cost;
-            cost = nc; sq = s_tot[1];
-            ++accepted;
-            lambda /= 10.0;
+        block_sum<kRegWaves>(v, s_part, s_tot);
+        bool stop;
+        if (lm.tentative(s_tot[0], s_tot[1], (double)a.min_rel, stop)) {     // accepted: commit the pose
 #pragma unroll
             for (int q = 0; q < 12; ++q) P[q] = Pt[q];
             __syncthreads();                              // every lane has read s_pose / s_try for this iteration
             if (tid < 12) s_pose[tid] = s_try[tid];
             __syncthreads();
-            if (!(rel >= (double)a.min_rel)) { status = SFM_REFINE_CONVERGED; break; }
-        } else {
-            lambda *= 10.0;
-            if (lambda > 1e16) break;
         }
+        if (stop) break;
     }
 
     // ---- every point under the final pose: pixel error, final inlier flag ----
@@ -371,20 +300,41 @@ void register_refine_kernel(RegisterArgs a)
     if (tid == 0) {
         int nfin = 0;
         for (int w = 0; w < kRegWaves; ++w) nfin += s_cnt[w];
-        reg_store_pose(P, a.state + kVsPose);
+        refine_store_pose(P, a.state + kVsPose);
         sfm_register_report rep;
-        rep.status = status;
+        rep.status = lm.status;
         rep.num_candidates = m;
         rep.ransac_inliers = nin;
         rep.num_inliers = nfin;
         rep.best_hypothesis = best;
-        rep.iterations = iters; rep.accepted = accepted;
+        rep.iterations = lm.iters; rep.accepted = lm.accepted;
         rep.initial_rms_px = initial_rms;
-        rep.final_rms_px = nin > 0 ? (float)sqrt(sq / (2.0 * nin)) : 0.0f;
-        rep.final_cost = (float)cost;
-        rep.lambda = (float)lambda;
+        rep.final_rms_px = nin > 0 ? (float)sqrt(lm.sq / (2.0 * nin)) : 0.0f;
+        rep.final_cost = (float)lm.cost;
+        rep.lambda = (float)lm.lambda;
         *reinterpret_cast<sfm_register_report *>(a.state + kVsReport) = rep;
     }
+}
+
+// pair->d_vwork for cap_points points: the arrays of `a` inside it; returns its size in bytes
+static size_t register_work_layout(void *buffer, int cap_points, RegisterArgs &a)
+{
+    const size_t cap = (size_t)cap_points;
+    Carver w(buffer);
+    a.Xc = w.take<float4>(cap);
+    a.Oc = w.take<float2>(cap);
+    a.slot = w.take<int>(cap);
+    a.inl = w.take<uint8_t>(cap);
+    return w.used;
+}
+
+// pair->d_vhyp for `hyps` hypotheses, likewise
+static size_t register_hyp_layout(void *buffer, size_t hyps, RegisterArgs &a)
+{
+    Carver h(buffer);
+    a.acc = h.take<unsigned long long>(hyps);
+    a.poses = h.take<float>(12 * hyps);
+    return h.used;
 }
 
 int launch_register(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_register_params &p, const float *d_points, const uint8_t *d_valid)
@@ -398,15 +348,8 @@ int launch_register(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_regi
     a.max_iter = p.max_iterations; a.huber = p.huber_px; a.min_rel = p.min_rel_decrease; a.lambda0 = p.initial_lambda;
     a.state = pair->d_vstate;
     a.reproj = pair->d_vreproj;
-    const size_t cap = (size_t)pair->cap_points;
-    char *w = static_cast<char *>(pair->d_vwork);
-    a.Xc = reinterpret_cast<float4 *>(w);   w += cap * sizeof(float4);
-    a.Oc = reinterpret_cast<float2 *>(w);   w += cap * sizeof(float2);
-    a.slot = reinterpret_cast<int *>(w);    w += cap * sizeof(int);
-    a.inl = reinterpret_cast<uint8_t *>(w);
-    char *h = static_cast<char *>(pair->d_vhyp);
-    a.acc = reinterpret_cast<unsigned long long *>(h);  h += (size_t)pair->cap_vhyps * sizeof(unsigned long long);
-    a.poses = reinterpret_cast<float *>(h);
+    register_work_layout(pair->d_vwork, pair->cap_points, a);
+    register_hyp_layout(pair->d_vhyp, pair->cap_vhyps, a);       // sized for the largest num_hypotheses seen
     a.counts = pair->d_vcounts;
     hipStream_t st = pair->ctx->stream;
     const int hblocks = (int)((p.num_hypotheses + kRegHypBlock - 1) / kRegHypBlock);
@@ -428,11 +371,16 @@ int launch_register(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_regi
 
 size_t register_work_bytes(int cap_points)
 {
-    const size_t cap = (size_t)cap_points;
-    return cap * (sizeof(float4) + sizeof(float2) + sizeof(int) + 1);
+    RegisterArgs a;
+    return register_work_layout(nullptr, cap_points, a);
 }
 
-size_t register_hyp_bytes(size_t num_hypotheses) { return num_hypotheses * (sizeof(unsigned long long) + 12 * sizeof(float)); }
+size_t register_hyp_bytes(size_t num_hypotheses)
+{
+    RegisterArgs a;
+    return register_hyp_layout(nullptr, num_hypotheses, a);
+}
+
 int register_state_words() { return kVsWords; }
 int register_pose_offset() { return kVsPose; }
 int register_report_offset() { return kVsReport; }

@@ -20,6 +20,7 @@
 //   - all bookkeeping lives on the device; the host synchronises once, at the end.
 #include "common.hpp"
 #include "sift_math.hpp"
+#include "block_ops.hpp"
 #include <cstring>
 #include <new>
 
@@ -338,29 +339,6 @@ void sift_find_kernel(const float *__restrict__ temp, Levels L, Workspace W, flo
         if (blk_base + i < (unsigned int)W.cap) stash[blk_base + i] = buf[i];
 }
 
-// block-wide exclusive scan of one value per thread (1024 threads); returns the exclusive prefix, total in *sum
-__device__ __forceinline__ unsigned int block_scan_1024(unsigned int v, unsigned int *wsum /* LDS [17] */, unsigned int *sum)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned int u = __shfl_up(inc, d);
-        if (lane >= d) inc += u;
-    }
-    __syncthreads();                                     // wsum may still be read from the previous call
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned int acc = 0;
-        for (int i = 0; i < 16; ++i) { const unsigned int t = wsum[i]; wsum[i] = acc; acc += t; }
-        wsum[16] = acc;
-    }
-    __syncthreads();
-    *sum = wsum[16];
-    return wsum[wave] + inc - v;
-}
-
 // per-segment counts -> exclusive offsets; closes LevelState::found / kept.  One block per level.
 __global__ __launch_bounds__(1024)
 void sift_scan_kernel(Levels L, Workspace W)
@@ -374,8 +352,8 @@ void sift_scan_kernel(Levels L, Workspace W)
         const int lo = min(n, (int)threadIdx.x * per), hi = min(n, lo + per);
         unsigned int mine = 0;
         for (int i = lo; i < hi; ++i) mine += a[i];
-        unsigned int running;
-        unsigned int run = block_scan_1024(mine, wsum, &running);
+        unsigned int run = block_scan<16>(mine, wsum);
+        const unsigned int running = wsum[16];
         for (int i = lo; i < hi; ++i) { const unsigned int c = a[i]; a[i] = run; run += c; }
         if (threadIdx.x == 0) { W.state[lvl].found = running; W.state[lvl].kept = min(running, (unsigned int)W.cap); }
     }
@@ -503,8 +481,8 @@ void sift_place_kernel(Levels L, Workspace W)
     const unsigned int lo = min(kept, threadIdx.x * per), hi = min(kept, lo + per);
     unsigned int mine = 0;
     for (unsigned int i = lo; i < hi; ++i) mine += flag[i];
-    unsigned int running;
-    unsigned int run = block_scan_1024(mine, wsum, &running);
+    unsigned int run = block_scan<16>(mine, wsum);
+    const unsigned int running = wsum[16];
     for (unsigned int i = lo; i < hi; ++i) { pre[i] = run; run += flag[i]; }
     if (threadIdx.x == 0) W.state[lvl].dups = running;
 }
