@@ -72,7 +72,7 @@ EXPORTS = [
     "sfm_get_key", "sfm_get_inlier_counts", "sfm_get_inlier_mask", "sfm_get_E_candidates",
     "sfm_get_pose_candidates", "sfm_get_pose_inverses", "sfm_get_pose_index", "sfm_get_points", "sfm_copy_points_to_vbo",
     "sfm_ransac_last_launch", "sfm_ransac_last_clock", "sfm_ransac_last_prefilter_rule", "sfm_process_pairs", "sfm_ctx_last_pairs_batched", "sfm_extract_views", "sfm_extract_views_u8",
-    "sfm_refine_default_params", "sfm_refine_two_view", "sfm_get_refine_report", "sfm_get_refined_pose", "sfm_get_refined_points",
+    "sfm_refine_default_params", "sfm_refine_two_view", "sfm_refine_pairs", "sfm_get_refine_report", "sfm_get_refined_pose", "sfm_get_refined_points",
     "sfm_get_reprojection_errors",
     "sfm_register_default_params", "sfm_register_view", "sfm_get_register_report", "sfm_get_view_pose", "sfm_get_view_errors",
     "sfm_get_view_counts",
@@ -187,6 +187,7 @@ _lib.sfm_get_result.argtypes = [_vp, _vp]
 _lib.sfm_refine_default_params.argtypes = [C.POINTER(RefineParams)]
 _lib.sfm_refine_default_params.restype = None
 _lib.sfm_refine_two_view.argtypes = [_vp, C.POINTER(RefineParams)]
+_lib.sfm_refine_pairs.argtypes = [C.POINTER(_vp), C.c_int, C.POINTER(RefineParams), C.POINTER(_vp)]
 _lib.sfm_get_refine_report.argtypes = [_vp, C.POINTER(RefineReport)]
 _lib.sfm_get_refined_pose.argtypes = [_vp, _vp, _vp]
 _lib.sfm_get_refined_points.argtypes = [_vp, _vp]
@@ -257,6 +258,29 @@ def refine_params(**kw):
         else:
             setattr(p, k, v)
     return p
+
+
+def refine_pairs_enqueue(pairs, params, masks=None):
+    """sfm_refine_pairs (enqueue only): every ImagePair of the list (one Context, none twice) refined in three launches, each left
+    exactly as its own refine_enqueue(params) leaves it.  masks: None, or one entry per pair (device uint8 tensor / pointer;
+    None = that pair's inlier mask); params.d_mask must stay unset."""
+    n = len(pairs)
+    handles = (_vp * n)(*[p._h.value for p in pairs])
+    d_masks = None
+    if masks is not None:
+        assert len(masks) == n, "one mask entry per pair"
+        d_masks = (_vp * n)(*[_ptr(m) for m in masks])
+    _check(_lib.sfm_refine_pairs(handles, n, C.byref(params), d_masks), "sfm_refine_pairs")
+
+
+def refine_pairs(pairs, max_iterations=20, huber_px=1.0, masks=None, min_rel_decrease=1e-6, initial_lambda=1e-3):
+    """ImagePair.refine for a list of pairs in one batched call.  Returns the list of report dicts: one wait for the device, then
+    a small copy per pair."""
+    refine_pairs_enqueue(pairs, refine_params(max_iterations=int(max_iterations), huber_px=float(huber_px),
+                                              min_rel_decrease=float(min_rel_decrease), initial_lambda=float(initial_lambda)), masks)
+    if pairs:
+        pairs[0].ctx.synchronize()
+    return [p.get_refine_report() for p in pairs]
 
 
 def register_params(**kw):

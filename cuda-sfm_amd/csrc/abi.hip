@@ -11,6 +11,8 @@
 #include <thread>
 #include <mutex>
 #include <vector>
+#include <algorithm>
+#include <functional>
 #include <initializer_list>
 
 namespace sfm {
@@ -183,6 +185,7 @@ static int ctx_destroy_now(sfm_ctx *ctx)
     if (ctx->views_image) (void)hipFree(ctx->views_image);
     if (ctx->views_ev) (void)hipEventDestroy(ctx->views_ev);
     sift_job_free(ctx);
+    refine_jobs_free(ctx);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     for (auto &t : ctx->tev) for (hipEvent_t e : t) if (e) (void)hipEventDestroy(e);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -814,6 +817,17 @@ void sfm_refine_default_params(sfm_refine_params *p)
     p->initial_lambda = 1e-3f;
 }
 
+// the refinement's per-pair buffers, allocated at the first call and sized to the creation-time count: sfm_pair_reset needs no reallocation
+static int refine_buffers(sfm_pair *pair)
+{
+    if (pair->d_rstate) return SFM_OK;
+    const size_t cap = (size_t)pair->cap_points;
+    return alloc_group({ { reinterpret_cast<void **>(&pair->d_rstate), (size_t)refine_state_words() * 4 },
+                         { reinterpret_cast<void **>(&pair->d_rpoints), 4 * cap * 4 },
+                         { reinterpret_cast<void **>(&pair->d_rreproj), reproj_bytes(cap) },
+                         { &pair->d_rwork, refine_work_bytes(pair->cap_points) } });
+}
+
 int sfm_refine_two_view(sfm_pair *pair, const sfm_refine_params *p)
 {
     SFM_REQUIRE(pair && p, SFM_E_INVALID, "null argument");
@@ -822,16 +836,40 @@ int sfm_refine_two_view(sfm_pair *pair, const sfm_refine_params *p)
     int rc = check_lm_params(*p, "sfm_refine_params");
     if (rc != SFM_OK) return rc;
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
-    if (!pair->d_rstate) {                              // sized to the creation-time count: sfm_pair_reset needs no reallocation
-        const size_t cap = (size_t)pair->cap_points;
-        rc = alloc_group({ { reinterpret_cast<void **>(&pair->d_rstate), (size_t)refine_state_words() * 4 },
-                           { reinterpret_cast<void **>(&pair->d_rpoints), 4 * cap * 4 },
-                           { reinterpret_cast<void **>(&pair->d_rreproj), reproj_bytes(cap) },
-                           { &pair->d_rwork, refine_work_bytes(pair->cap_points) } });
-        if (rc != SFM_OK) return rc;
-    }
+    rc = refine_buffers(pair);
+    if (rc != SFM_OK) return rc;
     rc = launch_refine(pair, *p);
     if (rc == SFM_OK) pair->state.refined();
+    return rc;
+}
+
+int sfm_refine_pairs(sfm_pair *const *pairs, int num_pairs, const sfm_refine_params *p, const uint8_t *const *d_masks)
+{
+    // the checks that need no device first, all of them before anything is enqueued or any pair changes
+    SFM_REQUIRE(p, SFM_E_INVALID, "null params");
+    SFM_REQUIRE(num_pairs >= 0 && num_pairs <= 65535, SFM_E_INVALID, "num_pairs %d outside 0..65535", num_pairs);
+    if (num_pairs == 0) return SFM_OK;
+    SFM_REQUIRE(pairs, SFM_E_INVALID, "null pair list");
+    for (int i = 0; i < num_pairs; ++i) SFM_REQUIRE(pairs[i], SFM_E_INVALID, "pairs[%d] is null", i);
+    SFM_REQUIRE(!p->d_mask, SFM_E_INVALID, "sfm_refine_params.d_mask must be null here: per-pair masks go through d_masks");
+    int rc = check_lm_params(*p, "sfm_refine_params");
+    if (rc != SFM_OK) return rc;
+    sfm_ctx *ctx = pairs[0]->ctx;
+    for (int i = 1; i < num_pairs; ++i) SFM_REQUIRE(pairs[i]->ctx == ctx, SFM_E_INVALID, "pairs[%d] belongs to another context than pairs[0]", i);
+    {
+        std::vector<const sfm_pair *> sorted(pairs, pairs + num_pairs);
+        std::sort(sorted.begin(), sorted.end(), std::less<const sfm_pair *>());
+        SFM_REQUIRE(std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end(), SFM_E_INVALID,
+                    "a pair is listed twice (two blocks would write the same buffers)");
+    }
+    for (int i = 0; i < num_pairs; ++i) {
+        SFM_FLUSH(pairs[i]);
+        SFM_REQUIRE(pairs[i]->state.has(kE), SFM_E_STATE, "pairs[%d]: %s", i, pair_stage_hint(pairs[i]->state.missing(kE)));
+    }
+    SFM_HIP_TRY(hipSetDevice(ctx->device));
+    for (int i = 0; i < num_pairs; ++i) { rc = refine_buffers(pairs[i]); if (rc != SFM_OK) return rc; }
+    rc = launch_refine_pairs(ctx, pairs, num_pairs, *p, d_masks);
+    for (int i = 0; i < num_pairs; ++i) if (rc == SFM_OK) pairs[i]->state.refined();
     return rc;
 }
 

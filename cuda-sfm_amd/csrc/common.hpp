@@ -138,6 +138,10 @@ struct sfm_ctx {
     size_t pool_records_cap = 0;       // floats
     void *batch_ws = nullptr;          // sfm_process_pairs, batched path: the PairJob array + every pair's buffers (pairs_batch.hpp)
     size_t batch_ws_bytes = 0;
+    // sfm_refine_pairs: the RefineArgs of a call (refine.hip), device array + pinned staging; the event sits behind the upload
+    void *refine_jobs = nullptr, *refine_jobs_pinned = nullptr;
+    size_t refine_jobs_cap = 0;        // jobs
+    hipEvent_t refine_jobs_ev = nullptr;
     void *sift_job = nullptr;          // the extraction in flight (sift.hip: SiftJob), sfm_extract_sift_begin .. _end
     // kernels that already opted in to > 64 KiB of dynamic LDS on THIS context's device (function attributes are
     // per device; a context is used by one host thread at a time, so no process-wide flag)
@@ -280,6 +284,9 @@ int launch_pose_chain(sfm_pair *pair, float *d_record);          // REFERENCE mo
 
 // refine.hip
 int launch_refine(sfm_pair *pair, const sfm_refine_params &p);   // start (grid), LM solve (one block), finish (grid)
+// the same three stages for many pairs of one context in three launches (grid = pairs); d_masks: null, or one entry per pair (null = its own)
+int launch_refine_pairs(sfm_ctx *ctx, sfm_pair *const *pairs, int num_pairs, const sfm_refine_params &p, const uint8_t *const *d_masks);
+void refine_jobs_free(sfm_ctx *ctx);                              // the context's job array, staging buffer and event
 size_t refine_work_bytes(int cap_points);                         // bytes of pair->d_rwork
 int refine_state_words();                                         // floats of pair->d_rstate
 int refine_pose_offset();                                         // refined P + E inside d_rstate

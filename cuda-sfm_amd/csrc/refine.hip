@@ -10,6 +10,11 @@
 //                         Cholesky on one lane, the back substitution and the cost of the tentative step -- and writes the
 //                         refined pose, E and the report.
 //   refine_finish_kernel  grid over points: refined point or DLT against the refined pose, reprojection errors, used flags.
+// Many pairs in one call (launch_refine_pairs): the same three bodies over an array of RefineArgs in device memory, one per pair --
+//   refine_start_pairs_kernel / refine_finish_pairs_kernel   grid (blocks of the largest pair, pairs): blocks past a pair's own
+//                         count leave as a whole;  refine_solve_pairs_kernel   grid (pairs), one solve block each.
+// A block copies its job into registers through a uniform address (scalar loads), then runs the body the single-pair kernel runs:
+// the arithmetic exists once, and a pair's result is the same bit for bit whichever entry point computed it.
 // Reductions: per-thread fp64 sums in a fixed point order, then block_sum (block_ops.hpp: wave butterflies, the wave partials in
 // wave order) -- no float atomics, so the result is the same bit for bit on every run.
 // The damping schedule, the accept test, the stop rules and the report's bookkeeping are LmControl's (refine_math.hpp), which
@@ -19,6 +24,8 @@
 #include "device_math.hpp"
 #include "block_ops.hpp"
 #include "refine_math.hpp"
+#include <algorithm>
+#include <vector>
 
 namespace sfm {
 
@@ -26,6 +33,7 @@ constexpr int kRefineSweeps = 8;          // = kSweeps4 of pose.hip: the start p
 constexpr int kRefineThreads = 512;      // 1024 needs > 128 VGPRs (the fp64 sums of the system + one point's Jacobians): it spilled
 constexpr int kRefineWaves = kRefineThreads / 64;
 constexpr int kStartPoints = 64;          // points per block of refine_start_kernel (4 lanes each)
+constexpr int kFinishPoints = 256;        // points (= threads) per block of refine_finish_kernel
 constexpr int kRefineMinPoints = 16;
 constexpr int kSysValues = 25;            // S (15), b (5), diag U (5)
 
@@ -50,13 +58,13 @@ struct RefineArgs {
     float *points, *reproj;               // outputs: 4 x n; err[n] then uint8 used[n]
 };
 
-__global__ __launch_bounds__(256)
-void refine_start_kernel(RefineArgs a)
+// The three bodies.  `a` is uniform over the block: the kernel's argument, or the block's copy of its job.
+__device__ __forceinline__ void refine_start_block(const RefineArgs &a, const int block)
 {
     __shared__ int s_votes[4][4];
     const int i = threadIdx.x & 3;
     const int wave = threadIdx.x >> 6;
-    const int j = blockIdx.x * kStartPoints + (int)(threadIdx.x >> 2);
+    const int j = block * kStartPoints + (int)(threadIdx.x >> 2);
     float e[9], p[64];
 #pragma unroll
     for (int k = 0; k < 9; ++k) e[k] = a.E[k];
@@ -80,8 +88,8 @@ void refine_start_kernel(RefineArgs a)
         s_votes[wave][i] = __builtin_popcountll(m & lanes);
     }
     __syncthreads();
-    if (threadIdx.x < 4) a.votes[4 * blockIdx.x + threadIdx.x] = s_votes[0][i] + s_votes[1][i] + s_votes[2][i] + s_votes[3][i];
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (threadIdx.x < 4) a.votes[4 * block + threadIdx.x] = s_votes[0][i] + s_votes[1][i] + s_votes[2][i] + s_votes[3][i];
+    if (block == 0 && threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < 64; ++k) a.state[kStP + k] = p[k];
     }
@@ -105,8 +113,7 @@ __device__ void set_basis(float *s)
     for (int k = 0; k < 3; ++k) { s[12 + k] = (float)b1[k]; s[15 + k] = (float)b2[k]; }
 }
 
-__global__ __launch_bounds__(kRefineThreads)
-void refine_solve_kernel(RefineArgs a)
+__device__ __forceinline__ void refine_solve_block(const RefineArgs &a)
 {
     __shared__ double s_part[kRefineWaves * kSysValues];
     __shared__ double s_tot[kSysValues];
@@ -306,10 +313,9 @@ void refine_solve_kernel(RefineArgs a)
     }
 }
 
-__global__ __launch_bounds__(256)
-void refine_finish_kernel(RefineArgs a)
+__device__ __forceinline__ void refine_finish_block(const RefineArgs &a, const int block)
 {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = block * kFinishPoints + threadIdx.x;
     if (j >= a.n) return;
     const float *Po = a.state + kStPose;
     float Pm[16];
@@ -343,6 +349,61 @@ void refine_finish_kernel(RefineArgs a)
     reinterpret_cast<uint8_t *>(a.reproj + a.n)[j] = k >= 0 ? 1 : 0;
 }
 
+__global__ __launch_bounds__(256)
+void refine_start_kernel(RefineArgs a) { refine_start_block(a, blockIdx.x); }
+
+__global__ __launch_bounds__(kRefineThreads)
+void refine_solve_kernel(RefineArgs a) { refine_solve_block(a); }
+
+__global__ __launch_bounds__(kFinishPoints)
+void refine_finish_kernel(RefineArgs a) { refine_finish_block(a, blockIdx.x); }
+
+// ---- many pairs: job blockIdx.y (start, finish) / blockIdx.x (solve) of `jobs` ----
+// A pointer read from memory is a generic one, and the bodies would go through flat loads and stores; a kernel argument is known
+// to be global.  Cast to the global address space and back -- with an empty asm in between that keeps the optimiser from folding
+// the two casts away (and the value in scalar registers) -- a job's pointer is a global one for every access that follows.
+template <typename T>
+__device__ __forceinline__ T *global_ptr(T *p)
+{
+    auto g = (__attribute__((address_space(1))) T *)p;
+    asm("" : "+s"(g));
+    return (T *)g;
+}
+
+// the block's job, through a uniform address (scalar loads), every pointer marked global
+__device__ __forceinline__ RefineArgs load_job(const RefineArgs *__restrict__ jobs, const unsigned int job)
+{
+    RefineArgs a = jobs[job];
+    a.X0 = global_ptr(a.X0); a.X1 = global_ptr(a.X1); a.E = global_ptr(a.E); a.K = global_ptr(a.K); a.mask = global_ptr(a.mask);
+    a.state = global_ptr(a.state); a.votes = global_ptr(a.votes); a.cand = global_ptr(a.cand);
+    a.obs = global_ptr(a.obs); a.Xa = global_ptr(a.Xa); a.Xb = global_ptr(a.Xb);
+    a.idx = global_ptr(a.idx); a.slot = global_ptr(a.slot); a.points = global_ptr(a.points); a.reproj = global_ptr(a.reproj);
+    return a;
+}
+
+__global__ __launch_bounds__(256)
+void refine_start_pairs_kernel(const RefineArgs *__restrict__ jobs)
+{
+    const RefineArgs a = load_job(jobs, blockIdx.y);
+    if ((int)blockIdx.x * kStartPoints >= a.n) return;    // past this pair's blocks: the whole block, before the ballot and the barrier
+    refine_start_block(a, blockIdx.x);
+}
+
+__global__ __launch_bounds__(kRefineThreads)
+void refine_solve_pairs_kernel(const RefineArgs *__restrict__ jobs)
+{
+    const RefineArgs a = load_job(jobs, blockIdx.x);
+    refine_solve_block(a);
+}
+
+__global__ __launch_bounds__(kFinishPoints)
+void refine_finish_pairs_kernel(const RefineArgs *__restrict__ jobs)
+{
+    const RefineArgs a = load_job(jobs, blockIdx.y);
+    if ((int)blockIdx.x * kFinishPoints >= a.n) return;
+    refine_finish_block(a, blockIdx.x);
+}
+
 // pair->d_rwork for cap_points points: the arrays of `a` inside it; returns its size in bytes
 static size_t refine_work_layout(void *buffer, int cap_points, RefineArgs &a)
 {
@@ -358,25 +419,85 @@ static size_t refine_work_layout(void *buffer, int cap_points, RefineArgs &a)
     return w.used;
 }
 
-int launch_refine(sfm_pair *pair, const sfm_refine_params &p)
+static void refine_args(sfm_pair *pair, const sfm_refine_params &p, const uint8_t *d_mask, RefineArgs &a)
 {
-    RefineArgs a;
     a.X0 = pair->d_X[0]; a.X1 = pair->d_X[1]; a.ld = pair->ld; a.n = pair->n; a.cap = pair->cap_points;
     a.E = pair->d_E; a.K = pair->d_K;
-    a.mask = p.d_mask ? p.d_mask : pair->d_mask;
+    a.mask = d_mask ? d_mask : pair->d_mask;
     a.huber = p.huber_px; a.min_rel = p.min_rel_decrease; a.lambda0 = p.initial_lambda; a.max_iter = p.max_iterations;
     a.state = pair->d_rstate;
     a.points = pair->d_rpoints; a.reproj = pair->d_rreproj;
     refine_work_layout(pair->d_rwork, pair->cap_points, a);
+}
+
+int launch_refine(sfm_pair *pair, const sfm_refine_params &p)
+{
+    RefineArgs a;
+    refine_args(pair, p, p.d_mask, a);
     hipStream_t st = pair->ctx->stream;
     const int nb = (pair->n + kStartPoints - 1) / kStartPoints;
     hipLaunchKernelGGL(refine_start_kernel, dim3(nb), dim3(256), 0, st, a);
     SFM_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(refine_solve_kernel, dim3(1), dim3(kRefineThreads), 0, st, a);
     SFM_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(refine_finish_kernel, dim3((pair->n + 255) / 256), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(refine_finish_kernel, dim3((pair->n + kFinishPoints - 1) / kFinishPoints), dim3(kFinishPoints), 0, st, a);
     SFM_HIP_TRY(hipGetLastError());
     return SFM_OK;
+}
+
+// The context's job array for `count` jobs: device buffer + pinned staging, grown on demand (rare: the stream is drained before
+// the old device buffer goes).  The staging buffer is rewritten by the host: the upload of the call before must have left it.
+static int refine_jobs_buffers(sfm_ctx *ctx, size_t count)
+{
+    if (!ctx->refine_jobs_ev) SFM_HIP_TRY(hipEventCreateWithFlags(&ctx->refine_jobs_ev, hipEventDisableTiming));
+    SFM_HIP_TRY(hipEventSynchronize(ctx->refine_jobs_ev));             // (an event never recorded is complete)
+    if (count <= ctx->refine_jobs_cap) return SFM_OK;
+    const size_t want = count > 2 * ctx->refine_jobs_cap ? count : 2 * ctx->refine_jobs_cap;
+    if (ctx->refine_jobs_pinned) (void)hipHostFree(ctx->refine_jobs_pinned);
+    ctx->refine_jobs_pinned = nullptr;
+    ctx->refine_jobs_cap = 0;                                          // the size counts for both: it is set when both exist
+    SFM_HIP_TRY(hipHostMalloc(&ctx->refine_jobs_pinned, want * sizeof(RefineArgs), hipHostMallocDefault));
+    size_t have = 0;
+    const int rc = grow(&ctx->refine_jobs, &have, want * sizeof(RefineArgs), ctx->stream);
+    if (rc != SFM_OK) return rc;
+    ctx->refine_jobs_cap = want;
+    return SFM_OK;
+}
+
+int launch_refine_pairs(sfm_ctx *ctx, sfm_pair *const *pairs, int num_pairs, const sfm_refine_params &p, const uint8_t *const *d_masks)
+{
+    int rc = refine_jobs_buffers(ctx, (size_t)num_pairs);
+    if (rc != SFM_OK) return rc;
+    // long chains first: the solve blocks are dispatched in job order.  Stable, so equal sizes keep the caller's order; a pair's
+    // result does not depend on its place (every block works on its own pair's buffers).
+    std::vector<int> order((size_t)num_pairs);
+    for (int i = 0; i < num_pairs; ++i) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return pairs[x]->n > pairs[y]->n; });
+    RefineArgs *h_jobs = static_cast<RefineArgs *>(ctx->refine_jobs_pinned);
+    for (int k = 0; k < num_pairs; ++k) {
+        const int i = order[(size_t)k];
+        refine_args(pairs[i], p, d_masks ? d_masks[i] : nullptr, h_jobs[k]);
+    }
+    const RefineArgs *d_jobs = static_cast<const RefineArgs *>(ctx->refine_jobs);
+    hipStream_t st = ctx->stream;
+    SFM_HIP_TRY(hipMemcpyAsync(ctx->refine_jobs, h_jobs, (size_t)num_pairs * sizeof(RefineArgs), hipMemcpyHostToDevice, st));
+    SFM_HIP_TRY(hipEventRecord(ctx->refine_jobs_ev, st));
+    const int nmax = h_jobs[0].n;
+    hipLaunchKernelGGL(refine_start_pairs_kernel, dim3((nmax + kStartPoints - 1) / kStartPoints, num_pairs), dim3(256), 0, st, d_jobs);
+    SFM_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(refine_solve_pairs_kernel, dim3(num_pairs), dim3(kRefineThreads), 0, st, d_jobs);
+    SFM_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(refine_finish_pairs_kernel, dim3((nmax + kFinishPoints - 1) / kFinishPoints, num_pairs), dim3(kFinishPoints), 0, st, d_jobs);
+    SFM_HIP_TRY(hipGetLastError());
+    return SFM_OK;
+}
+
+void refine_jobs_free(sfm_ctx *ctx)
+{
+    if (ctx->refine_jobs_pinned) (void)hipHostFree(ctx->refine_jobs_pinned);
+    if (ctx->refine_jobs) (void)hipFree(ctx->refine_jobs);
+    if (ctx->refine_jobs_ev) (void)hipEventDestroy(ctx->refine_jobs_ev);
+    ctx->refine_jobs_pinned = nullptr; ctx->refine_jobs = nullptr; ctx->refine_jobs_ev = nullptr; ctx->refine_jobs_cap = 0;
 }
 
 size_t refine_work_bytes(int cap_points)

@@ -155,6 +155,22 @@ public:
     }
 };
 
+// two-view bundle adjustment of many pairs in one batched call (sfm_refine_pairs): every pair is left as its own refine() leaves
+// it, bit for bit; returns the reports in the order of the list (one wait for the device)
+inline std::vector<sfm_refine_report> refine_pairs(Image_pair *const *pairs, int count, int max_iterations = 20, float huber_px = 1.0f)
+{
+    sfm_refine_params p;
+    sfm_refine_default_params(&p);
+    p.max_iterations = max_iterations;
+    p.huber_px = huber_px;
+    std::vector<sfm_pair *> handles;
+    for (int i = 0; i < count; ++i) handles.push_back(pairs[i] ? pairs[i]->handle() : nullptr);
+    SFM_FACADE_CALL(sfm_refine_pairs(handles.data(), count, &p, nullptr));
+    std::vector<sfm_refine_report> reports;
+    for (int i = 0; i < count; ++i) reports.push_back(pairs[i]->getRefineReport());
+    return reports;
+}
+
 } // namespace SfM
 
 #endif

@@ -315,6 +315,14 @@ typedef struct sfm_refine_report {
 } sfm_refine_report;
 
 int sfm_refine_two_view(sfm_pair *pair, const sfm_refine_params *p);              /* enqueue only */
+/* The same refinement for many pairs of ONE context in three launches (grid = pairs) on its stream: afterwards every pair is
+ * exactly as after sfm_refine_two_view(pair, p) with its mask -- bit for bit, whatever the order of the list -- and the getters
+ * and SFM_BUF_REFINED_* / SFM_BUF_REPROJ serve it per pair.  pairs: HOST array of num_pairs (0..65535) handles, none listed
+ * twice; p: one parameter set for all of them, p->d_mask must be NULL; d_masks: optional HOST array of num_pairs DEVICE
+ * pointers (NULL, or a NULL entry: that pair's estimateE inlier mask).  Every check precedes the first launch: SFM_E_INVALID
+ * (arguments) or SFM_E_STATE (the text names the first pair without a current E) leave every pair as it was. */
+int sfm_refine_pairs(sfm_pair *const *pairs, int num_pairs, const sfm_refine_params *p,
+                     const uint8_t *const *d_masks);                              /* enqueue only */
 int sfm_get_refine_report(sfm_pair *pair, sfm_refine_report *r);                   /* synchronises */
 /* [R|t; 0 0 0 1] (X2 = R X1 + t, |t| = 1) and E = [t]x R, row-major */
 int sfm_get_refined_pose(sfm_pair *pair, float h_P[16], float h_E[9]);
