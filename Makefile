@@ -34,9 +34,12 @@ GEOMTEST := tests/cpp/geom_test
 
 all: $(LIB) $(LIB_AB) $(COMMLIB) oracle hostcheck fakeccl $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(IOTEST) $(GEOMTEST)
 
+# the product's objects come with the compiler's resource-usage report (registers, scratch, LDS of every kernel) next to them:
+# $(BUILD)/<source>.usage.txt, read by tests/test_register_budget.py; warnings and errors of the compile are still shown
 $(BUILD)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) $(FLAGS_$*) -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) $(FLAGS_$*) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(BUILD)/$*.usage.txt || { cat $(BUILD)/$*.usage.txt >&2; exit 1; }
+	@grep -v -e 'remark:' -e '^ *[0-9]* | ' -e '^ *| ' $(BUILD)/$*.usage.txt >&2 || true
 
 $(BUILD_AB)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(BUILD_AB)
@@ -93,7 +96,7 @@ $(GEOMTEST): tests/cpp/geom_test.cpp $(PKG)/host/geomFuncs.h $(PKG)/host/sfm_io.
 
 # CPU-only: the host-compiled arithmetic check of the non-GPU tests (the fakeccl target, which needs the gfx950 build and the RCCL
 # header, is a target of its own and part of `all`)
-hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libpairstatecheck.so
+hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so
 
 # TEST HARNESS: comm.cpp linked against a shared-memory stand-in for the nine RCCL calls it makes, so that a 1-GPU box can run the
 # exchange code with two real ranks (tests/test_gpu_fakeccl.py); the product's libsfm_amd_rccl.so is linked against librccl
@@ -115,12 +118,16 @@ tests/hostcheck/librefinecheck.so: tests/hostcheck/refinecheck.hip tests/hostche
 tests/hostcheck/libregistercheck.so: tests/hostcheck/registercheck.hip $(CSRC)/register_math.hpp $(CSRC)/refine_math.hpp $(CSRC)/device_math.hpp include/sfm_amd.h
 	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
 
+# the scoring block's dynamic LDS size (prefilter_lds.hpp), host-compiled for tests/test_register_budget.py
+tests/hostcheck/libpfldscheck.so: tests/hostcheck/pfldscheck.hip $(CSRC)/prefilter_lds.hpp $(CSRC)/prefilter_record.hpp $(CSRC)/prefilter_math.hpp $(CSRC)/device_math.hpp
+	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
+
 # the pair's stage bookkeeping (pair_state.hpp), built by the plain host compiler for tests/test_pair_state_host.py
 tests/hostcheck/libpairstatecheck.so: tests/hostcheck/pairstatecheck.cpp $(CSRC)/pair_state.hpp
 	g++ -O2 -std=c++17 -Wall -fPIC -shared -o $@ $<
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libpairstatecheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
+	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all ab oracle hostcheck fakeccl clean

@@ -1,0 +1,54 @@
+// prefilter_lds.hpp -- the LDS footprint of the pre-filter scoring block (ransac_prefilter.hip): tile size, per-wavefront tables and the
+// map of one block's dynamic shared memory.  Plain host + device arithmetic, in a header of its own so that the host-compiled check
+// (tests/hostcheck/pfldscheck.hip, tests/test_register_budget.py) computes the very number launch_score_prefilter asks for: the block's
+// LDS is dynamic, so the code object does not carry it.
+#pragma once
+#include "prefilter_record.hpp"
+
+namespace sfm {
+
+constexpr int kPfTileMax = 1024;         // points per tile at most; a launch picks the smallest multiple of 32 that covers the points with the fewest
+                                         // tiles (pf_tile_points).  The band rule's 80 bytes per point would allow 1536 (3 tiles for 4096 points, 11 for
+                                         // 16384: fewer, longer passes) -- measured SLOWER at every size (profiles/r05_ab_tile_size.txt: 0.369 against
+                                         // 0.360 ms at 2^20 x 4096, 0.068 against 0.058 at a rank's share): coarser passes, longer tails.  AB build,
+                                         // reserved[1] == 7: tiles of up to 1536 points.
+constexpr int kPfWaves = 16;             // wavefronts per block (LDS is laid out for 16; the kernel also runs with 12, see launch_score_prefilter)
+constexpr int kPfRing = 128;             // survivor ring entries (8 bytes) per wavefront: < 64 waiting + 64 appended per step;
+                                         // a flush re-queues at most 64 more, onto slots its own 64 entries have just left
+
+// LDS map
+constexpr int kPfERow = 10;                                   // floats per hypothesis reserved in the E table (9 used): etab[32 k + row] -- a lane's nine
+                                                              // reads for a random row hit bank (row mod 32) + const, so distinct rows never conflict
+                                                              // (row-major 40-byte rows put rows r and r + 16 on the same banks: 19 % of the LDS cycles were conflicts)
+constexpr int kPfWaveBytes = 32 * kPfERow * 4 + 32 * 4;
+// The map for a tile of `tile` points (a multiple of 32); an even number of 32-point blocks is staged (the scan takes two per iteration).
+template <int RULE> struct PfLds {
+    static constexpr int kFragsPerBlock = RULE == kPfRuleG ? 3 : 2;
+    static constexpr int kBlockBytes = kFragsPerBlock * 64 * 16;   // one 32-point block: [n k-step 0 | n k-step 1 (| G)][lane][8 fp16]
+    static constexpr int kFrag = 0;
+    static constexpr int kTileMax = kPfTileMax;
+    int staged, pts, ring, wave, next, lut, bytes;
+    __host__ __device__ explicit PfLds(int tile, int ring_entries = kPfRing, int entry_bytes = 8)
+    {
+        staged = (tile + 63) & ~63;                           // points staged: whole iterations of two blocks (beyond `tile`: padding)
+        pts = kFrag + (staged / 32) * kBlockBytes;            // float4 (x2x, x1x, x2y, x1y) per point
+        ring = pts + staged * 16;                             // the wavefronts' survivor rings, 1024 bytes each, 1024-byte aligned (a slot's
+                                                              // address is (offset & 1023) | base: one v_and_or_b32): staged is a multiple of 64
+        ring = (ring + ring_entries * entry_bytes - 1) & ~(ring_entries * entry_bytes - 1);
+        wave = ring + kPfWaves * ring_entries * entry_bytes;  // per wavefront: E table 9 x 32 floats (component-major), 32 counters
+        next = wave + kPfWaves * kPfWaveBytes;                // the block's pass counter
+        lut = next + 16;                                      // packed scan: survivor bit -> (accumulator row, step), 32 bytes (pf_pack_code)
+        bytes = lut + 32;
+    }
+};
+static_assert(kPfRing * 8 == 1024, "ring slots are addressed with (offset & 1023) | base");
+
+// Tile size of a launch: the fewest tiles of at most `tmax` points, equal sizes rounded up to 32 (4096 points: 4 x 1024; 4608: 5 x 928).
+static inline int pf_tile_points(int ld, int tmax)
+{
+    const int ntiles = (ld + tmax - 1) / tmax;
+    const int t = ((ld + ntiles - 1) / ntiles + 31) & ~31;
+    return t < 32 ? 32 : t;
+}
+
+} // namespace sfm

@@ -25,17 +25,10 @@
 #include "block_ops.hpp"
 #include "prefilter_math.hpp"
 #include "prefilter_record.hpp"
+#include "prefilter_lds.hpp"
 
 namespace sfm {
 
-constexpr int kPfTileMax = 1024;         // points per tile at most; a launch picks the smallest multiple of 32 that covers the points with the fewest
-                                         // tiles (pf_tile_points).  The band rule's 80 bytes per point would allow 1536 (3 tiles for 4096 points, 11 for
-                                         // 16384: fewer, longer passes) -- measured SLOWER at every size (profiles/r05_ab_tile_size.txt: 0.369 against
-                                         // 0.360 ms at 2^20 x 4096, 0.068 against 0.058 at a rank's share): coarser passes, longer tails.  AB build,
-                                         // reserved[1] == 7: tiles of up to 1536 points.
-constexpr int kPfWaves = 16;             // wavefronts per block (LDS is laid out for 16; the kernel also runs with 12, see launch_score_prefilter)
-constexpr int kPfRing = 128;             // survivor ring entries (8 bytes) per wavefront: < 64 waiting + 64 appended per step;
-                                         // a flush re-queues at most 64 more, onto slots its own 64 entries have just left
 typedef float f16v __attribute__((ext_vector_type(16)));
 
 // The pre-filter rule a kernel instance runs (prefilter_math.hpp): the G rule of rounds 2-4 (a per-pair threshold from a third
@@ -43,45 +36,10 @@ typedef float f16v __attribute__((ext_vector_type(16)));
 // coefficients: one v_alignbit per pair, two matrix-core instructions per 32 x 32 pairs, ~1.9 x the survivors).
 // (kPfRuleG = 0, kPfRuleBand = 1: prefilter_record.hpp)
 
-// LDS map
-constexpr int kPfERow = 10;                                   // floats per hypothesis reserved in the E table (9 used): etab[32 k + row] -- a lane's nine
-                                                              // reads for a random row hit bank (row mod 32) + const, so distinct rows never conflict
-                                                              // (row-major 40-byte rows put rows r and r + 16 on the same banks: 19 % of the LDS cycles were conflicts)
-constexpr int kPfWaveBytes = 32 * kPfERow * 4 + 32 * 4;
 // component order of the table: slot k holds E entry kPfESlot[k] -- the pairs the packed exact filter wants, (e2 e6) (e1 e3) (e5 e7)
 // (e0 e4), sit in neighbouring slots, so each arrives as ONE ds_read2_b32 in an aligned register pair (the natural order cost six
 // register moves per flush)
 __device__ constexpr int kPfESlot[9] = { 2, 6, 1, 3, 5, 7, 0, 4, 8 };
-// The map for a tile of `tile` points (a multiple of 32); an even number of 32-point blocks is staged (the scan takes two per iteration).
-template <int RULE> struct PfLds {
-    static constexpr int kFragsPerBlock = RULE == kPfRuleG ? 3 : 2;
-    static constexpr int kBlockBytes = kFragsPerBlock * 64 * 16;   // one 32-point block: [n k-step 0 | n k-step 1 (| G)][lane][8 fp16]
-    static constexpr int kFrag = 0;
-    static constexpr int kTileMax = kPfTileMax;
-    int staged, pts, ring, wave, next, lut, bytes;
-    __host__ __device__ explicit PfLds(int tile, int ring_entries = kPfRing, int entry_bytes = 8)
-    {
-        staged = (tile + 63) & ~63;                           // points staged: whole iterations of two blocks (beyond `tile`: padding)
-        pts = kFrag + (staged / 32) * kBlockBytes;            // float4 (x2x, x1x, x2y, x1y) per point
-        ring = pts + staged * 16;                             // the wavefronts' survivor rings, 1024 bytes each, 1024-byte aligned (a slot's
-                                                              // address is (offset & 1023) | base: one v_and_or_b32): staged is a multiple of 64
-        ring = (ring + ring_entries * entry_bytes - 1) & ~(ring_entries * entry_bytes - 1);
-        wave = ring + kPfWaves * ring_entries * entry_bytes;  // per wavefront: E table 9 x 32 floats (component-major), 32 counters
-        next = wave + kPfWaves * kPfWaveBytes;                // the block's pass counter
-        lut = next + 16;                                      // packed scan: survivor bit -> (accumulator row, step), 32 bytes (pf_pack_code)
-        bytes = lut + 32;
-    }
-};
-static_assert(kPfRing * 8 == 1024, "ring slots are addressed with (offset & 1023) | base");
-
-// Tile size of a launch: the fewest tiles of at most `tmax` points, equal sizes rounded up to 32 (4096 points: 4 x 1024; 4608: 5 x 928).
-static int pf_tile_points(int ld, int tmax)
-{
-    const int ntiles = (ld + tmax - 1) / tmax;
-    const int t = ((ld + ntiles - 1) / ntiles + 31) & ~31;
-    return t < 32 ? 32 : t;
-}
-
 // rejected = (rejected << 1) | sign(G - nt^2): v_fma_f32 with a negated operand and v_alignbit_b32.  Plain C++ (no inline
 // assembly), so the compiler inserts the wait states the MFMA result registers need before a vector instruction reads them.
 __device__ __forceinline__ uint32_t shift_in_reject(uint32_t rejected, float nt, float G)
@@ -220,8 +178,17 @@ constexpr int kPfVarTickets = 1;
 // WIDE (experiment): ring entries of 16 bytes that cover FOUR steps (two conversions): half as many appends
 // PRIO (experiment): s_setprio -- 1: the wavefront issues its four MFMAs and fragment loads at raised priority; 2: the exact filter of a
 // flush runs at raised priority (the default is 0 everywhere: the oldest wavefront issues first)
+// Register budget (tests/test_register_budget.py): the block keeps a CU for itself -- 16 wavefronts, 4 per SIMD -- and the lane-solve kernel
+// of the NEXT pipelined call is meant to run next to it (sfm_estimate_E_pipelined), so 4 scoring wavefronts must leave a solve wavefront's
+// registers free on every SIMD: 4 x 96 + 112 (ransac_solve_lanes1_qr: 105, allocated in eights) = 496 of 512.  The two instances the
+// product runs are compiled for five wavefronts per SIMD, which caps them at 96; the lab bench's variants keep the default.
+constexpr int pf_score_waves_per_simd(int var, int rule, int fl2, int pipe, int wide, int prio)
+{
+    return (var == 0 && (rule == kPfRuleBandTile || rule == kPfRuleBandPack) && !fl2 && !pipe && !wide && !prio) ? 5 : 4;
+}
+
 template <int W, int VAR = 0, int RULE = kPfRuleBandTile, int FL2 = 0, int PIPE = 0, int WIDE = 0, int PRIO = 0>
-__global__ __launch_bounds__(W * 64)
+__global__ __launch_bounds__(W * 64, pf_score_waves_per_simd(VAR, RULE, FL2, PIPE, WIDE, PRIO))
 void ransac_score_prefilter(const float *__restrict__ X0, const float *__restrict__ X1, int ld, int n,
                             const float *__restrict__ Ecand, const PfRecord *__restrict__ recs, uint32_t h0, uint32_t count, float thr,
                             int dynamic, int tile,
@@ -236,7 +203,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool probe = clk && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;
     unsigned long long c0 = 0, w0 = 0;
-    if (probe) { c0 = clock64(); w0 = wall_clock64(); }
+    if (clk && blockIdx.x == 0 && blockIdx.y == 0 && wave == 0) { c0 = clock64(); w0 = wall_clock64(); }      // (a wave-uniform test: the stamps stay in scalar registers)
 #if SFM_AB
     // trace (sfm_ransac_last_trace, AB build): start / end stamps of every block and wavefront, a handful of stores per block
     const uint32_t trace_blk = blockIdx.y * gridDim.x + blockIdx.x;
@@ -270,7 +237,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
     uint32_t key0 = 0u;
     float rec_dn = 0.0f, rec_lin = 0.0f;                     // tile rule: the rest of the record fetch_pass has just read
     float e_row[9] = {};
-    auto fetch_pass = [&](uint32_t pass, PfFrags &af, uint32_t &k0, float (&e)[9]) {
+    auto fetch_pass = [&](uint32_t pass, PfFrags &af, uint32_t &k0, float (&e)[9], float &dn, float &lin) {
         const uint32_t hf = pass * (uint32_t)kPfGroup;
         const uint32_t h = hf + (uint32_t)min(row, (int)min((uint32_t)kPfGroup, count - hf) - 1);
         if (kTile) {                                                                  // E and the flag word; the operands are derived at install time
@@ -278,7 +245,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
 #pragma unroll
             for (int k = 0; k < 9; ++k) e[k] = src[k];
             const uint4 rec = reinterpret_cast<const uint4 *>(recs)[h];
-            k0 = rec.x; rec_dn = __uint_as_float(rec.y); rec_lin = __uint_as_float(rec.z);
+            k0 = rec.x; dn = __uint_as_float(rec.y); lin = __uint_as_float(rec.z);
             return;
         }
         const uint4 *r = reinterpret_cast<const uint4 *>(recs + h) + 2 * half;        // this lane's half of the record: 32 bytes
@@ -301,7 +268,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
     // the first pass' operands are requested before the tile is staged: their way through the memory system overlaps it
     uint32_t ps = blockIdx.x * (uint32_t)W + (uint32_t)wave;
     bool have = ps < npass;
-    if (have) { fetch_pass(ps, afrag, key0, e_row); install_rows(e_row); }
+    if (have) { fetch_pass(ps, afrag, key0, e_row, rec_dn, rec_lin); install_rows(e_row); }
 
     SFM_PHASE("stage_tile");
     // ---- stage the tile: one point per thread -> 48 fp16 feature slots in MFMA B-fragment order + its coordinates
@@ -367,8 +334,13 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
     __syncthreads();
     // tile rule: the first pass' operands (E and the flag word are in registers)
     PfBox tbox = {};
-    auto build_operands = [&](const float (&e)[9], uint32_t fl) {
-        pf_tile_operands(e, fl, rec_dn, rec_lin, thr, pf_B, tbox, half, afrag.n0, afrag.n1);
+    auto build_operands = [&](const float (&e)[9], uint32_t fl, float dn, float lin) {
+        // what depends only on the launch (the half's side of the box, the threshold's and the bound's factors) is derived again for
+        // every pass: hoisted out of the pass loop it would sit in vector registers through every scan
+        int half_l = half;
+        float thr_l = thr, B_l = pf_B;
+        asm volatile("" : "+v"(half_l), "+s"(thr_l), "+s"(B_l));
+        pf_tile_operands(e, fl, dn, lin, thr_l, B_l, tbox, half_l, afrag.n0, afrag.n1);
         key0 = fl & kPfTileFlagScan;
     };
     if (kTile) {
@@ -376,7 +348,9 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
         for (int k = 0; k < 8; ++k) bw[k] = (uint32_t)__builtin_amdgcn_readlane((int)bw_lane, k);
         pf_B = uniform(pf_B);
         tbox = pf_box_from_bits(bw, pf_B);
-        if (have) build_operands(e_row, key0);
+        // (the fences leave the bounds in vector registers; they are the same in every lane: handed to scalar registers for the rest of the launch)
+        tbox = PfBox{ uniform(tbox.xlo), uniform(tbox.xhi), uniform(tbox.ylo), uniform(tbox.yhi), uniform(tbox.ulo), uniform(tbox.uhi), uniform(tbox.vlo), uniform(tbox.vhi) };
+        if (have) build_operands(e_row, key0, rec_dn, rec_lin);
     }
 #if SFM_AB
     if (probe) clk[2] = wall_clock64() - w0;
@@ -705,7 +679,8 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
         const bool have_next = ps_next < npass;
         PfFrags afrag_next = afrag;
         uint32_t key0n = 0u;
-        if (have_next) fetch_pass(ps_next, afrag_next, key0n, e_row);
+        float e_next[9] = {}, dn_next = 0.0f, lin_next = 0.0f;      // (a pass' own copies: nothing of the previous fetch stays live across the scan)
+        if (have_next) fetch_pass(ps_next, afrag_next, key0n, e_next, dn_next, lin_next);
         SFM_PHASE("drain_flush");
         if (FL2) { while (nq >= 128) flush2(); }
         if (WIDE) { while (nq > 0) flush_w(min(nq, 64)); }
@@ -758,9 +733,9 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
         const int nvalid_done = nvalid;
         const uint32_t h_done = h_first;
         if (have_next) {
-            if (kTile) build_operands(e_row, key0n);
+            if (kTile) build_operands(e_next, key0n, dn_next, lin_next);
             else { afrag = afrag_next; key0 = key0n; }
-            install_rows(e_row);
+            install_rows(e_next);
         }
         unsigned long long k = 0;
         if (lane < nvalid_done && (uint32_t)(old >> 32) == gridDim.y - 1u) {
@@ -785,7 +760,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
         have = have_next;
         if (have_next) {
             ps = ps_next;
-            if (VAR & kPfVarTickets) { afrag = afrag_next; key0 = key0n; install_rows(e_row); }     // (otherwise installed above, under the accumulator's round trip)
+            if (VAR & kPfVarTickets) { afrag = afrag_next; key0 = key0n; install_rows(e_next); }     // (otherwise installed above, under the accumulator's round trip)
         }
     }
     SFM_PHASE("kernel_end");
