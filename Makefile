@@ -32,7 +32,7 @@ RPDEMO   := $(PKG)/host/refine_pairs_demo
 IOTEST   := tests/cpp/io_test
 GEOMTEST := tests/cpp/geom_test
 
-all: $(LIB) $(LIB_AB) $(COMMLIB) oracle hostcheck fakeccl $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(IOTEST) $(GEOMTEST)
+all: $(LIB) $(LIB_AB) $(COMMLIB) $(BUILD)/ransac.s oracle hostcheck fakeccl $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(IOTEST) $(GEOMTEST)
 
 # the product's objects come with the compiler's resource-usage report (registers, scratch, LDS of every kernel) next to them:
 # $(BUILD)/<source>.usage.txt, read by tests/test_register_budget.py; warnings and errors of the compile are still shown
@@ -40,6 +40,12 @@ $(BUILD)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(FLAGS_$*) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(BUILD)/$*.usage.txt || { cat $(BUILD)/$*.usage.txt >&2; exit 1; }
 	@grep -v -e 'remark:' -e '^ *[0-9]* | ' -e '^ *| ' $(BUILD)/$*.usage.txt >&2 || true
+
+# the instruction text of ransac.hip's kernels as the product compiles them (the object's flags, assembly out): the lane-solve kernels'
+# issue budget is read from it (tests/test_solve_issue_budget.py, profiles/isa_census.py)
+$(BUILD)/ransac.s: $(CSRC)/ransac.hip $(HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) $(FLAGS_ransac) --cuda-device-only -S $< -o $@
 
 $(BUILD_AB)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(BUILD_AB)

@@ -62,6 +62,36 @@ void ransac_solve_lanes(const float *__restrict__ X0, const float *__restrict__ 
     for (int k = 0; k < 9; ++k) Ecand[9 * (size_t)i + k] = E[k];
 }
 
+// Addressing of the lane-solve kernels below: every access is a wave-uniform base (kernel argument, or argument + the block's
+// first element, both in scalar registers) plus an unsigned 32-bit byte offset per lane, the form global_load / global_store take
+// with the base in an SGPR pair and ONE vector register -- no 64-bit vector add (a VOP3: twice the issue time of a 32-bit shift)
+// in front of each access.  Per-lane outputs are addressed from the block's base, so their offsets stay below 64 elements
+// whatever the launch; a gathered 16-byte record's offset is idx * 16, which fits for point sets up to kOffset32MaxPoints.  Not covered:
+// the scattered words of generic-z points (three row bases per view: the compiler keeps a 64-bit address per lane for rows 1 and 2).
+constexpr int kOffset32MaxPoints = 1 << 28;
+template <class T>
+__device__ __forceinline__ T *at_u32(T *base, uint32_t byte_off)
+{
+    typedef typename std::conditional<std::is_const<T>::value, const char, char>::type B;
+    return reinterpret_cast<T *>(reinterpret_cast<B *>(base) + byte_off);
+}
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+// The sample's eight correspondences out of the 16-byte records.  Each record is ONE 16-byte load: read through float4's members the four
+// words become scalar loads, which the compiler merges with the scattered branch's into 32 dword gathers on 32 addresses.
+// OFF32: offsets as above; otherwise (point sets beyond kOffset32MaxPoints; no test reaches them) a 64-bit address per lane.
+template <bool OFF32>
+__device__ __forceinline__ void gather8_records(const float4 *__restrict__ pts4, const int (&idx)[8], float (&x1)[8][3], float (&x2)[8][3])
+{
+    const f32x4 *recs = reinterpret_cast<const f32x4 *>(pts4);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const f32x4 q = OFF32 ? *at_u32(recs, (uint32_t)idx[k] * 16u) : recs[idx[k]];
+        x1[k][0] = q.x; x1[k][1] = q.y; x1[k][2] = 1.0f;
+        x2[k][0] = q.z; x2[k][1] = q.w; x2[k][2] = 1.0f;
+    }
+}
+
 // One hypothesis per lane, Householder solver only (the scalar instantiation of the same templates: bit-identical).  Half the
 // registers of the packed kernel below, so twice the hypotheses are in flight per SIMD and every wavefront walks a chain of plain
 // (not packed) instructions: the latency-bound regime -- shards of up to a few hundred thousand hypotheses, where the packed
@@ -78,24 +108,21 @@ void solve_lanes1_qr_body(const float *__restrict__ X0, const float *__restrict_
                           const uint32_t *__restrict__ cells, uint32_t cells_mask, int rule)
 {
     reset_keys(zero_key, zero_key2);
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t blk = blockIdx.x * blockDim.x;           // the block's first hypothesis (wave-uniform)
+    const uint32_t i = blk + threadIdx.x;
     // the pre-filter kernel's per-hypothesis accumulators (two words each: count | tiles arrived), cleared here
     if (zero_ticks) for (uint32_t w = i; w < nzero; w += gridDim.x * blockDim.x) zero_ticks[w] = 0u;
     if (i >= count) return;
-    if (zero_counts) zero_counts[i] = 0;
+    if (zero_counts) *at_u32(zero_counts + blk, threadIdx.x * 4u) = 0;
     SFM_PHASE("sampler");
     int idx[8];
     load_tuple(indices, seed, h0 + i, n, idx);
     SFM_PHASE("gather");
     float x1[8][3], x2[8][3];
     if (pts4) {                                             // unit-z points as 16-byte records: 8 gathers instead of 48
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const float4 q = pts4[idx[k]];
-            x1[k][0] = q.x; x1[k][1] = q.y; x1[k][2] = 1.0f;
-            x2[k][0] = q.z; x2[k][1] = q.w; x2[k][2] = 1.0f;
-        }
-    } else {
+        if (n <= kOffset32MaxPoints) gather8_records<true>(pts4, idx, x1, x2);      // (wave-uniform)
+        else gather8_records<false>(pts4, idx, x1, x2);
+    } else {                                                // generic z: 48 scattered words, a 64-bit address each (three row bases per view)
 #pragma unroll
         for (int k = 0; k < 8; ++k)
 #pragma unroll
@@ -110,18 +137,23 @@ void solve_lanes1_qr_body(const float *__restrict__ X0, const float *__restrict_
     SFM_PHASE("normalize_E");
     normalize_E(E);
     SFM_PHASE("store_E");
+    float *const Eblk = Ecand + 9 * (size_t)blk;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) Ecand[9 * (size_t)i + k] = E[k];
+    for (int k = 0; k < 9; ++k) *at_u32(Eblk, threadIdx.x * 36u + 4u * k) = E[k];
     SFM_PHASE("record");
     // the operands of the matrix-core pre-filter for this hypothesis (prefilter_record.hpp), once for all tiles
     if (recs) {
         const float B = __uint_as_float((uint32_t)(*bound_word & 0xFFFFFFFFull));
-        if (TILE) reinterpret_cast<uint4 *>(recs)[i] = pf_tile_record(E, B, cells, cells_mask);        // sigma and the slots: per (hypothesis, tile), in the scoring kernel
+        if (TILE) *at_u32(reinterpret_cast<uint4 *>(recs) + blk, threadIdx.x * 16u) = pf_tile_record(E, B, cells, cells_mask);        // sigma and the slots: per (hypothesis, tile), in the scoring kernel
+        else {
+            PfRecord *const rec = at_u32(recs + blk, threadIdx.x * (uint32_t)sizeof(PfRecord));
 #if SFM_AB
-        else if (rule == kPfRuleG) pf_prep_store(E, thr, B, sc, cells, cells_mask, recs + i);
-        else if (rule == kPfRuleBand) pf_band_prep_store(E, thr, B, pf_box_from_bound(bound_word, B), cells, cells_mask, recs + i, kPfBandTop);
+            if (rule == kPfRuleG) pf_prep_store(E, thr, B, sc, cells, cells_mask, rec);
+            else if (rule == kPfRuleBand) pf_band_prep_store(E, thr, B, pf_box_from_bound(bound_word, B), cells, cells_mask, rec, kPfBandTop);
+            else
 #endif
-        else pf_band_prep_store(E, thr, B, pf_box_from_bound(bound_word, B), cells, cells_mask, recs + i, kPfBandTopPack);
+            pf_band_prep_store(E, thr, B, pf_box_from_bound(bound_word, B), cells, cells_mask, rec, kPfBandTopPack);
+        }
     }
     (void)sc; (void)rule;
     SFM_PHASE("end");

@@ -180,7 +180,7 @@ constexpr int kPfVarTickets = 1;
 // flush runs at raised priority (the default is 0 everywhere: the oldest wavefront issues first)
 // Register budget (tests/test_register_budget.py): the block keeps a CU for itself -- 16 wavefronts, 4 per SIMD -- and the lane-solve kernel
 // of the NEXT pipelined call is meant to run next to it (sfm_estimate_E_pipelined), so 4 scoring wavefronts must leave a solve wavefront's
-// registers free on every SIMD: 4 x 96 + 112 (ransac_solve_lanes1_qr: 105, allocated in eights) = 496 of 512.  The two instances the
+// registers free on every SIMD: 4 x 96 + 88 (ransac_solve_lanes1_qr: 88, allocated in eights) = 472 of 512.  The two instances the
 // product runs are compiled for five wavefronts per SIMD, which caps them at 96; the lab bench's variants keep the default.
 constexpr int pf_score_waves_per_simd(int var, int rule, int fl2, int pipe, int wide, int prio)
 {
