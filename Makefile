@@ -102,7 +102,7 @@ $(GEOMTEST): tests/cpp/geom_test.cpp $(PKG)/host/geomFuncs.h $(PKG)/host/sfm_io.
 
 # CPU-only: the host-compiled arithmetic check of the non-GPU tests (the fakeccl target, which needs the gfx950 build and the RCCL
 # header, is a target of its own and part of `all`)
-hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so
+hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so
 
 # TEST HARNESS: comm.cpp linked against a shared-memory stand-in for the nine RCCL calls it makes, so that a 1-GPU box can run the
 # exchange code with two real ranks (tests/test_gpu_fakeccl.py); the product's libsfm_amd_rccl.so is linked against librccl
@@ -128,12 +128,17 @@ tests/hostcheck/libregistercheck.so: tests/hostcheck/registercheck.hip $(CSRC)/r
 tests/hostcheck/libpfldscheck.so: tests/hostcheck/pfldscheck.hip $(CSRC)/prefilter_lds.hpp $(CSRC)/prefilter_record.hpp $(CSRC)/prefilter_math.hpp $(CSRC)/device_math.hpp
 	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
 
+# the job layout and matcher-launch grouping of a batched sfm_process_pairs call (pairs_batch.hpp), host-compiled for
+# tests/test_pairs_plan_host.py
+tests/hostcheck/libpairsplancheck.so: tests/hostcheck/pairsplancheck.hip $(CSRC)/pairs_batch.hpp $(CSRC)/common.hpp $(CSRC)/pair_state.hpp include/sfm_amd.h
+	$(HIPCC) -x hip --cuda-host-only -O2 -fPIC -shared -Wall -Wno-pass-failed -o $@ $<
+
 # the pair's stage bookkeeping (pair_state.hpp), built by the plain host compiler for tests/test_pair_state_host.py
 tests/hostcheck/libpairstatecheck.so: tests/hostcheck/pairstatecheck.cpp $(CSRC)/pair_state.hpp
 	g++ -O2 -std=c++17 -Wall -fPIC -shared -o $@ $<
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
+	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all ab oracle hostcheck fakeccl clean

@@ -1,6 +1,5 @@
-// abi.hip -- implementation of the C ABI declared in include/sfm_amd.h.
+// abi.hip -- implementation of the C ABI declared in include/sfm_amd.h (its two host-side drivers: views.hip, pairs.hip).
 #include "common.hpp"
-#include "pairs_batch.hpp"
 #include "device_math.hpp"
 #include <stdarg.h>
 #include <stdio.h>
@@ -8,8 +7,6 @@
 #include <new>
 #include <atomic>
 #include <utility>
-#include <thread>
-#include <mutex>
 #include <vector>
 #include <algorithm>
 #include <functional>
@@ -56,9 +53,6 @@ static int resolve_shard(const sfm_pair *pair, const sfm_ransac_params *p, uint3
     return SFM_OK;
 }
 
-// the last row of K^-1 is (0 0 1): every normalised z is exactly 1
-static bool unit_z_Kinv(const float h_Kinv[9]) { return h_Kinv[6] == 0.0f && h_Kinv[7] == 0.0f && h_Kinv[8] == 1.0f; }
-
 // buffers that are allocated together on first use: all of them or none
 struct BufSpec { void **ptr; size_t bytes; };
 static int alloc_group(std::initializer_list<BufSpec> bufs)
@@ -91,6 +85,44 @@ static int copy_out(sfm_pair *pair, void *h_dst, const void *d_src, size_t bytes
     SFM_HIP_TRY(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, pair->ctx->stream));
     SFM_HIP_TRY(hipStreamSynchronize(pair->ctx->stream));
     return SFM_OK;
+}
+
+// rows of the second view that MatchSiftData visits (matching.cu:325: under SFM_QUIRK_MATCH_TAIL the tile loop stops 32 points short)
+int match_db_rows(const sfm_ctx *ctx, int n2) { return (ctx->quirks & SFM_QUIRK_MATCH_TAIL) ? n2 - n2 % 32 : n2; }
+
+// THE matcher rule for SiftPoint records (sfm_match, and every pair of sfm_process_pairs that is not part of a many-matches launch)
+int match_records(sfm_ctx *ctx, sfm_sift_point *d_sift1, int n1, const sfm_sift_point *d_sift2, int n2, int *out_idx)
+{
+    n2 = match_db_rows(ctx, n2);
+    if (n2 == 0) {                                                      // nothing left to match against: index -1 everywhere
+        const int rc = launch_match_none(ctx, n1, d_sift1);
+        if (rc == SFM_OK && out_idx) SFM_HIP_TRY(hipMemsetAsync(out_idx, 0xFF, (size_t)n1 * 4, ctx->stream));
+        return rc;
+    }
+    const int ld = (int)(sizeof(sfm_sift_point) / sizeof(float));
+    const int rc = launch_match(ctx, d_sift1->data, n1, ld, d_sift2->data, n2, ld, nullptr, nullptr, out_idx, d_sift1, d_sift2);
+    if (rc != SFM_OK || !(ctx->quirks & SFM_QUIRK_MATCH_AMBIGUITY)) return rc;
+    return launch_match_ambiguity_quirk(ctx, d_sift1->data, n1, ld, d_sift2->data, n2, ld, d_sift1, nullptr);      // matching.cu:378-396
+}
+
+// poses, triangulation and (d_record given) the pair's record on the device: one launch in SFM_POSE_REFERENCE, four otherwise
+int pose_chain(sfm_pair *pair, int mode, float *d_record)
+{
+    SFM_REQUIRE(pair, SFM_E_INVALID, "null pair");
+    SFM_FLUSH(pair);
+    SFM_REQUIRE(mode == SFM_POSE_REFERENCE || mode == SFM_POSE_CORRECT, SFM_E_INVALID, "unknown pose mode %d", mode);
+    SFM_NEED(pair, kE);
+    if (mode == SFM_POSE_CORRECT) {               // the majority vote needs every point before the choice: three launches
+        int rc = sfm_pose_candidates(pair, mode);
+        if (rc == SFM_OK) rc = sfm_choose_pose(pair, mode);
+        if (rc == SFM_OK) rc = sfm_triangulate(pair, mode);
+        if (rc == SFM_OK && d_record) rc = launch_pair_record(pair, mode, d_record);
+        return rc;
+    }
+    SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
+    const int rc = launch_pose_chain(pair, d_record);
+    if (rc == SFM_OK) { pair->state.chain_done(); pair->pose_mode = mode; }
+    return rc;
 }
 
 } // namespace sfm
@@ -374,14 +406,7 @@ int sfm_match(sfm_ctx *ctx, sfm_sift_point *d_sift1, int n1, const sfm_sift_poin
     SFM_REQUIRE(n1 >= 0 && n2 >= 0, SFM_E_INVALID, "negative point count");
     if (n1 == 0 || n2 == 0 || !d_sift1 || !d_sift2) return SFM_OK;      // matching.cu:1095-1102
     SFM_HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->quirks & SFM_QUIRK_MATCH_TAIL) {                           // matching.cu:325: the tile loop stops 32 points short
-        n2 -= n2 % 32;
-        if (n2 == 0) return launch_match_none(ctx, n1, d_sift1);
-    }
-    const int ld = (int)(sizeof(sfm_sift_point) / sizeof(float));
-    const int rc = launch_match(ctx, d_sift1->data, n1, ld, d_sift2->data, n2, ld, nullptr, nullptr, nullptr, d_sift1, d_sift2);
-    if (rc != SFM_OK || !(ctx->quirks & SFM_QUIRK_MATCH_AMBIGUITY)) return rc;
-    return launch_match_ambiguity_quirk(ctx, d_sift1->data, n1, ld, d_sift2->data, n2, ld, d_sift1, nullptr);      // matching.cu:378-396
+    return match_records(ctx, d_sift1, n1, d_sift2, n2, nullptr);
 }
 
 int sfm_match_soa(sfm_ctx *ctx, const float *d_desc1, int n1, int ld1, const float *d_desc2, int n2, int ld2,
@@ -785,25 +810,6 @@ int sfm_triangulate(sfm_pair *pair, int mode)
     return rc;
 }
 
-static int pose_chain(sfm_pair *pair, int mode, float *d_record)
-{
-    SFM_REQUIRE(pair, SFM_E_INVALID, "null pair");
-    SFM_FLUSH(pair);
-    SFM_REQUIRE(mode == SFM_POSE_REFERENCE || mode == SFM_POSE_CORRECT, SFM_E_INVALID, "unknown pose mode %d", mode);
-    SFM_NEED(pair, kE);
-    if (mode == SFM_POSE_CORRECT) {               // the majority vote needs every point before the choice: three launches
-        int rc = sfm_pose_candidates(pair, mode);
-        if (rc == SFM_OK) rc = sfm_choose_pose(pair, mode);
-        if (rc == SFM_OK) rc = sfm_triangulate(pair, mode);
-        if (rc == SFM_OK && d_record) rc = launch_pair_record(pair, mode, d_record);
-        return rc;
-    }
-    SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
-    const int rc = launch_pose_chain(pair, d_record);
-    if (rc == SFM_OK) { pair->state.chain_done(); pair->pose_mode = mode; }
-    return rc;
-}
-
 int sfm_pose_chain(sfm_pair *pair, int mode) { return pose_chain(pair, mode, nullptr); }
 
 // ---- two-view bundle adjustment (refine.hip) ------------------------------------------------------
@@ -1169,457 +1175,6 @@ int sfm_copy_points_to_vbo(sfm_pair *pair, float *d_positions, float *d_velociti
     SFM_REQUIRE((((uintptr_t)d_positions | (uintptr_t)d_velocities) & 15u) == 0, SFM_E_INVALID, "vertex buffers must be 16-byte aligned");
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
     return launch_points_to_vbo(pair, d_positions, d_velocities, scale);
-}
-
-// ---- lanes: the caller's context + auxiliary contexts with streams of their own (sfm_extract_views, sfm_process_pairs) ----
-// out[0] = ctx, out[1 .. n) = the first n - 1 lane contexts, created on first use; every call hands them the caller's matcher
-// choice and SFM_QUIRK_* flags (every pair of one call honours the same ones)
-static int lane_contexts(sfm_ctx *ctx, int n, sfm_ctx **out)
-{
-    out[0] = ctx;
-    for (int l = 1; l < n; ++l) {
-        if (!ctx->lane[l - 1]) {
-            int rc = sfm_ctx_create(ctx->device, &ctx->lane[l - 1]);
-            if (rc == SFM_OK) rc = sfm_ctx_own_stream(ctx->lane[l - 1]);
-            if (rc != SFM_OK) return rc;
-        }
-        out[l] = ctx->lane[l - 1];
-        out[l]->match_kernel = ctx->match_kernel;
-        out[l]->quirks = ctx->quirks;
-    }
-    return SFM_OK;
-}
-
-// the caller's stream waits for lanes 1 .. n - 1; the first failure is kept in *rc (an earlier one is not overwritten)
-static void join_lanes(sfm_ctx *ctx, sfm_ctx *const *lanes, int n, int *rc)
-{
-    for (int l = 1; l < n; ++l) {
-        const hipError_t e1 = hipEventRecord(ctx->lane_ev[l], lanes[l]->stream);
-        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(ctx->stream, ctx->lane_ev[l], 0) : e1;
-        if (e2 != hipSuccess && *rc == SFM_OK) { set_error("lane join failed: %s", hipGetErrorString(e2)); *rc = SFM_E_HIP; }
-    }
-}
-
-// a pair sfm_process_pairs can work on: enough features for the 8-point solver, a second view (if given) that is not empty
-static bool usable(const sfm_pair_desc &d) { return d.n1 >= 8 && (!d.d_sift2 || d.n2 >= 1); }
-
-// Pairs that share their FIRST view stay on one lane in list order: the k-th distinct first view goes to lane k % nlanes.
-static sfm_ctx *lane_of_first_view(std::vector<const void *> &first_views, const void *sift1, sfm_ctx *const *lanes, int nlanes)
-{
-    size_t v = 0;
-    while (v < first_views.size() && first_views[v] != sift1) ++v;
-    if (v == first_views.size()) first_views.push_back(sift1);
-    return lanes[v % (size_t)nlanes];
-}
-
-// ---- many views: ExtractSift for a rank's share of the images --------------------------------------------------------
-static int views_buffers(sfm_ctx *c, size_t floats)
-{
-    if (!c->views_ev) SFM_HIP_TRY(hipEventCreateWithFlags(&c->views_ev, hipEventDisableTiming));
-    if (c->views_floats >= floats) return SFM_OK;
-    SFM_HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->views_pinned) (void)hipHostFree(c->views_pinned);
-    c->views_pinned = nullptr; c->views_floats = 0;     // (the size counts for both: the device image grows last)
-    SFM_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->views_pinned), floats * sizeof(float), hipHostMallocDefault));
-    return grow(&c->views_image, &c->views_floats, floats, c->stream);
-}
-
-// 8-bit grey values -> float (exact), four pixels per thread; count is a multiple of four (the pitch is a multiple of 128)
-__global__ __launch_bounds__(256)
-void views_u8_to_float_kernel(const uchar4 *__restrict__ src, float4 *__restrict__ dst, size_t count4)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count4) return;
-    const uchar4 v = src[i];
-    dst[i] = make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);
-}
-
-// h_images: float images (bytes_per_pixel 4) or 8-bit grey images (bytes_per_pixel 1: a quarter of the PCIe traffic, the
-// conversion -- exact -- runs on the device in front of the extraction)
-static int extract_views_impl(sfm_ctx *ctx, const void *const *h_images, int bytes_per_pixel, int num_views, int width, int height, int first, int stride,
-                              void *d_block, size_t slot_bytes, int max_pts, int num_octaves, double init_blur, float thresh,
-                              float lowest_scale, int scale_up, int *h_counts)
-{
-    const bool u8 = bytes_per_pixel == 1;
-    SFM_REQUIRE(ctx && h_images && d_block, SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(num_views >= 0 && first >= 0 && stride >= 1, SFM_E_INVALID, "bad view range");
-    SFM_REQUIRE(width > 0 && height > 0 && width <= 16384 && height <= 16384, SFM_E_INVALID, "image size %d x %d", width, height);
-    SFM_REQUIRE(num_octaves >= 1 && num_octaves <= 7 && max_pts > 0, SFM_E_INVALID, "bad extraction parameters");
-    SFM_REQUIRE(slot_bytes >= (size_t)max_pts * sizeof(sfm_sift_point) + 4 && slot_bytes % 16 == 0, SFM_E_INVALID,
-                "slot_bytes %zu: need max_pts records + the count, a multiple of 16", slot_bytes);
-    SFM_HIP_TRY(hipSetDevice(ctx->device));
-    // EIGHT contexts (the caller's + the auxiliary lanes): one image's per-level kernels leave most CUs idle, and every view
-    // ends with a host synchronisation (its feature count), so eight views are in flight on eight streams.
-    constexpr int NC = sfm_ctx::kViewLanes;           // contexts
-    constexpr int NR = 2 * NC;                        // pinned staging buffers (two per context)
-    constexpr int NT = 3;                             // helper threads that fill them
-    sfm_ctx *cs[NC];
-    const int rcl = lane_contexts(ctx, NC, cs);
-    if (rcl != SFM_OK) return rcl;
-    const int pitch = round_up(width, 128);
-    const size_t floats = (size_t)pitch * height;
-    // device image per context; pinned staging buffers filled by helper threads that run ahead of the enqueueing thread:
-    // the row-by-row copy into pinned memory is the host-side cost of a view (~0.1 ms for 720 x 576, about what its
-    // extraction takes and more than its upload), so it must neither sit between two enqueues nor be done by ONE thread
-    for (sfm_ctx *c : cs) { int rc = views_buffers(c, 2 * floats); if (rc != SFM_OK) return rc; }
-    float *ring[NR], *image[NC];
-    for (int k = 0; k < NC; ++k) { ring[k] = cs[k]->views_pinned; ring[NC + k] = cs[k]->views_pinned + floats; image[k] = cs[k]->views_image; }
-    SFM_HIP_TRY(hipEventRecord(ctx->views_ev, ctx->stream));                 // the lanes start after what the caller enqueued
-    for (int k = 1; k < NC; ++k) SFM_HIP_TRY(hipStreamWaitEvent(cs[k]->stream, ctx->views_ev, 0));
-    int nown = 0;
-    for (int v = first; v < num_views; v += stride) { SFM_REQUIRE(h_images[v], SFM_E_INVALID, "view %d: null image", v); ++nown; }
-    if (nown == 0) return SFM_OK;
-    // Threads: NT stagers fill the pinned buffers (view i -> buffer i % NR, once view i - NR is through); one worker per
-    // context uploads, enqueues and reads back the count of the views i = k, k + NC, ... -- about fifteen runtime calls per
-    // view, 60-100 us of host time.  With float images the uploads (1.66 MB per 720 x 576 view, one copy engine) bound the
-    // front end and a single enqueueing thread is enough; with 8-bit images (a quarter of the bytes) the enqueueing thread did.
-    std::vector<std::atomic<int>> staged((size_t)nown), finished((size_t)nown);
-    for (auto &f : staged) f.store(0, std::memory_order_relaxed);
-    for (auto &f : finished) f.store(0, std::memory_order_relaxed);
-    std::atomic<int> stop(0), first_rc(SFM_OK);
-    std::mutex err_mutex;
-    char err_text[512] = "";
-    auto stage = [&](int t) {
-        for (int i = t; i < nown && !stop.load(std::memory_order_relaxed); i += NT) {
-            while (i >= NR && finished[(size_t)(i - NR)].load(std::memory_order_acquire) == 0 && !stop.load(std::memory_order_relaxed)) std::this_thread::yield();
-            char *pin = reinterpret_cast<char *>(ring[i % NR]);
-            const char *src = static_cast<const char *>(h_images[first + i * stride]);
-            const size_t px = (size_t)bytes_per_pixel;
-            for (int y = 0; y < height; ++y) {
-                memcpy(pin + (size_t)y * pitch * px, src + (size_t)y * width * px, (size_t)width * px);
-                if (pitch > width) memset(pin + ((size_t)y * pitch + width) * px, 0, (size_t)(pitch - width) * px);
-            }
-            staged[(size_t)i].store(1, std::memory_order_release);
-        }
-    };
-    char *block = static_cast<char *>(d_block);
-    std::vector<int> counts((size_t)nown, 0);
-    auto fail = [&](int rc) {
-        int expected = SFM_OK;
-        if (first_rc.compare_exchange_strong(expected, rc)) {
-            std::lock_guard<std::mutex> g(err_mutex);
-            snprintf(err_text, sizeof(err_text), "%s", sfm_last_error());      // (the message lives in this thread's buffer)
-        }
-        stop.store(1, std::memory_order_relaxed);
-    };
-    auto work = [&](int k) {
-        if (hipSetDevice(ctx->device) != hipSuccess) { set_error("hipSetDevice failed in a view worker"); fail(SFM_E_HIP); return; }
-        for (int i = k; i < nown && !stop.load(std::memory_order_relaxed); i += NC) {
-            while (staged[(size_t)i].load(std::memory_order_acquire) == 0 && !stop.load(std::memory_order_relaxed)) std::this_thread::yield();
-            if (stop.load(std::memory_order_relaxed)) break;
-            hipError_t e;
-            if (u8) {
-                // (the second half of the context's device image buffer holds the bytes until the kernel has widened them)
-                unsigned char *d_bytes = reinterpret_cast<unsigned char *>(image[k] + floats);
-                e = hipMemcpyAsync(d_bytes, ring[i % NR], floats, hipMemcpyHostToDevice, cs[k]->stream);
-                if (e == hipSuccess) {
-                    hipLaunchKernelGGL(views_u8_to_float_kernel, dim3((unsigned)((floats / 4 + 255) / 256)), dim3(256), 0, cs[k]->stream,
-                                       reinterpret_cast<const uchar4 *>(d_bytes), reinterpret_cast<float4 *>(image[k]), floats / 4);
-                    e = hipGetLastError();
-                }
-            } else {
-                e = hipMemcpyAsync(image[k], ring[i % NR], floats * sizeof(float), hipMemcpyHostToDevice, cs[k]->stream);
-            }
-            if (e != hipSuccess) { set_error("view upload failed: %s", hipGetErrorString(e)); fail(SFM_E_HIP); break; }
-            int rc = launch_extract_sift_begin(cs[k], reinterpret_cast<sfm_sift_point *>(block + (size_t)i * slot_bytes), max_pts, image[k],
-                                               width, height, pitch, num_octaves, init_blur, thresh, lowest_scale, scale_up ? 1 : 0, nullptr);
-            int n = 0, stored = 0;
-            if (rc == SFM_OK) rc = launch_extract_sift_end(cs[k], &n, &stored);    // waits for this context's stream: its upload is done too
-            if (rc != SFM_OK) { fail(rc); break; }
-            counts[(size_t)i] = n;
-            finished[(size_t)i].store(1, std::memory_order_release);           // staging buffer i % NR may be refilled
-        }
-    };
-    std::vector<std::thread> threads;
-    // the caller's thread takes the LAST context: it starts after the others have been spawned, and the last contexts get one
-    // view fewer when the views do not divide evenly (36 views on eight contexts: 5 5 5 5 4 4 4 4)
-    const int lanes_used = nown < NC ? nown : NC;
-    bool spawned = true;
-    try {
-        for (int t = 0; t < NT && t < nown; ++t) threads.emplace_back(stage, t);
-        for (int k = 0; k + 1 < lanes_used; ++k) threads.emplace_back(work, k);
-    } catch (...) {                                       // (std::system_error: the process is out of threads)
-        spawned = false;
-        stop.store(1, std::memory_order_relaxed);
-    }
-    if (spawned) work(lanes_used - 1);
-    for (std::thread &t : threads) t.join();
-    if (!spawned) {
-        for (sfm_ctx *c : cs) (void)hipStreamSynchronize(c->stream);
-        set_error("sfm_extract_views could not start its worker threads");
-        return SFM_E_NOMEM;
-    }
-    if (first_rc.load() != SFM_OK) {
-        for (sfm_ctx *c : cs) (void)hipStreamSynchronize(c->stream);
-        set_error("%s", err_text);
-        return first_rc.load();
-    }
-    // the feature counts of all slots with ONE strided copy
-    SFM_HIP_TRY(hipMemcpy2DAsync(block + (size_t)max_pts * sizeof(sfm_sift_point), slot_bytes, counts.data(), sizeof(int), sizeof(int), (size_t)nown,
-                                 hipMemcpyHostToDevice, ctx->stream));
-    SFM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (h_counts) memcpy(h_counts, counts.data(), (size_t)nown * sizeof(int));
-    return SFM_OK;
-}
-
-int sfm_extract_views(sfm_ctx *ctx, const float *const *h_images, int num_views, int width, int height, int first, int stride,
-                      void *d_block, size_t slot_bytes, int max_pts, int num_octaves, double init_blur, float thresh,
-                      float lowest_scale, int scale_up, int *h_counts)
-{
-    return extract_views_impl(ctx, reinterpret_cast<const void *const *>(h_images), 4, num_views, width, height, first, stride, d_block, slot_bytes,
-                              max_pts, num_octaves, init_blur, thresh, lowest_scale, scale_up, h_counts);
-}
-
-int sfm_extract_views_u8(sfm_ctx *ctx, const unsigned char *const *h_images, int num_views, int width, int height, int first, int stride,
-                         void *d_block, size_t slot_bytes, int max_pts, int num_octaves, double init_blur, float thresh,
-                         float lowest_scale, int scale_up, int *h_counts)
-{
-    return extract_views_impl(ctx, reinterpret_cast<const void *const *>(h_images), 1, num_views, width, height, first, stride, d_block, slot_bytes,
-                              max_pts, num_octaves, init_blur, thresh, lowest_scale, scale_up, h_counts);
-}
-
-// ---- many view pairs --------------------------------------------------------------------------------
-int sfm_process_pairs(sfm_ctx *ctx, const float h_K[9], const float h_Kinv[9], const sfm_pair_desc *pairs, int num_pairs,
-                      int first, int stride, uint32_t num_hypotheses, int pose_mode, float *h_records, int *h_status)
-{
-    SFM_REQUIRE(ctx && h_K && h_Kinv && h_records, SFM_E_INVALID, "null argument");
-    SFM_REQUIRE(num_pairs >= 0 && first >= 0 && stride >= 1, SFM_E_INVALID, "bad pair range (%d pairs, first %d, stride %d)", num_pairs, first, stride);
-    SFM_REQUIRE(pose_mode == SFM_POSE_REFERENCE || pose_mode == SFM_POSE_CORRECT, SFM_E_INVALID, "unknown pose mode %d", pose_mode);
-    SFM_REQUIRE(num_pairs == 0 || pairs, SFM_E_INVALID, "null pair list");
-    SFM_HIP_TRY(hipSetDevice(ctx->device));
-    int owned = 0, max_n = 0;
-    for (int i = first; i < num_pairs; i += stride) {
-        SFM_REQUIRE(pairs[i].n1 >= 0 && pairs[i].n2 >= 0, SFM_E_INVALID, "pair %d: negative feature count", i);
-        SFM_REQUIRE(pairs[i].n1 == 0 || pairs[i].d_sift1, SFM_E_INVALID, "pair %d: null feature pointer", i);
-        if (pairs[i].n1 > max_n) max_n = pairs[i].n1;
-        ++owned;
-    }
-    if (owned == 0) return SFM_OK;
-    int rc = SFM_OK;
-    // lanes: the context itself + up to three auxiliary contexts on streams of their own.  Pairs that share their FIRST view
-    // stay on one lane in list order (MatchSiftData writes that view's match fields, fillXU reads them); everything else
-    // of a record is only read, so different lanes may work on pairs that share views.
-    const int nlanes = owned >= 8 ? sfm_ctx::kPairLanes : 1;
-    sfm_ctx *lanes[sfm_ctx::kPairLanes] = {};
-    static_assert(sfm_ctx::kViewLanes >= sfm_ctx::kPairLanes, "the lane contexts are shared with sfm_extract_views");
-    rc = lane_contexts(ctx, nlanes, lanes);
-    if (rc != SFM_OK) return rc;
-    for (int l = 0; l < nlanes; ++l)
-        if (!ctx->lane_ev[l]) SFM_HIP_TRY(hipEventCreateWithFlags(&ctx->lane_ev[l], hipEventDisableTiming));
-    // ONE pooled Image_pair per lane at the largest size (the reference constructs one per pair: ~20 cudaMalloc / cudaFree each)
-    if (max_n >= 8) {
-        for (int l = 0; l < nlanes; ++l) {
-            sfm_ctx *c = lanes[l];
-            if (c->pool_pair && (c->pool_pair->cap_points < max_n || memcmp(c->pool_K, h_K, 36) != 0 || memcmp(c->pool_Kinv, h_Kinv, 36) != 0)) {
-                (void)sfm_pair_destroy(c->pool_pair);
-                c->pool_pair = nullptr;
-            }
-            if (!c->pool_pair) {
-                rc = sfm_pair_create(c, h_K, h_Kinv, 2, max_n, &c->pool_pair);
-                if (rc == SFM_OK) { c->pool_pair->holds_ctx_ref = false; c->refs--; }      // the context's own pair: destroyed WITH the context
-                if (rc != SFM_OK) return rc;
-                memcpy(c->pool_K, h_K, 36); memcpy(c->pool_Kinv, h_Kinv, 36);
-            }
-        }
-    }
-    rc = grow(&ctx->pool_records, &ctx->pool_records_cap, (size_t)owned * SFM_RECORD_FLOATS, ctx->stream);
-    if (rc != SFM_OK) return rc;
-    // the auxiliary streams start after everything already enqueued on the caller's stream (the features, typically)
-    if (nlanes > 1) {
-        SFM_HIP_TRY(hipEventRecord(ctx->lane_ev[0], ctx->stream));
-        for (int l = 1; l < nlanes; ++l) SFM_HIP_TRY(hipStreamWaitEvent(lanes[l]->stream, ctx->lane_ev[0], 0));
-    }
-    // ---- batched path (pairs_batch.hpp): the matcher stays one launch per pair (it fills the chip), everything after it is
-    // FIVE launches for all pairs of the call -- 630 pairs x 5 small launches are bound by the host's launch rate, not by
-    // the GPU.  Taken for the reference's own pipeline (SFM_POSE_REFERENCE, K^-1 with last row (0 0 1), up to 4096
-    // hypotheses per pair); anything else runs the per-pair loop below.  Results are bit-identical (same device functions on
-    // the same inputs: tests/test_gpu_dino.py::test_dino_ring_batched_equals_per_pair).
-    bool batched_done = false;
-    int slot = 0;
-    const bool unbatched_env = getenv("SFM_PAIRS_UNBATCHED") != nullptr;      // A/B and tests: read on EVERY call (sfm_ctx_last_pairs_batched says what ran)
-    bool batch = pose_mode == SFM_POSE_REFERENCE && unit_z_Kinv(h_Kinv) && owned >= 4 && !unbatched_env;
-    ctx->last_pairs_batched = 0;
-    uint32_t max_H = 0;
-    for (int i = first; i < num_pairs && batch; i += stride) {
-        if (!usable(pairs[i])) continue;
-        // already matched pairs (no second view given) read match_xpos / match_ypos of the records: not supported by the batch
-        // kernels -- such lists take the per-pair loop, decided HERE, before anything has been launched for them
-        if (!pairs[i].d_sift2) { batch = false; break; }
-        const uint32_t H = num_hypotheses ? num_hypotheses : (uint32_t)(pairs[i].n1 / 8);
-        if (H > 4096u || H < 1u) batch = false;
-        if (H > max_H) max_H = H;
-    }
-    // (host staging of the job arrays: declared here so that they outlive every asynchronous copy made from them)
-    std::vector<PairJob> jobs;
-    std::vector<std::vector<MatchJob>> keep_alive;
-    if (batch && max_H > 0) {
-        auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        std::vector<int> job_slot;
-        jobs.reserve((size_t)owned); job_slot.reserve((size_t)owned);
-        size_t bytes = 0;
-        int slot_b = 0, max_ld = 0, max_nn = 0;
-        for (int i = first; i < num_pairs; i += stride, ++slot_b) {
-            const sfm_pair_desc &d = pairs[i];
-            if (h_status) h_status[slot_b] = usable(d) ? SFM_OK : SFM_E_INVALID;
-            if (!usable(d)) continue;
-            PairJob j{};
-            j.s1 = d.d_sift1; j.s2 = d.d_sift2; j.n = d.n1; j.ld = round_up(d.n1, 128);
-            j.H = num_hypotheses ? num_hypotheses : (uint32_t)(d.n1 / 8);
-            sfm_ransac_params dp; sfm_ransac_default_params(&dp, d.n1);
-            j.seed = dp.seed; j.thr = dp.threshold;
-            // offsets first (pointers once the workspace is known)
-            size_t o = bytes;
-            j.m_idx = reinterpret_cast<const int *>(o);            o += up((size_t)j.n * 4);
-            j.X0 = reinterpret_cast<float *>(o);                   o += up((size_t)3 * j.ld * 4);
-            j.X1 = reinterpret_cast<float *>(o);                   o += up((size_t)3 * j.ld * 4);
-            j.counts = reinterpret_cast<int *>(o);                 o += up((size_t)j.H * 4);
-            j.Ecand = reinterpret_cast<float *>(o);                o += up((size_t)j.H * 36);
-            j.key = reinterpret_cast<unsigned long long *>(o);     o += 256;
-            j.mask = reinterpret_cast<uint8_t *>(o);               o += up((size_t)j.n);
-            j.points = reinterpret_cast<float *>(o);               o += up((size_t)4 * j.n * 4);
-            j.chosen = reinterpret_cast<float *>(o);               o += 256;
-            bytes = o;
-            j.record = ctx->pool_records + (size_t)slot_b * SFM_RECORD_FLOATS;
-            if (j.ld > max_ld) max_ld = j.ld;
-            if (j.n > max_nn) max_nn = j.n;
-            jobs.push_back(j); job_slot.push_back(slot_b);
-        }
-        const size_t jobs_bytes = up(jobs.size() * sizeof(PairJob));
-        rc = grow(&ctx->batch_ws, &ctx->batch_ws_bytes, bytes + jobs_bytes, ctx->stream);
-        if (rc != SFM_OK) return rc;
-        char *base = static_cast<char *>(ctx->batch_ws) + jobs_bytes;
-        for (PairJob &j : jobs) {
-            auto fix = [&](auto *&ptr) { ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(base + reinterpret_cast<size_t>(ptr)); };
-            fix(j.m_idx); fix(j.X0); fix(j.X1); fix(j.counts); fix(j.Ecand); fix(j.key); fix(j.mask); fix(j.points); fix(j.chosen);
-        }
-        PairJob *d_jobs = static_cast<PairJob *>(ctx->batch_ws);
-        SFM_HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(PairJob), hipMemcpyHostToDevice, ctx->stream));
-        if (nlanes > 1) {
-            SFM_HIP_TRY(hipEventRecord(ctx->lane_ev[0], ctx->stream));
-            for (int l = 1; l < nlanes; ++l) SFM_HIP_TRY(hipStreamWaitEvent(lanes[l]->stream, ctx->lane_ev[0], 0));
-        }
-        // MatchSiftData per pair: the SiftPoint fields of the first view as always (pairs that share their first view stay
-        // on one lane in list order: the fields end up as after the sequential loop) + the index array the batch reads
-        // Consecutive pairs that share their first view (the all-pairs list of configs[4] has 35, 34, ... of them in a row) go
-        // through ONE matcher launch (launch_match_jobs, grid.z = pair) unless the four-kernel pre-filter is what they would run.
-        std::vector<const void *> first_views;
-        const int ldf = (int)(sizeof(sfm_sift_point) / sizeof(float));
-        for (size_t k = 0; k < jobs.size() && rc == SFM_OK; ) {
-            PairJob &j = jobs[k];
-            if (!j.s2) { ++k; continue; }
-            sfm_ctx *c = lane_of_first_view(first_views, j.s1, lanes, nlanes);
-            const bool tail = (c->quirks & SFM_QUIRK_MATCH_TAIL) != 0;            // matching.cu:325 (as sfm_match)
-            size_t k1 = k;                                                        // the run [k, k1) of pairs with this first view
-            std::vector<MatchJob> mj;
-            int run_kernel = -1;                                                  // one kernel per launch: what match_pick says for the first pair
-            while (k1 < jobs.size() && jobs[k1].s1 == j.s1 && jobs[k1].s2 && jobs[k1].n == j.n) {
-                const sfm_pair_desc &d = pairs[first + job_slot[k1] * stride];
-                const int n2 = tail ? d.n2 - d.n2 % 32 : d.n2;
-                const int pick = n2 < 1 ? SFM_MATCH_PREFILTER : match_pick_jobs(c, j.n, n2);
-                if (pick == SFM_MATCH_PREFILTER || (run_kernel >= 0 && pick != run_kernel)) break;
-                run_kernel = pick;
-                MatchJob m{};
-                m.db = jobs[k1].s2->data; m.ndb = n2; m.lddb = ldf; m.sift2 = jobs[k1].s2;
-                m.sift1 = nullptr;                                                // the record fields: the LAST pair of the run writes them (below)
-                m.out_idx = const_cast<int *>(jobs[k1].m_idx);
-                mj.push_back(m);
-                ++k1;
-            }
-            if (mj.size() >= 2) {
-                mj.back().sift1 = const_cast<sfm_sift_point *>(j.s1);             // as after the sequential loop: the last match's fields
-                keep_alive.push_back(std::move(mj));
-                rc = launch_match_jobs(c, j.s1->data, j.n, ldf, keep_alive.back().data(), (int)keep_alive.back().size(), run_kernel);
-                if (rc == SFM_OK && (c->quirks & SFM_QUIRK_MATCH_AMBIGUITY)) {     // the record fields are the LAST match's: so is the reference's ambiguity
-                    const MatchJob &last = keep_alive.back().back();
-                    rc = launch_match_ambiguity_quirk(c, j.s1->data, j.n, ldf, last.db, last.ndb, ldf, const_cast<sfm_sift_point *>(j.s1), nullptr);
-                }
-                k = k1;
-                continue;
-            }
-            const sfm_pair_desc &d = pairs[first + job_slot[k] * stride];
-            int n2 = d.n2;
-            sfm_sift_point *s1w = const_cast<sfm_sift_point *>(j.s1);
-            if (tail) n2 -= n2 % 32;
-            if (n2 == 0) {
-                rc = launch_match_none(c, j.n, s1w);
-                if (rc == SFM_OK) {                                               // index -1 everywhere (no early return: the lanes are joined below)
-                    const hipError_t em = hipMemsetAsync(const_cast<int *>(j.m_idx), 0xFF, (size_t)j.n * 4, c->stream);
-                    if (em != hipSuccess) { set_error("hipMemsetAsync failed: %s", hipGetErrorString(em)); rc = SFM_E_HIP; }
-                }
-            } else {
-                rc = launch_match(c, j.s1->data, j.n, ldf, j.s2->data, n2, ldf, nullptr, nullptr, const_cast<int *>(j.m_idx), s1w, j.s2);
-                if (rc == SFM_OK && (c->quirks & SFM_QUIRK_MATCH_AMBIGUITY)) rc = launch_match_ambiguity_quirk(c, j.s1->data, j.n, ldf, j.s2->data, n2, ldf, s1w, nullptr);
-            }
-            ++k;
-        }
-        join_lanes(ctx, lanes, nlanes, &rc);
-        if (rc != SFM_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        {
-            // the rest of the chain for ALL pairs of the call: fill_xu_pairs | ransac_pairs_solve + ransac_fused_pairs |
-            // choose_pose_pairs + triangulate_pairs -- five launches
-            rc = launch_fill_xu_pairs(ctx, d_jobs, (int)jobs.size(), max_ld, h_Kinv);
-            // eight blocks of eight wavefronts per pair: each stages the pair's points once and runs its share of the batches
-            const int bpp = (int)std::min<uint32_t>(8u, (max_H + 7u) / 8u);
-            if (rc == SFM_OK) rc = launch_fused_pairs(ctx, d_jobs, (int)jobs.size(), bpp, max_H);
-            if (rc == SFM_OK) rc = launch_finalize_pose_pairs(ctx, d_jobs, (int)jobs.size(), max_nn);
-            if (rc != SFM_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-            batched_done = true;
-            ctx->last_pairs_batched = 1;
-        }
-    }
-    if (!batched_done) {
-    // per pair: MatchSiftData (optional) -> fillXU -> estimateE -> pose candidates -> choosePose -> linear triangulation
-    // (src/main.cpp:282-307), everything enqueued back to back, no host synchronisation, the record stays on the device
-    std::vector<const void *> first_views;
-    slot = 0;
-    for (int i = first; i < num_pairs; i += stride, ++slot) {
-        const sfm_pair_desc &d = pairs[i];
-        if (h_status) h_status[slot] = usable(d) ? SFM_OK : SFM_E_INVALID;
-        if (!usable(d)) continue;
-        sfm_ctx *c = lane_of_first_view(first_views, d.d_sift1, lanes, nlanes);
-        sfm_pair *ip = c->pool_pair;
-        if (d.d_sift2) { rc = sfm_match(c, d.d_sift1, d.n1, d.d_sift2, d.n2); if (rc != SFM_OK) break; }
-        rc = sfm_pair_reset(ip, d.n1);                                  if (rc != SFM_OK) break;
-        rc = sfm_fill_xu(ip, d.d_sift1);                                if (rc != SFM_OK) break;
-        sfm_ransac_params p;
-        sfm_ransac_default_params(&p, d.n1);
-        if (num_hypotheses) p.num_hypotheses = num_hypotheses;
-        rc = sfm_estimate_E(ip, &p);                                    if (rc != SFM_OK) break;
-        // poses, triangulation and the record: one launch in SFM_POSE_REFERENCE (sfm_pose_chain), four otherwise
-        rc = pose_chain(ip, pose_mode, ctx->pool_records + (size_t)slot * SFM_RECORD_FLOATS);
-        if (rc != SFM_OK) break;
-    }
-    // join the lanes -- also when an enqueue failed: what the lanes already hold must not outlive this call's view of the buffers
-    join_lanes(ctx, lanes, nlanes, &rc);
-    if (rc != SFM_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    }
-    // ONE read-back for all pairs of this rank
-    std::vector<float> rec((size_t)owned * SFM_RECORD_FLOATS);
-    SFM_HIP_TRY(hipMemcpyAsync(rec.data(), ctx->pool_records, rec.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    SFM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    slot = 0;
-    int worst = SFM_OK;
-    for (int i = first; i < num_pairs; i += stride, ++slot) {
-        float *out = h_records + (size_t)slot * 28;
-        if (!usable(pairs[i])) { for (int k = 0; k < 28; ++k) out[k] = -1.0f; continue; }
-        memcpy(out, rec.data() + (size_t)slot * SFM_RECORD_FLOATS, 28 * sizeof(float));
-        if (rec[(size_t)slot * SFM_RECORD_FLOATS + 28] != 0.0f) {
-            if (h_status) h_status[slot] = SFM_E_SINGULAR;
-            set_error("pair %d: chosen pose candidate is singular", i);
-            worst = SFM_E_SINGULAR;
-        }
-    }
-    return h_status ? SFM_OK : worst;
-}
-
-int sfm_ctx_last_pairs_batched(sfm_ctx *ctx, int *batched)
-{
-    SFM_REQUIRE(ctx && batched, SFM_E_INVALID, "null argument");
-    *batched = ctx->last_pairs_batched;
-    return SFM_OK;
 }
 
 int sfm_ransac_last_clock(sfm_pair *pair, double *shader_mhz)

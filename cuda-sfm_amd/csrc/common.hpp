@@ -66,14 +66,19 @@ inline int grow(T **buf, N *have, size_t need, hipStream_t st)
     return SFM_OK;
 }
 
+// the last row of K^-1 is (0 0 1): every normalised z is exactly 1
+inline bool unit_z_Kinv(const float h_Kinv[9]) { return h_Kinv[6] == 0.0f && h_Kinv[7] == 0.0f && h_Kinv[8] == 1.0f; }
+
 // Consecutive arrays carved out of one device buffer.  A buffer's layout is ONE function that takes its arrays from a Carver
 // and returns used: run over the buffer it yields the pointers, run over a null base the size to allocate.
 struct Carver {
     uintptr_t base;
     size_t used = 0;
     explicit Carver(void *buffer) : base(reinterpret_cast<uintptr_t>(buffer)) {}
-    template <typename T> T *take(size_t count)
+    // the array starts at the next multiple of `align` bytes (a power of two) from the base
+    template <typename T> T *take(size_t count, size_t align = 1)
     {
+        used = (used + align - 1) & ~(align - 1);
         T *p = reinterpret_cast<T *>(base + used);
         used += count * sizeof(T);
         return p;
@@ -245,6 +250,16 @@ struct sfm_pair {
 };
 
 namespace sfm {
+
+// abi.hip
+int match_db_rows(const sfm_ctx *ctx, int n2);                    // rows of the second view MatchSiftData visits (SFM_QUIRK_MATCH_TAIL)
+// MatchSiftData on SiftPoint records: the first view's match fields, + the index of the best match per point when out_idx is given
+int match_records(sfm_ctx *ctx, sfm_sift_point *d_sift1, int n1, const sfm_sift_point *d_sift2, int n2, int *out_idx);
+int pose_chain(sfm_pair *pair, int mode, float *d_record);        // sfm_pose_chain + the pair's record on the device
+
+// pairs.hip: the caller's context + auxiliary contexts with streams of their own (sfm_extract_views, sfm_process_pairs)
+int lane_contexts(sfm_ctx *ctx, int n, sfm_ctx **out);
+int start_lanes_after(sfm_ctx *ctx, sfm_ctx *const *lanes, int n, hipEvent_t event);
 
 // ransac.hip
 int launch_ransac_score(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0, uint32_t count, unsigned long long *key2 = nullptr,
