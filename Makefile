@@ -28,11 +28,12 @@ HDEMO    := $(PKG)/host/homography_demo
 SDEMO    := $(PKG)/host/sift_demo
 MAINAPP  := $(PKG)/host/sfm_main
 RPDEMO   := $(PKG)/host/refine_pairs_demo
+RVDEMO   := $(PKG)/host/register_views_demo
 
 IOTEST   := tests/cpp/io_test
 GEOMTEST := tests/cpp/geom_test
 
-all: $(LIB) $(LIB_AB) $(COMMLIB) $(BUILD)/ransac.s oracle hostcheck fakeccl $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(IOTEST) $(GEOMTEST)
+all: $(LIB) $(LIB_AB) $(COMMLIB) $(BUILD)/ransac.s oracle hostcheck fakeccl $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(IOTEST) $(GEOMTEST)
 
 # the product's objects come with the compiler's resource-usage report (registers, scratch, LDS of every kernel) next to them:
 # $(BUILD)/<source>.usage.txt, read by tests/test_register_budget.py; warnings and errors of the compile are still shown
@@ -94,6 +95,9 @@ $(MAINAPP): $(PKG)/host/sfm_main.cpp $(PKG)/host/cudaImage.h $(PKG)/host/sfm.h $
 $(RPDEMO): $(PKG)/host/refine_pairs_demo.cpp $(PKG)/host/sfm.h $(PKG)/host/sfm_io.h $(PKG)/host/cudaSift.h include/sfm_amd.h $(LIB)
 	g++ -O2 -std=c++14 -Wall -o $@ $< -L$(PKG)/lib -lsfm_amd -Wl,-rpath,'$$ORIGIN/../lib' -Wl,-rpath,/opt/rocm/lib
 
+$(RVDEMO): $(PKG)/host/register_views_demo.cpp $(PKG)/host/sfm.h $(PKG)/host/sfm_io.h $(PKG)/host/cudaSift.h include/sfm_amd.h $(LIB)
+	g++ -O2 -std=c++14 -Wall -o $@ $< -L$(PKG)/lib -lsfm_amd -Wl,-rpath,'$$ORIGIN/../lib' -Wl,-rpath,/opt/rocm/lib
+
 $(IOTEST): tests/cpp/io_test.cpp $(PKG)/host/sfm_io.h $(PKG)/host/cudaSift.h include/sfm_amd.h
 	g++ -O2 -std=c++14 -Wall -o $@ $<
 
@@ -138,7 +142,7 @@ tests/hostcheck/libpairstatecheck.so: tests/hostcheck/pairstatecheck.cpp $(CSRC)
 	g++ -O2 -std=c++17 -Wall -fPIC -shared -o $@ $<
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
+	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all ab oracle hostcheck fakeccl clean

@@ -74,7 +74,7 @@ EXPORTS = [
     "sfm_ransac_last_launch", "sfm_ransac_last_clock", "sfm_ransac_last_prefilter_rule", "sfm_process_pairs", "sfm_ctx_last_pairs_batched", "sfm_extract_views", "sfm_extract_views_u8",
     "sfm_refine_default_params", "sfm_refine_two_view", "sfm_refine_pairs", "sfm_get_refine_report", "sfm_get_refined_pose", "sfm_get_refined_points",
     "sfm_get_reprojection_errors",
-    "sfm_register_default_params", "sfm_register_view", "sfm_get_register_report", "sfm_get_view_pose", "sfm_get_view_errors",
+    "sfm_register_default_params", "sfm_register_view", "sfm_register_views", "sfm_get_register_report", "sfm_get_view_pose", "sfm_get_view_errors",
     "sfm_get_view_counts",
 ]
 AB_EXPORTS = ["sfm_ransac_last_phases", "sfm_ransac_last_trace", "sfm_prefilter_probe", "sfm_prefilter_band_probe"]      # include/sfm_amd_ab.h
@@ -195,6 +195,7 @@ _lib.sfm_get_reprojection_errors.argtypes = [_vp, _vp, _vp]
 _lib.sfm_register_default_params.argtypes = [C.POINTER(RegisterParams)]
 _lib.sfm_register_default_params.restype = None
 _lib.sfm_register_view.argtypes = [_vp, _vp, C.POINTER(RegisterParams)]
+_lib.sfm_register_views.argtypes = [C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.POINTER(RegisterParams), C.POINTER(_vp), C.POINTER(_vp)]
 _lib.sfm_get_register_report.argtypes = [_vp, C.POINTER(RegisterReport)]
 _lib.sfm_get_view_pose.argtypes = [_vp, _vp, _vp]
 _lib.sfm_get_view_errors.argtypes = [_vp, _vp, _vp]
@@ -299,6 +300,34 @@ def register_params(**kw):
         else:
             setattr(p, k, v)
     return p
+
+
+def register_views_enqueue(pairs, d_sifts, params, points=None, valid=None):
+    """sfm_register_views (enqueue only): a view registered to every ImagePair of the list (one Context, none twice) in four
+    launches, each pair left exactly as its own register_enqueue leaves it.  d_sifts: one entry per pair (view 1's records
+    re-matched against that pair's new view; device tensor / pointer); points / valid: None, or one entry per pair (device
+    tensor / pointer; None = that pair's refined points and used flags); params.d_points / d_valid must stay unset."""
+    n = len(pairs)
+    assert len(d_sifts) == n, "one record pointer per pair"
+    handles = (_vp * n)(*[p._h.value for p in pairs])
+    sifts = (_vp * n)(*[_ptr(d) for d in d_sifts])
+    lists = []
+    for name, entries in (("points", points), ("valid", valid)):
+        if entries is None:
+            lists.append(None)
+            continue
+        assert len(entries) == n, f"one {name} entry per pair"
+        lists.append((_vp * n)(*[_ptr(e) for e in entries]))
+    _check(_lib.sfm_register_views(handles, n, sifts, C.byref(params), lists[0], lists[1]), "sfm_register_views")
+
+
+def register_views(pairs, d_sifts, points=None, valid=None, **kw):
+    """ImagePair.register_view for a list of pairs in one batched call; kw are RegisterParams fields, the same for every pair.
+    Returns the list of report dicts: one wait for the device, then a small copy per pair."""
+    register_views_enqueue(pairs, d_sifts, register_params(**kw), points, valid)
+    if pairs:
+        pairs[0].ctx.synchronize()
+    return [p.get_register_report() for p in pairs]
 
 
 def sift_temp_layout(width, height, num_octaves=5, scale_up=False):

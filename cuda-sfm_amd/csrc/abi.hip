@@ -217,7 +217,8 @@ static int ctx_destroy_now(sfm_ctx *ctx)
     if (ctx->views_image) (void)hipFree(ctx->views_image);
     if (ctx->views_ev) (void)hipEventDestroy(ctx->views_ev);
     sift_job_free(ctx);
-    refine_jobs_free(ctx);
+    job_array_free(ctx->refine_jobs);
+    job_array_free(ctx->register_jobs);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     for (auto &t : ctx->tev) for (hipEvent_t e : t) if (e) (void)hipEventDestroy(e);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -930,36 +931,96 @@ void sfm_register_default_params(sfm_register_params *p)
     p->initial_lambda = 1e-3f;
 }
 
-int sfm_register_view(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_register_params *p)
+// the parameter checks of sfm_register_view and sfm_register_views (none needs a device)
+static int check_register_params(const sfm_register_params &p)
 {
-    SFM_REQUIRE(pair && d_sift && p, SFM_E_INVALID, "null argument");
-    SFM_FLUSH(pair);
-    int rc = check_lm_params(*p, "sfm_register_params");
+    const int rc = check_lm_params(p, "sfm_register_params");
     if (rc != SFM_OK) return rc;
-    SFM_REQUIRE(p->num_hypotheses >= 1 && p->num_hypotheses <= (1u << 20), SFM_E_INVALID, "num_hypotheses %u outside 1..2^20", p->num_hypotheses);
-    SFM_REQUIRE(isfinite(p->threshold_px) && p->threshold_px > 0.0f, SFM_E_INVALID, "threshold_px must be finite and > 0");
-    SFM_REQUIRE(isfinite(p->min_score) && isfinite(p->max_ambiguity), SFM_E_INVALID, "min_score / max_ambiguity must be finite");
-    SFM_REQUIRE(p->d_points || !p->d_valid, SFM_E_INVALID, "d_valid needs d_points");
-    SFM_NEED(pair, p->d_points ? kPoints : kPoints | kRefined);       // without d_points: the refined points, on the current points
-    SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
+    SFM_REQUIRE(p.num_hypotheses >= 1 && p.num_hypotheses <= (1u << 20), SFM_E_INVALID, "num_hypotheses %u outside 1..2^20", p.num_hypotheses);
+    SFM_REQUIRE(isfinite(p.threshold_px) && p.threshold_px > 0.0f, SFM_E_INVALID, "threshold_px must be finite and > 0");
+    SFM_REQUIRE(isfinite(p.min_score) && isfinite(p.max_ambiguity), SFM_E_INVALID, "min_score / max_ambiguity must be finite");
+    return SFM_OK;
+}
+
+// the registration's per-pair buffers: the per-point ones allocated at the first call, the per-hypothesis ones grown on demand
+static int register_buffers(sfm_pair *pair, uint32_t num_hypotheses)
+{
+    int rc = SFM_OK;
     if (!pair->d_vstate) {                              // sized to the creation-time count: sfm_pair_reset needs no reallocation
         rc = alloc_group({ { reinterpret_cast<void **>(&pair->d_vstate), (size_t)register_state_words() * 4 },
                            { reinterpret_cast<void **>(&pair->d_vreproj), reproj_bytes((size_t)pair->cap_points) },
                            { &pair->d_vwork, register_work_bytes(pair->cap_points) } });
         if (rc != SFM_OK) return rc;
     }
-    if (p->num_hypotheses > pair->cap_vhyps) {          // grows with the largest num_hypotheses seen (the old buffers may be in use)
+    if (num_hypotheses > pair->cap_vhyps) {             // grows with the largest num_hypotheses seen (the old buffers may be in use)
         pair->state.view_dropped();
         pair->cap_vhyps = 0;                            // ... until BOTH buffers exist again (d_vhyp has no size of its own)
         size_t hyp_bytes = 0;
-        rc = grow(&pair->d_vhyp, &hyp_bytes, register_hyp_bytes(p->num_hypotheses), pair->ctx->stream);
-        if (rc == SFM_OK) rc = grow(&pair->d_vcounts, &pair->cap_vhyps, p->num_hypotheses, pair->ctx->stream);
-        if (rc != SFM_OK) return rc;
+        rc = grow(&pair->d_vhyp, &hyp_bytes, register_hyp_bytes(num_hypotheses), pair->ctx->stream);
+        if (rc == SFM_OK) rc = grow(&pair->d_vcounts, &pair->cap_vhyps, num_hypotheses, pair->ctx->stream);
     }
+    return rc;
+}
+
+int sfm_register_view(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_register_params *p)
+{
+    SFM_REQUIRE(pair && d_sift && p, SFM_E_INVALID, "null argument");
+    SFM_FLUSH(pair);
+    int rc = check_register_params(*p);
+    if (rc != SFM_OK) return rc;
+    SFM_REQUIRE(p->d_points || !p->d_valid, SFM_E_INVALID, "d_valid needs d_points");
+    SFM_NEED(pair, p->d_points ? kPoints : kPoints | kRefined);       // without d_points: the refined points, on the current points
+    SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
+    rc = register_buffers(pair, p->num_hypotheses);
+    if (rc != SFM_OK) return rc;
     const float *d_points = p->d_points ? p->d_points : pair->d_rpoints;
     const uint8_t *d_valid = p->d_points ? p->d_valid : reproj_flags(pair, pair->d_rreproj);   // the used flags
     rc = launch_register(pair, d_sift, *p, d_points, d_valid);
     if (rc == SFM_OK) { pair->state.view_registered(); pair->view_hyps = p->num_hypotheses; }
+    return rc;
+}
+
+int sfm_register_views(sfm_pair *const *pairs, int num_pairs, const sfm_sift_point *const *d_sifts, const sfm_register_params *p,
+                       const float *const *d_points, const uint8_t *const *d_valid)
+{
+    // the checks that need no device first, all of them before anything is enqueued or any pair changes
+    SFM_REQUIRE(p, SFM_E_INVALID, "null params");
+    SFM_REQUIRE(num_pairs >= 0 && num_pairs <= 65535, SFM_E_INVALID, "num_pairs %d outside 0..65535", num_pairs);
+    SFM_REQUIRE(!p->d_points && !p->d_valid, SFM_E_INVALID,
+                "sfm_register_params.d_points / d_valid must be null here: per-pair points go through d_points / d_valid");
+    int rc = check_register_params(*p);
+    if (rc != SFM_OK) return rc;
+    if (num_pairs == 0) return SFM_OK;
+    SFM_REQUIRE(pairs && d_sifts, SFM_E_INVALID, "null pair list or null d_sifts list");
+    for (int i = 0; i < num_pairs; ++i) {
+        SFM_REQUIRE(pairs[i], SFM_E_INVALID, "pairs[%d] is null", i);
+        SFM_REQUIRE(d_sifts[i], SFM_E_INVALID, "d_sifts[%d] is null", i);
+        SFM_REQUIRE(!(d_valid && d_valid[i]) || (d_points && d_points[i]), SFM_E_INVALID, "d_valid[%d] needs d_points[%d]", i, i);
+    }
+    sfm_ctx *ctx = pairs[0]->ctx;
+    for (int i = 1; i < num_pairs; ++i) SFM_REQUIRE(pairs[i]->ctx == ctx, SFM_E_INVALID, "pairs[%d] belongs to another context than pairs[0]", i);
+    {
+        std::vector<const sfm_pair *> sorted(pairs, pairs + num_pairs);
+        std::sort(sorted.begin(), sorted.end(), std::less<const sfm_pair *>());
+        SFM_REQUIRE(std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end(), SFM_E_INVALID,
+                    "a pair is listed twice (a pair holds one registered view)");
+    }
+    for (int i = 0; i < num_pairs; ++i) SFM_FLUSH(pairs[i]);
+    for (int i = 0; i < num_pairs; ++i) {
+        const uint32_t need = (d_points && d_points[i]) ? kPoints : kPoints | kRefined;      // without points: the refined ones, on the current points
+        SFM_REQUIRE(pairs[i]->state.has(need), SFM_E_STATE, "pairs[%d]: %s", i, pair_stage_hint(pairs[i]->state.missing(need)));
+    }
+    SFM_HIP_TRY(hipSetDevice(ctx->device));
+    for (int i = 0; i < num_pairs; ++i) { rc = register_buffers(pairs[i], p->num_hypotheses); if (rc != SFM_OK) return rc; }
+    std::vector<const float *> points((size_t)num_pairs);
+    std::vector<const uint8_t *> valid((size_t)num_pairs);
+    for (int i = 0; i < num_pairs; ++i) {
+        const bool given = d_points && d_points[i];
+        points[(size_t)i] = given ? d_points[i] : pairs[i]->d_rpoints;
+        valid[(size_t)i] = given ? (d_valid ? d_valid[i] : nullptr) : reproj_flags(pairs[i], pairs[i]->d_rreproj);   // the used flags
+    }
+    rc = launch_register_views(ctx, pairs, num_pairs, d_sifts, *p, points.data(), valid.data());
+    for (int i = 0; i < num_pairs; ++i) if (rc == SFM_OK) { pairs[i]->state.view_registered(); pairs[i]->view_hyps = p->num_hypotheses; }
     return rc;
 }
 

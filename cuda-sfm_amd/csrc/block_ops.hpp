@@ -9,6 +9,18 @@ namespace sfm {
 // vector registers.
 __device__ __forceinline__ float uniform(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
 
+// A pointer read from memory (a field of a job struct, many pairs per launch) is a generic one, and the bodies would go through
+// flat loads and stores; a kernel argument is known to be global.  Cast to the global address space and back -- with an empty asm
+// in between that keeps the optimiser from folding the two casts away (and the value in scalar registers) -- a job's pointer is a
+// global one for every access that follows.
+template <typename T>
+__device__ __forceinline__ T *global_ptr(T *p)
+{
+    auto g = (__attribute__((address_space(1))) T *)p;
+    asm("" : "+s"(g));
+    return (T *)g;
+}
+
 // Maximum over the wavefront, in every lane: folds packed arg-max keys (pack_key: count << 32 | ~id, so the first maximum wins).
 __device__ __forceinline__ unsigned long long wave_max(unsigned long long k)
 {

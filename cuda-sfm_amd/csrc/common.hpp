@@ -85,6 +85,50 @@ struct Carver {
     }
 };
 
+// The job array of a many-pairs call (sfm_refine_pairs: RefineArgs, sfm_register_views: RegisterArgs): a context-owned device
+// array + pinned staging, grown on demand, and the event that sits behind the upload.  One mechanism, parameterised by the
+// element size.
+struct JobArray {
+    void *dev = nullptr, *pinned = nullptr;
+    size_t cap = 0;                    // jobs
+    hipEvent_t ev = nullptr;
+};
+
+// Room for `count` jobs of `elem` bytes (growth is rare: the stream is drained before the old device buffer goes).  The staging
+// buffer is rewritten by the host: the upload of the call before must have left it -- the only host wait of a batched call.
+inline int job_array_reserve(JobArray &j, size_t count, size_t elem, hipStream_t st)
+{
+    if (!j.ev) SFM_HIP_TRY(hipEventCreateWithFlags(&j.ev, hipEventDisableTiming));
+    SFM_HIP_TRY(hipEventSynchronize(j.ev));                            // (an event never recorded is complete)
+    if (count <= j.cap) return SFM_OK;
+    const size_t want = count > 2 * j.cap ? count : 2 * j.cap;
+    if (j.pinned) (void)hipHostFree(j.pinned);
+    j.pinned = nullptr;
+    j.cap = 0;                                                         // the size counts for both: it is set when both exist
+    SFM_HIP_TRY(hipHostMalloc(&j.pinned, want * elem, hipHostMallocDefault));
+    size_t have = 0;
+    const int rc = grow(&j.dev, &have, want * elem, st);
+    if (rc != SFM_OK) return rc;
+    j.cap = want;
+    return SFM_OK;
+}
+
+// the staged jobs to the device: ONE copy, the event behind it
+inline int job_array_upload(JobArray &j, size_t count, size_t elem, hipStream_t st)
+{
+    SFM_HIP_TRY(hipMemcpyAsync(j.dev, j.pinned, count * elem, hipMemcpyHostToDevice, st));
+    SFM_HIP_TRY(hipEventRecord(j.ev, st));
+    return SFM_OK;
+}
+
+inline void job_array_free(JobArray &j)
+{
+    if (j.pinned) (void)hipHostFree(j.pinned);
+    if (j.dev) (void)hipFree(j.dev);
+    if (j.ev) (void)hipEventDestroy(j.ev);
+    j = JobArray();
+}
+
 } // namespace sfm
 
 struct sfm_ctx {
@@ -143,10 +187,8 @@ struct sfm_ctx {
     size_t pool_records_cap = 0;       // floats
     void *batch_ws = nullptr;          // sfm_process_pairs, batched path: the PairJob array + every pair's buffers (pairs_batch.hpp)
     size_t batch_ws_bytes = 0;
-    // sfm_refine_pairs: the RefineArgs of a call (refine.hip), device array + pinned staging; the event sits behind the upload
-    void *refine_jobs = nullptr, *refine_jobs_pinned = nullptr;
-    size_t refine_jobs_cap = 0;        // jobs
-    hipEvent_t refine_jobs_ev = nullptr;
+    // sfm_refine_pairs / sfm_register_views: the RefineArgs (refine.hip) / RegisterArgs (register.hip) of a call
+    sfm::JobArray refine_jobs, register_jobs;
     void *sift_job = nullptr;          // the extraction in flight (sift.hip: SiftJob), sfm_extract_sift_begin .. _end
     // kernels that already opted in to > 64 KiB of dynamic LDS on THIS context's device (function attributes are
     // per device; a context is used by one host thread at a time, so no process-wide flag)
@@ -301,7 +343,6 @@ int launch_pose_chain(sfm_pair *pair, float *d_record);          // REFERENCE mo
 int launch_refine(sfm_pair *pair, const sfm_refine_params &p);   // start (grid), LM solve (one block), finish (grid)
 // the same three stages for many pairs of one context in three launches (grid = pairs); d_masks: null, or one entry per pair (null = its own)
 int launch_refine_pairs(sfm_ctx *ctx, sfm_pair *const *pairs, int num_pairs, const sfm_refine_params &p, const uint8_t *const *d_masks);
-void refine_jobs_free(sfm_ctx *ctx);                              // the context's job array, staging buffer and event
 size_t refine_work_bytes(int cap_points);                         // bytes of pair->d_rwork
 int refine_state_words();                                         // floats of pair->d_rstate
 int refine_pose_offset();                                         // refined P + E inside d_rstate
@@ -309,6 +350,9 @@ int refine_report_offset();                                       // sfm_refine_
 
 // register.hip
 int launch_register(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_register_params &p, const float *d_points, const uint8_t *d_valid);
+// the same four stages for many pairs of one context in four launches (grid = pairs); one entry of d_sifts / d_points / d_valid per pair
+int launch_register_views(sfm_ctx *ctx, sfm_pair *const *pairs, int num_pairs, const sfm_sift_point *const *d_sifts, const sfm_register_params &p,
+                          const float *const *d_points, const uint8_t *const *d_valid);
 size_t register_work_bytes(int cap_points);                       // bytes of pair->d_vwork
 size_t register_hyp_bytes(size_t num_hypotheses);                 // bytes of pair->d_vhyp
 int register_state_words();                                       // floats of pair->d_vstate

@@ -359,18 +359,7 @@ __global__ __launch_bounds__(kFinishPoints)
 void refine_finish_kernel(RefineArgs a) { refine_finish_block(a, blockIdx.x); }
 
 // ---- many pairs: job blockIdx.y (start, finish) / blockIdx.x (solve) of `jobs` ----
-// A pointer read from memory is a generic one, and the bodies would go through flat loads and stores; a kernel argument is known
-// to be global.  Cast to the global address space and back -- with an empty asm in between that keeps the optimiser from folding
-// the two casts away (and the value in scalar registers) -- a job's pointer is a global one for every access that follows.
-template <typename T>
-__device__ __forceinline__ T *global_ptr(T *p)
-{
-    auto g = (__attribute__((address_space(1))) T *)p;
-    asm("" : "+s"(g));
-    return (T *)g;
-}
-
-// the block's job, through a uniform address (scalar loads), every pointer marked global
+// the block's job, through a uniform address (scalar loads), every pointer marked global (global_ptr, block_ops.hpp)
 __device__ __forceinline__ RefineArgs load_job(const RefineArgs *__restrict__ jobs, const unsigned int job)
 {
     RefineArgs a = jobs[job];
@@ -445,43 +434,25 @@ int launch_refine(sfm_pair *pair, const sfm_refine_params &p)
     return SFM_OK;
 }
 
-// The context's job array for `count` jobs: device buffer + pinned staging, grown on demand (rare: the stream is drained before
-// the old device buffer goes).  The staging buffer is rewritten by the host: the upload of the call before must have left it.
-static int refine_jobs_buffers(sfm_ctx *ctx, size_t count)
-{
-    if (!ctx->refine_jobs_ev) SFM_HIP_TRY(hipEventCreateWithFlags(&ctx->refine_jobs_ev, hipEventDisableTiming));
-    SFM_HIP_TRY(hipEventSynchronize(ctx->refine_jobs_ev));             // (an event never recorded is complete)
-    if (count <= ctx->refine_jobs_cap) return SFM_OK;
-    const size_t want = count > 2 * ctx->refine_jobs_cap ? count : 2 * ctx->refine_jobs_cap;
-    if (ctx->refine_jobs_pinned) (void)hipHostFree(ctx->refine_jobs_pinned);
-    ctx->refine_jobs_pinned = nullptr;
-    ctx->refine_jobs_cap = 0;                                          // the size counts for both: it is set when both exist
-    SFM_HIP_TRY(hipHostMalloc(&ctx->refine_jobs_pinned, want * sizeof(RefineArgs), hipHostMallocDefault));
-    size_t have = 0;
-    const int rc = grow(&ctx->refine_jobs, &have, want * sizeof(RefineArgs), ctx->stream);
-    if (rc != SFM_OK) return rc;
-    ctx->refine_jobs_cap = want;
-    return SFM_OK;
-}
-
 int launch_refine_pairs(sfm_ctx *ctx, sfm_pair *const *pairs, int num_pairs, const sfm_refine_params &p, const uint8_t *const *d_masks)
 {
-    int rc = refine_jobs_buffers(ctx, (size_t)num_pairs);
+    hipStream_t st = ctx->stream;
+    JobArray &ja = ctx->refine_jobs;
+    int rc = job_array_reserve(ja, (size_t)num_pairs, sizeof(RefineArgs), st);
     if (rc != SFM_OK) return rc;
     // long chains first: the solve blocks are dispatched in job order.  Stable, so equal sizes keep the caller's order; a pair's
     // result does not depend on its place (every block works on its own pair's buffers).
     std::vector<int> order((size_t)num_pairs);
     for (int i = 0; i < num_pairs; ++i) order[(size_t)i] = i;
     std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return pairs[x]->n > pairs[y]->n; });
-    RefineArgs *h_jobs = static_cast<RefineArgs *>(ctx->refine_jobs_pinned);
+    RefineArgs *h_jobs = static_cast<RefineArgs *>(ja.pinned);
     for (int k = 0; k < num_pairs; ++k) {
         const int i = order[(size_t)k];
         refine_args(pairs[i], p, d_masks ? d_masks[i] : nullptr, h_jobs[k]);
     }
-    const RefineArgs *d_jobs = static_cast<const RefineArgs *>(ctx->refine_jobs);
-    hipStream_t st = ctx->stream;
-    SFM_HIP_TRY(hipMemcpyAsync(ctx->refine_jobs, h_jobs, (size_t)num_pairs * sizeof(RefineArgs), hipMemcpyHostToDevice, st));
-    SFM_HIP_TRY(hipEventRecord(ctx->refine_jobs_ev, st));
+    const RefineArgs *d_jobs = static_cast<const RefineArgs *>(ja.dev);
+    rc = job_array_upload(ja, (size_t)num_pairs, sizeof(RefineArgs), st);
+    if (rc != SFM_OK) return rc;
     const int nmax = h_jobs[0].n;
     hipLaunchKernelGGL(refine_start_pairs_kernel, dim3((nmax + kStartPoints - 1) / kStartPoints, num_pairs), dim3(256), 0, st, d_jobs);
     SFM_HIP_TRY(hipGetLastError());
@@ -490,14 +461,6 @@ int launch_refine_pairs(sfm_ctx *ctx, sfm_pair *const *pairs, int num_pairs, con
     hipLaunchKernelGGL(refine_finish_pairs_kernel, dim3((nmax + kFinishPoints - 1) / kFinishPoints, num_pairs), dim3(kFinishPoints), 0, st, d_jobs);
     SFM_HIP_TRY(hipGetLastError());
     return SFM_OK;
-}
-
-void refine_jobs_free(sfm_ctx *ctx)
-{
-    if (ctx->refine_jobs_pinned) (void)hipHostFree(ctx->refine_jobs_pinned);
-    if (ctx->refine_jobs) (void)hipFree(ctx->refine_jobs);
-    if (ctx->refine_jobs_ev) (void)hipEventDestroy(ctx->refine_jobs_ev);
-    ctx->refine_jobs_pinned = nullptr; ctx->refine_jobs = nullptr; ctx->refine_jobs_ev = nullptr; ctx->refine_jobs_cap = 0;
 }
 
 size_t refine_work_bytes(int cap_points)

@@ -21,10 +21,16 @@
 //                           stop rules are LmControl's, refine_math.hpp, as in refine.hip), then every point's error and
 //                           final flag and the report.  The candidate set of a view is at most the pair's points (thousands): one block
 //                           runs an iteration in a few microseconds, less than a grid launch per iteration would cost.
+//
+// Many views in one call (launch_register_views): the same four bodies over an array of RegisterArgs in device memory, one per
+// pair -- gate and LM chain one block per job, solve grid (hypothesis blocks, jobs), scoring grid (hypothesis blocks, shares, jobs)
+// with ONE share count for the launch.  Every block works on its own pair's buffers: a pair ends bit for bit as its single call.
 #include "common.hpp"
 #include "device_math.hpp"
 #include "block_ops.hpp"
 #include "register_math.hpp"
+#include <algorithm>
+#include <vector>
 
 namespace sfm {
 
@@ -73,8 +79,7 @@ __device__ __forceinline__ bool register_gate(const RegisterArgs &a, int j)
     return isfinite(X) && isfinite(Y) && isfinite(Z) && isfinite(W) && W != 0.0f && Z / W > 0.0f;
 }
 
-__global__ __launch_bounds__(kRegGateThreads)
-void register_gate_kernel(RegisterArgs a)
+__device__ __forceinline__ void register_gate_block(const RegisterArgs &a)
 {
     __shared__ int wsum[kRegGateThreads / 64 + 1];
     const int per = (a.n + kRegGateThreads - 1) / kRegGateThreads;
@@ -97,8 +102,7 @@ void register_gate_kernel(RegisterArgs a)
     }
 }
 
-__global__ __launch_bounds__(kRegHypBlock)
-void register_solve_kernel(RegisterArgs a)
+__device__ __forceinline__ void register_solve_block(const RegisterArgs &a)
 {
     const uint32_t h = blockIdx.x * kRegHypBlock + threadIdx.x;
     if (h == 0) *reinterpret_cast<unsigned long long *>(a.state + kVsKey) = 0ull;
@@ -112,8 +116,8 @@ void register_solve_kernel(RegisterArgs a)
     for (int q = 0; q < 12; ++q) a.poses[(size_t)q * a.H + h] = P[q];
 }
 
-__global__ __launch_bounds__(kRegHypBlock)
-void register_score_kernel(RegisterArgs a)
+// blockIdx.y of gridDim.y candidate shares (a share that is empty -- a job with few candidates -- still adds its arrival)
+__device__ __forceinline__ void register_score_block(const RegisterArgs &a)
 {
     __shared__ float4 sX[kRegTile];
     __shared__ float2 sO[kRegTile];
@@ -152,8 +156,7 @@ void register_score_kernel(RegisterArgs a)
     if ((threadIdx.x & 63) == 0 && key) atomicMax(reinterpret_cast<unsigned long long *>(a.state + kVsKey), key);
 }
 
-__global__ __launch_bounds__(kRegThreads)
-void register_refine_kernel(RegisterArgs a)
+__device__ __forceinline__ void register_refine_block(const RegisterArgs &a)
 {
     __shared__ double s_part[kRegWaves * kRegSysValues];
     __shared__ double s_tot[kRegSysValues];
@@ -316,6 +319,59 @@ void register_refine_kernel(RegisterArgs a)
     }
 }
 
+__global__ __launch_bounds__(kRegGateThreads)
+void register_gate_kernel(RegisterArgs a) { register_gate_block(a); }
+
+__global__ __launch_bounds__(kRegHypBlock)
+void register_solve_kernel(RegisterArgs a) { register_solve_block(a); }
+
+__global__ __launch_bounds__(kRegHypBlock)
+void register_score_kernel(RegisterArgs a) { register_score_block(a); }
+
+__global__ __launch_bounds__(kRegThreads)
+void register_refine_kernel(RegisterArgs a) { register_refine_block(a); }
+
+// ---- many views: job blockIdx.x (gate, refine) / blockIdx.y (solve) / blockIdx.z (score) of `jobs` ----
+// the block's job, through a uniform address (scalar loads), every pointer marked global (block_ops.hpp)
+__device__ __forceinline__ RegisterArgs load_job(const RegisterArgs *__restrict__ jobs, const unsigned int job)
+{
+    RegisterArgs a = jobs[job];
+    a.sift = global_ptr(a.sift); a.points = global_ptr(a.points); a.valid = global_ptr(a.valid); a.K = global_ptr(a.K); a.Kinv = global_ptr(a.Kinv);
+    a.state = global_ptr(a.state); a.Xc = global_ptr(a.Xc); a.Oc = global_ptr(a.Oc); a.slot = global_ptr(a.slot); a.inl = global_ptr(a.inl);
+    a.poses = global_ptr(a.poses); a.acc = global_ptr(a.acc); a.counts = global_ptr(a.counts); a.reproj = global_ptr(a.reproj);
+    return a;
+}
+
+// Every block of the four runs its body to the end (the solve body's lanes past H leave on their own, behind no barrier): no
+// block is cut short in front of a barrier or a ballot.
+__global__ __launch_bounds__(kRegGateThreads)
+void register_gate_views_kernel(const RegisterArgs *__restrict__ jobs)
+{
+    const RegisterArgs a = load_job(jobs, blockIdx.x);
+    register_gate_block(a);
+}
+
+__global__ __launch_bounds__(kRegHypBlock)
+void register_solve_views_kernel(const RegisterArgs *__restrict__ jobs)
+{
+    const RegisterArgs a = load_job(jobs, blockIdx.y);
+    register_solve_block(a);
+}
+
+__global__ __launch_bounds__(kRegHypBlock)
+void register_score_views_kernel(const RegisterArgs *__restrict__ jobs)
+{
+    const RegisterArgs a = load_job(jobs, blockIdx.z);
+    register_score_block(a);
+}
+
+__global__ __launch_bounds__(kRegThreads)
+void register_refine_views_kernel(const RegisterArgs *__restrict__ jobs)
+{
+    const RegisterArgs a = load_job(jobs, blockIdx.x);
+    register_refine_block(a);
+}
+
 // pair->d_vwork for cap_points points: the arrays of `a` inside it; returns its size in bytes
 static size_t register_work_layout(void *buffer, int cap_points, RegisterArgs &a)
 {
@@ -337,9 +393,9 @@ static size_t register_hyp_layout(void *buffer, size_t hyps, RegisterArgs &a)
     return h.used;
 }
 
-int launch_register(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_register_params &p, const float *d_points, const uint8_t *d_valid)
+static void register_args(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_register_params &p, const float *d_points, const uint8_t *d_valid,
+                          RegisterArgs &a)
 {
-    RegisterArgs a;
     a.sift = d_sift; a.points = d_points; a.valid = d_valid;
     a.K = pair->d_K; a.Kinv = pair->d_Kinv;
     a.n = pair->n;
@@ -351,13 +407,27 @@ int launch_register(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_regi
     register_work_layout(pair->d_vwork, pair->cap_points, a);
     register_hyp_layout(pair->d_vhyp, pair->cap_vhyps, a);       // sized for the largest num_hypotheses seen
     a.counts = pair->d_vcounts;
-    hipStream_t st = pair->ctx->stream;
-    const int hblocks = (int)((p.num_hypotheses + kRegHypBlock - 1) / kRegHypBlock);
-    // candidate shares: about four blocks per CU in all, each share at least 128 candidates when every point is one
-    int splits = (4 * pair->ctx->num_cus + hblocks - 1) / hblocks;
-    const int max_splits = pair->n / 128 > 1 ? pair->n / 128 : 1;
+}
+
+// candidate shares of a scoring launch: about four blocks per CU over all its jobs, each share at least 128 candidates when every
+// point of the largest job is one
+static int register_splits(int num_cus, int hblocks, int num_jobs, int nmax)
+{
+    const long long blocks = (long long)hblocks * num_jobs;
+    int splits = (int)((4LL * num_cus + blocks - 1) / blocks);
+    const int max_splits = nmax / 128 > 1 ? nmax / 128 : 1;
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
+    return splits;
+}
+
+int launch_register(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_register_params &p, const float *d_points, const uint8_t *d_valid)
+{
+    RegisterArgs a;
+    register_args(pair, d_sift, p, d_points, d_valid, a);
+    hipStream_t st = pair->ctx->stream;
+    const int hblocks = (int)((p.num_hypotheses + kRegHypBlock - 1) / kRegHypBlock);
+    const int splits = register_splits(pair->ctx->num_cus, hblocks, 1, pair->n);
     hipLaunchKernelGGL(register_gate_kernel, dim3(1), dim3(kRegGateThreads), 0, st, a);
     SFM_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(register_solve_kernel, dim3(hblocks), dim3(kRegHypBlock), 0, st, a);
@@ -365,6 +435,39 @@ int launch_register(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_regi
     hipLaunchKernelGGL(register_score_kernel, dim3(hblocks, splits), dim3(kRegHypBlock), 0, st, a);
     SFM_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(register_refine_kernel, dim3(1), dim3(kRegThreads), 0, st, a);
+    SFM_HIP_TRY(hipGetLastError());
+    return SFM_OK;
+}
+
+int launch_register_views(sfm_ctx *ctx, sfm_pair *const *pairs, int num_pairs, const sfm_sift_point *const *d_sifts, const sfm_register_params &p,
+                          const float *const *d_points, const uint8_t *const *d_valid)
+{
+    hipStream_t st = ctx->stream;
+    JobArray &ja = ctx->register_jobs;
+    int rc = job_array_reserve(ja, (size_t)num_pairs, sizeof(RegisterArgs), st);
+    if (rc != SFM_OK) return rc;
+    // large views first: the one-block gates and LM chains are dispatched in job order.  Stable, so equal sizes keep the caller's
+    // order; a pair's result does not depend on its place (every block works on its own pair's buffers).
+    std::vector<int> order((size_t)num_pairs);
+    for (int i = 0; i < num_pairs; ++i) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return pairs[x]->n > pairs[y]->n; });
+    RegisterArgs *h_jobs = static_cast<RegisterArgs *>(ja.pinned);
+    for (int k = 0; k < num_pairs; ++k) {
+        const int i = order[(size_t)k];
+        register_args(pairs[i], d_sifts[i], p, d_points[i], d_valid[i], h_jobs[k]);
+    }
+    const RegisterArgs *d_jobs = static_cast<const RegisterArgs *>(ja.dev);
+    rc = job_array_upload(ja, (size_t)num_pairs, sizeof(RegisterArgs), st);
+    if (rc != SFM_OK) return rc;
+    const int hblocks = (int)((p.num_hypotheses + kRegHypBlock - 1) / kRegHypBlock);
+    const int splits = register_splits(ctx->num_cus, hblocks, num_pairs, h_jobs[0].n);       // ONE for the launch: counts do not depend on it
+    hipLaunchKernelGGL(register_gate_views_kernel, dim3(num_pairs), dim3(kRegGateThreads), 0, st, d_jobs);
+    SFM_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(register_solve_views_kernel, dim3(hblocks, num_pairs), dim3(kRegHypBlock), 0, st, d_jobs);
+    SFM_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(register_score_views_kernel, dim3(hblocks, splits, num_pairs), dim3(kRegHypBlock), 0, st, d_jobs);
+    SFM_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(register_refine_views_kernel, dim3(num_pairs), dim3(kRegThreads), 0, st, d_jobs);
     SFM_HIP_TRY(hipGetLastError());
     return SFM_OK;
 }

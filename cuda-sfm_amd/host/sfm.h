@@ -171,6 +171,32 @@ inline std::vector<sfm_refine_report> refine_pairs(Image_pair *const *pairs, int
     return reports;
 }
 
+// a further view registered to each of many pairs in one batched call (sfm_register_views), on the refined points like
+// registerView: data[i] = image 1's records of pair i re-matched against that pair's new view; every pair is left as its own
+// registerView() leaves it, bit for bit; returns the reports in the order of the list (one wait for the device)
+inline std::vector<sfm_register_report> register_views(Image_pair *const *pairs, SiftPoint *const *data, int count, int max_iterations = 10,
+                                                       float threshold_px = 4.0f)
+{
+    sfm_register_params p;
+    sfm_register_default_params(&p);
+    p.max_iterations = max_iterations;
+    p.threshold_px = threshold_px;
+    std::vector<sfm_pair *> handles;
+    std::vector<const sfm_sift_point *> records;
+    for (int i = 0; i < count; ++i) {
+        handles.push_back(pairs[i] ? pairs[i]->handle() : nullptr);
+        records.push_back(reinterpret_cast<const sfm_sift_point *>(data[i]));
+    }
+    SFM_FACADE_CALL(sfm_register_views(handles.data(), count, records.data(), &p, nullptr, nullptr));
+    std::vector<sfm_register_report> reports;
+    for (int i = 0; i < count; ++i) {
+        sfm_register_report r;
+        SFM_FACADE_CALL(sfm_get_register_report(handles[(size_t)i], &r));
+        reports.push_back(r);
+    }
+    return reports;
+}
+
 } // namespace SfM
 
 #endif

@@ -379,6 +379,17 @@ typedef struct sfm_register_report {
 } sfm_register_report;
 
 int sfm_register_view(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_register_params *p);   /* enqueue only */
+/* The same registration for many pairs of ONE context in four launches (grid = pairs) on its stream: afterwards every pair is
+ * exactly as after sfm_register_view with the same parameters and its own d_sift / points / valid -- bit for bit, wherever it
+ * stands in the list -- and the getters and SFM_BUF_VIEW_* serve it per pair.  pairs: HOST array of num_pairs (0..65535)
+ * handles, none listed twice (a pair holds one registered view); d_sifts: HOST array of num_pairs DEVICE pointers, d_sifts[i] =
+ * view 1's records of pair i re-matched against that pair's new view (the same pointer may serve several pairs); p: one
+ * parameter set for all of them, p->d_points and p->d_valid must be NULL; d_points, d_valid: optional HOST arrays of num_pairs
+ * DEVICE pointers (d_points NULL, or a NULL entry: that pair's refined points and the refinement's used flags; d_valid[i]
+ * without d_points[i] is SFM_E_INVALID).  Every check precedes the first launch: SFM_E_INVALID (arguments) or SFM_E_STATE (the
+ * text names the first pair without the stage it needs) leave every pair as it was. */
+int sfm_register_views(sfm_pair *const *pairs, int num_pairs, const sfm_sift_point *const *d_sifts, const sfm_register_params *p,
+                       const float *const *d_points, const uint8_t *const *d_valid);   /* enqueue only */
 int sfm_get_register_report(sfm_pair *pair, sfm_register_report *r);                               /* synchronises */
 /* refined [R3|t3; 0 0 0 1] and the RANSAC winner's, row-major; either pointer may be NULL */
 int sfm_get_view_pose(sfm_pair *pair, float h_P[16], float h_P_ransac[16]);
