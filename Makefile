@@ -33,7 +33,7 @@ RVDEMO   := $(PKG)/host/register_views_demo
 IOTEST   := tests/cpp/io_test
 GEOMTEST := tests/cpp/geom_test
 
-all: $(LIB) $(LIB_AB) $(COMMLIB) $(BUILD)/ransac.s oracle hostcheck fakeccl $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(IOTEST) $(GEOMTEST)
+all: $(LIB) $(LIB_AB) $(COMMLIB) $(BUILD)/ransac.s $(BUILD)/view_points.s oracle hostcheck fakeccl $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(IOTEST) $(GEOMTEST)
 
 # the product's objects come with the compiler's resource-usage report (registers, scratch, LDS of every kernel) next to them:
 # $(BUILD)/<source>.usage.txt, read by tests/test_register_budget.py; warnings and errors of the compile are still shown
@@ -47,6 +47,11 @@ $(BUILD)/%.o: $(CSRC)/%.hip $(HDRS)
 $(BUILD)/ransac.s: $(CSRC)/ransac.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(FLAGS_ransac) --cuda-device-only -S $< -o $@
+
+# the same for view_points.hip: the record loads its source describes are read back from it (tests/test_view_points_host.py)
+$(BUILD)/view_points.s: $(CSRC)/view_points.hip $(HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) $(FLAGS_view_points) --cuda-device-only -S $< -o $@
 
 $(BUILD_AB)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(BUILD_AB)
@@ -106,7 +111,7 @@ $(GEOMTEST): tests/cpp/geom_test.cpp $(PKG)/host/geomFuncs.h $(PKG)/host/sfm_io.
 
 # CPU-only: the host-compiled arithmetic check of the non-GPU tests (the fakeccl target, which needs the gfx950 build and the RCCL
 # header, is a target of its own and part of `all`)
-hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so
+hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so
 
 # TEST HARNESS: comm.cpp linked against a shared-memory stand-in for the nine RCCL calls it makes, so that a 1-GPU box can run the
 # exchange code with two real ranks (tests/test_gpu_fakeccl.py); the product's libsfm_amd_rccl.so is linked against librccl
@@ -128,6 +133,11 @@ tests/hostcheck/librefinecheck.so: tests/hostcheck/refinecheck.hip tests/hostche
 tests/hostcheck/libregistercheck.so: tests/hostcheck/registercheck.hip $(CSRC)/register_math.hpp $(CSRC)/refine_math.hpp $(CSRC)/device_math.hpp include/sfm_amd.h
 	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
 
+# the arithmetic of sfm_triangulate_view (view_points_math.hpp: DLT start, point LM, acceptance test) run over arrays on the CPU,
+# for tests/test_view_points_host.py and the byte parity of tests/test_gpu_view_points.py
+tests/hostcheck/libviewpointscheck.so: tests/hostcheck/viewpointscheck.hip $(CSRC)/view_points_math.hpp $(CSRC)/register_math.hpp $(CSRC)/refine_math.hpp $(CSRC)/device_math.hpp include/sfm_amd.h
+	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
+
 # the scoring block's dynamic LDS size (prefilter_lds.hpp), host-compiled for tests/test_register_budget.py
 tests/hostcheck/libpfldscheck.so: tests/hostcheck/pfldscheck.hip $(CSRC)/prefilter_lds.hpp $(CSRC)/prefilter_record.hpp $(CSRC)/prefilter_math.hpp $(CSRC)/device_math.hpp
 	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
@@ -142,7 +152,7 @@ tests/hostcheck/libpairstatecheck.so: tests/hostcheck/pairstatecheck.cpp $(CSRC)
 	g++ -O2 -std=c++17 -Wall -fPIC -shared -o $@ $<
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
+	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all ab oracle hostcheck fakeccl clean

@@ -51,6 +51,7 @@ POSE_REFERENCE, POSE_CORRECT = 0, 1
 (BUF_X0, BUF_X1, BUF_U0, BUF_U1, BUF_E, BUF_P, BUF_PINV, BUF_POINTS, BUF_COUNTS, BUF_MASK, BUF_KEY,
  BUF_ECAND, BUF_PIND, BUF_REFINED_POSE, BUF_REFINED_POINTS, BUF_REPROJ, BUF_VIEW_POSE, BUF_VIEW_COUNTS, BUF_VIEW_REPROJ) = range(19)
 REFINE_CONVERGED, REFINE_MAX_ITER, REFINE_DEGENERATE = 0, 1, 2         # sfm_refine_report.status, sfm_register_report.status
+VP_UNSEEN, VP_NEW, VP_REFINED, VP_NEW_REJECTED, VP_KEPT = range(5)     # sfm_view_points_out.d_flags
 
 SIFT_DTYPE = np.dtype([
     ("xpos", "<f4"), ("ypos", "<f4"), ("scale", "<f4"), ("sharpness", "<f4"),
@@ -76,6 +77,7 @@ EXPORTS = [
     "sfm_get_reprojection_errors",
     "sfm_register_default_params", "sfm_register_view", "sfm_register_views", "sfm_get_register_report", "sfm_get_view_pose", "sfm_get_view_errors",
     "sfm_get_view_counts",
+    "sfm_view_points_default_params", "sfm_triangulate_view", "sfm_triangulate_views",
 ]
 AB_EXPORTS = ["sfm_ransac_last_phases", "sfm_ransac_last_trace", "sfm_prefilter_probe", "sfm_prefilter_band_probe"]      # include/sfm_amd_ab.h
 if AB:
@@ -117,6 +119,18 @@ class RegisterReport(C.Structure):
     _fields_ = [("status", C.c_int32), ("num_candidates", C.c_int32), ("ransac_inliers", C.c_int32), ("num_inliers", C.c_int32),
                 ("best_hypothesis", C.c_uint32), ("iterations", C.c_int32), ("accepted", C.c_int32),
                 ("initial_rms_px", C.c_float), ("final_rms_px", C.c_float), ("final_cost", C.c_float), ("lambda", C.c_float)]
+
+
+class ViewPointsParams(C.Structure):
+    """sfm_view_points_params (include/sfm_amd.h)."""
+    _fields_ = [("threshold_px", C.c_float), ("min_score", C.c_float), ("max_ambiguity", C.c_float), ("min_parallax_deg", C.c_float),
+                ("max_iterations", C.c_int32), ("huber_px", C.c_float), ("min_rel_decrease", C.c_float), ("initial_lambda", C.c_float),
+                ("d_points", C.c_void_p), ("d_valid", C.c_void_p), ("d_poses", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class ViewPointsOut(C.Structure):
+    """sfm_view_points_out (include/sfm_amd.h): the caller's device buffers."""
+    _fields_ = [("d_points", C.c_void_p), ("d_flags", C.c_void_p), ("d_err", C.c_void_p), ("d_counts", C.c_void_p)]
 
 
 _vp = C.c_void_p
@@ -200,6 +214,10 @@ _lib.sfm_get_register_report.argtypes = [_vp, C.POINTER(RegisterReport)]
 _lib.sfm_get_view_pose.argtypes = [_vp, _vp, _vp]
 _lib.sfm_get_view_errors.argtypes = [_vp, _vp, _vp]
 _lib.sfm_get_view_counts.argtypes = [_vp, _vp]
+_lib.sfm_view_points_default_params.argtypes = [C.POINTER(ViewPointsParams)]
+_lib.sfm_view_points_default_params.restype = None
+_lib.sfm_triangulate_view.argtypes = [_vp, _vp, C.POINTER(ViewPointsParams), C.POINTER(ViewPointsOut)]
+_lib.sfm_triangulate_views.argtypes = [C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.POINTER(ViewPointsParams), C.POINTER(ViewPointsOut)]
 if AB:
     _lib.sfm_ransac_last_phases.argtypes = [_vp, C.POINTER(C.c_uint64)]
     _lib.sfm_ransac_last_trace.argtypes = [_vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_size_t)]
@@ -328,6 +346,64 @@ def register_views(pairs, d_sifts, points=None, valid=None, **kw):
     if pairs:
         pairs[0].ctx.synchronize()
     return [p.get_register_report() for p in pairs]
+
+
+_VIEW_POINTS_FIELDS = {f for f, _ in ViewPointsParams._fields_}
+
+
+def view_points_params(**kw):
+    """sfm_view_points_params with the library's defaults (4 px, gate 0.85 / 0.95, 1 degree, 5 iterations, Huber 1 px, 1e-6,
+    lambda 1e-3), fields overridden by kw (points / valid / poses: device tensors / pointers)."""
+    p = ViewPointsParams()
+    _lib.sfm_view_points_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k in ("points", "d_points"):
+            p.d_points = _ptr(v)
+        elif k in ("valid", "d_valid"):
+            p.d_valid = _ptr(v)
+        elif k in ("poses", "d_poses"):
+            p.d_poses = _ptr(v)
+        elif k == "reserved":
+            for i, x in enumerate(v):
+                p.reserved[i] = int(x)
+        elif k in _VIEW_POINTS_FIELDS:
+            setattr(p, k, v)
+        else:
+            raise TypeError(f"view_points_params: no field {k!r} in sfm_view_points_params")
+    return p
+
+
+def _view_points_buffers(torch, device, n):
+    """Output tensors of one triangulate_view call: points 4 x n, flags, err, counts."""
+    return (torch.empty((4, n), dtype=torch.float32, device=device), torch.empty(n, dtype=torch.uint8, device=device),
+            torch.empty(n, dtype=torch.float32, device=device), torch.empty(8, dtype=torch.int32, device=device))
+
+
+def triangulate_views_enqueue(pairs, d_sifts, params, outs):
+    """sfm_triangulate_views (enqueue only): ImagePair.triangulate_view_enqueue for every pair of the list (one Context, none
+    twice, each refined and registered) in one launch.  d_sifts: one entry per pair; outs: one (points, flags, err, counts)
+    tuple of device tensors / pointers per pair (err, counts may be None); params.d_points / d_valid / d_poses must stay
+    unset."""
+    n = len(pairs)
+    assert len(d_sifts) == n and len(outs) == n, "one record pointer and one output set per pair"
+    handles = (_vp * n)(*[p._h.value for p in pairs])
+    sifts = (_vp * n)(*[_ptr(d) for d in d_sifts])
+    o = (ViewPointsOut * n)(*[ViewPointsOut(*[_ptr(t) for t in (tuple(out) + (None, None))[:4]]) for out in outs])
+    _check(_lib.sfm_triangulate_views(handles, n, sifts, C.byref(params), o), "sfm_triangulate_views")
+
+
+def triangulate_views(pairs, d_sifts, **kw):
+    """ImagePair.triangulate_view for a list of pairs in one batched call; kw are ViewPointsParams fields, the same for every
+    pair.  Returns one (points 4 x n, flags, err, counts) tuple of numpy arrays per pair: one wait for the device."""
+    if not pairs:
+        triangulate_views_enqueue([], [], view_points_params(**kw), [])
+        return []
+    dev = torch.device("cuda", pairs[0].ctx.device)
+    counts = torch.empty((len(pairs), 8), dtype=torch.int32, device=dev)         # one array: the launcher zeroes it with one memset
+    outs = [_view_points_buffers(torch, dev, p.num_points)[:3] + (counts[i],) for i, p in enumerate(pairs)]
+    triangulate_views_enqueue(pairs, d_sifts, view_points_params(**kw), outs)
+    pairs[0].ctx.synchronize()
+    return [tuple(t.cpu().numpy() for t in out) for out in outs]
 
 
 def sift_temp_layout(width, height, num_octaves=5, scale_up=False):
@@ -663,6 +739,22 @@ class ImagePair:
         out = np.empty(nbytes // 4, np.int32)
         _check(_lib.sfm_get_view_counts(self._h, out.ctypes.data_as(_vp)), "sfm_get_view_counts")
         return out
+
+    # -- the pair's points over its registered view -----------------------------------------------------
+    def triangulate_view_enqueue(self, d_sift, params, points, flags, err=None, counts=None):
+        """sfm_triangulate_view with a ViewPointsParams (enqueue only): points (4 x n float32), flags (n uint8), err (n float32,
+        optional) and counts (8 int32, optional) are the caller's device tensors / pointers.  Nothing in the pair changes."""
+        out = ViewPointsOut(_ptr(points), _ptr(flags), _ptr(err), _ptr(counts))
+        _check(_lib.sfm_triangulate_view(self._h, _ptr(d_sift), C.byref(params), C.byref(out)), "sfm_triangulate_view")
+
+    def triangulate_view(self, d_sift, **kw):
+        """The pair's points triangulated / refined over views 1, 2 and the registered view: d_sift holds view 1's records
+        re-matched against it (register_view's); kw are ViewPointsParams fields (points / valid / poses: device tensors).
+        Returns (points 4 x n, flags VP_*, err px, counts int32[8]) as numpy (synchronises)."""
+        outs = _view_points_buffers(torch, torch.device("cuda", self.ctx.device), self.num_points)
+        self.triangulate_view_enqueue(d_sift, view_points_params(**kw), *outs)
+        self.ctx.synchronize()
+        return tuple(t.cpu().numpy() for t in outs)
 
     # -- accessors --------------------------------------------------------------------------------
     def device_ptr(self, which):

@@ -219,6 +219,7 @@ static int ctx_destroy_now(sfm_ctx *ctx)
     sift_job_free(ctx);
     job_array_free(ctx->refine_jobs);
     job_array_free(ctx->register_jobs);
+    job_array_free(ctx->view_points_jobs);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     for (auto &t : ctx->tev) for (hipEvent_t e : t) if (e) (void)hipEventDestroy(e);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -1057,6 +1058,99 @@ int sfm_get_view_counts(sfm_pair *pair, int32_t *h_counts)
     SFM_REQUIRE(pair && h_counts, SFM_E_INVALID, "null argument");
     SFM_NEED(pair, kView);
     return copy_out(pair, h_counts, pair->d_vcounts, (size_t)pair->view_hyps * 4);
+}
+
+// ---- the pair's points over its registered view (view_points.hip) ---------------------------------
+void sfm_view_points_default_params(sfm_view_points_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->threshold_px = 4.0f;
+    p->min_score = 0.85f;
+    p->max_ambiguity = 0.95f;
+    p->min_parallax_deg = 1.0f;
+    p->max_iterations = 5;
+    p->huber_px = 1.0f;
+    p->min_rel_decrease = 1e-6f;
+    p->initial_lambda = 1e-3f;
+}
+
+// the parameter checks of sfm_triangulate_view and sfm_triangulate_views (none needs a device)
+static int check_view_points_params(const sfm_view_points_params &p)
+{
+    SFM_REQUIRE(p.reserved[0] == 0 && p.reserved[1] == 0 && p.reserved[2] == 0 && p.reserved[3] == 0, SFM_E_INVALID,
+                "sfm_view_points_params.reserved[] must be zero");
+    SFM_REQUIRE(p.max_iterations >= 0 && p.max_iterations <= 50, SFM_E_INVALID, "max_iterations %d outside 0..50", p.max_iterations);
+    SFM_REQUIRE(p.huber_px >= 0.0f && isfinite(p.huber_px), SFM_E_INVALID, "huber_px must be finite and >= 0");
+    SFM_REQUIRE(isfinite(p.min_rel_decrease) && p.min_rel_decrease >= 0.0f, SFM_E_INVALID, "min_rel_decrease must be finite and >= 0");
+    SFM_REQUIRE(isfinite(p.initial_lambda) && p.initial_lambda >= 0.0f, SFM_E_INVALID, "initial_lambda must be finite and >= 0");
+    SFM_REQUIRE(isfinite(p.threshold_px) && p.threshold_px > 0.0f, SFM_E_INVALID, "threshold_px must be finite and > 0");
+    SFM_REQUIRE(isfinite(p.min_score) && isfinite(p.max_ambiguity), SFM_E_INVALID, "min_score / max_ambiguity must be finite");
+    SFM_REQUIRE(p.min_parallax_deg >= 0.0f && p.min_parallax_deg <= 90.0f, SFM_E_INVALID, "min_parallax_deg outside 0..90");
+    return SFM_OK;
+}
+
+// the inputs a call reads where the caller gave none: the refined points and used flags, the refined pose, the view's refined pose
+static ViewPointsInputs view_points_inputs(const sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_view_points_params &p)
+{
+    ViewPointsInputs in;
+    in.sift = d_sift;
+    in.points = p.d_points ? p.d_points : pair->d_rpoints;
+    in.valid = p.d_points ? p.d_valid : reproj_flags(pair, pair->d_rreproj);
+    in.pose2 = p.d_poses ? p.d_poses : pair->d_rstate + refine_pose_offset();
+    in.pose3 = p.d_poses ? p.d_poses + 12 : pair->d_vstate + register_pose_offset();
+    in.pose_rows = p.d_poses ? 3 : 4;
+    return in;
+}
+
+int sfm_triangulate_view(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_view_points_params *p, const sfm_view_points_out *out)
+{
+    SFM_REQUIRE(pair && d_sift && p && out, SFM_E_INVALID, "null argument");
+    int rc = check_view_points_params(*p);
+    if (rc != SFM_OK) return rc;
+    SFM_REQUIRE(p->d_points || !p->d_valid, SFM_E_INVALID, "d_valid needs d_points");
+    SFM_REQUIRE(out->d_points && out->d_flags, SFM_E_INVALID, "sfm_view_points_out.d_points and d_flags are required");
+    SFM_REQUIRE(out->d_points != p->d_points, SFM_E_INVALID, "the output points must not be the input points");
+    SFM_REQUIRE((reinterpret_cast<uintptr_t>(d_sift) & 15) == 0, SFM_E_INVALID, "d_sift must be 16-byte aligned (the records are read with 16-byte loads)");
+    SFM_FLUSH(pair);
+    SFM_NEED(pair, kPoints | ((p->d_points && p->d_poses) ? 0u : (uint32_t)kRefined) | (p->d_poses ? 0u : (uint32_t)kView));
+    SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
+    return launch_view_points(pair, view_points_inputs(pair, d_sift, *p), *p, *out);       // reads the pair: no stage changes
+}
+
+int sfm_triangulate_views(sfm_pair *const *pairs, int num_pairs, const sfm_sift_point *const *d_sifts, const sfm_view_points_params *p,
+                          const sfm_view_points_out *outs)
+{
+    // the checks that need no device first, all of them before anything is enqueued
+    SFM_REQUIRE(p, SFM_E_INVALID, "null params");
+    SFM_REQUIRE(num_pairs >= 0 && num_pairs <= 65535, SFM_E_INVALID, "num_pairs %d outside 0..65535", num_pairs);
+    SFM_REQUIRE(!p->d_points && !p->d_valid && !p->d_poses, SFM_E_INVALID,
+                "sfm_view_points_params.d_points / d_valid / d_poses must be null here: every pair reads its own refinement and registration");
+    int rc = check_view_points_params(*p);
+    if (rc != SFM_OK) return rc;
+    if (num_pairs == 0) return SFM_OK;
+    SFM_REQUIRE(pairs && d_sifts && outs, SFM_E_INVALID, "null pair list, d_sifts list or outs list");
+    for (int i = 0; i < num_pairs; ++i) {
+        SFM_REQUIRE(pairs[i], SFM_E_INVALID, "pairs[%d] is null", i);
+        SFM_REQUIRE(d_sifts[i], SFM_E_INVALID, "d_sifts[%d] is null", i);
+        SFM_REQUIRE((reinterpret_cast<uintptr_t>(d_sifts[i]) & 15) == 0, SFM_E_INVALID, "d_sifts[%d] must be 16-byte aligned", i);
+        SFM_REQUIRE(outs[i].d_points && outs[i].d_flags, SFM_E_INVALID, "outs[%d]: d_points and d_flags are required", i);
+    }
+    sfm_ctx *ctx = pairs[0]->ctx;
+    for (int i = 1; i < num_pairs; ++i) SFM_REQUIRE(pairs[i]->ctx == ctx, SFM_E_INVALID, "pairs[%d] belongs to another context than pairs[0]", i);
+    {
+        std::vector<const sfm_pair *> sorted(pairs, pairs + num_pairs);
+        std::sort(sorted.begin(), sorted.end(), std::less<const sfm_pair *>());
+        SFM_REQUIRE(std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end(), SFM_E_INVALID, "a pair is listed twice");
+    }
+    for (int i = 0; i < num_pairs; ++i) SFM_FLUSH(pairs[i]);
+    const uint32_t need = kPoints | kRefined | kView;
+    for (int i = 0; i < num_pairs; ++i)
+        SFM_REQUIRE(pairs[i]->state.has(need), SFM_E_STATE, "pairs[%d]: %s", i, pair_stage_hint(pairs[i]->state.missing(need)));
+    SFM_HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<ViewPointsInputs> in((size_t)num_pairs);
+    for (int i = 0; i < num_pairs; ++i) in[(size_t)i] = view_points_inputs(pairs[i], d_sifts[i], *p);
+    return launch_view_points_views(ctx, pairs, num_pairs, in.data(), *p, outs);
 }
 
 // ---- accessors ------------------------------------------------------------------------------------

@@ -187,8 +187,9 @@ struct sfm_ctx {
     size_t pool_records_cap = 0;       // floats
     void *batch_ws = nullptr;          // sfm_process_pairs, batched path: the PairJob array + every pair's buffers (pairs_batch.hpp)
     size_t batch_ws_bytes = 0;
-    // sfm_refine_pairs / sfm_register_views: the RefineArgs (refine.hip) / RegisterArgs (register.hip) of a call
-    sfm::JobArray refine_jobs, register_jobs;
+    // sfm_refine_pairs / sfm_register_views / sfm_triangulate_views: the RefineArgs (refine.hip) / RegisterArgs (register.hip) /
+    // ViewPointsArgs (view_points.hip) of a call
+    sfm::JobArray refine_jobs, register_jobs, view_points_jobs;
     void *sift_job = nullptr;          // the extraction in flight (sift.hip: SiftJob), sfm_extract_sift_begin .. _end
     // kernels that already opted in to > 64 KiB of dynamic LDS on THIS context's device (function attributes are
     // per device; a context is used by one host thread at a time, so no process-wide flag)
@@ -358,6 +359,14 @@ size_t register_hyp_bytes(size_t num_hypotheses);                 // bytes of pa
 int register_state_words();                                       // floats of pair->d_vstate
 int register_pose_offset();                                       // refined pose, then the RANSAC pose, inside d_vstate
 int register_report_offset();                                     // sfm_register_report inside d_vstate
+
+// view_points.hip: the pair's points over its registered view, one lane per point; d_points / d_valid / d_pose2 / d_pose3 resolved
+// by the caller (pose_rows: 3 = [R|t] as R (9) then t (3), 4 = a 4 x 4 row-major matrix as the pair stores its poses)
+struct ViewPointsInputs { const sfm_sift_point *sift; const float *points; const uint8_t *valid; const float *pose2, *pose3; int pose_rows; };
+int launch_view_points(sfm_pair *pair, const ViewPointsInputs &in, const sfm_view_points_params &p, const sfm_view_points_out &out);
+// the same for many pairs of one context in one launch (grid = point blocks x pairs)
+int launch_view_points_views(sfm_ctx *ctx, sfm_pair *const *pairs, int num_pairs, const ViewPointsInputs *in, const sfm_view_points_params &p,
+                             const sfm_view_points_out *outs);
 
 // sift.hip
 void sift_layout(int width, int height, int num_octaves, int scale_up, sfm_sift_layout *L);

@@ -96,6 +96,19 @@ SFM_HD constexpr int symn(int i, int j) { return i <= j ? i * N - i * (i - 1) / 
 SFM_HD constexpr int sym5(int i, int j) { return symn<5>(i, j); }
 SFM_HD constexpr int sym3(int i, int j) { return symn<3>(i, j); }
 
+// Vi = (V + lambda diag V)^-1 of a packed symmetric 3 x 3 by the adjugate (not finite for a singular V): the point block of the
+// two-view refinement and the whole system of a point-only refinement (view_points_math.hpp)
+SFM_HD void refine_damped_inverse3(const float V[6], float lambda, float Vi[6])
+{
+    const float d = 1.0f + lambda;
+    const float a = V[0] * d, b = V[1], c = V[2], e = V[3] * d, f = V[4], g = V[5] * d;
+    const float A = e * g - f * f, B = c * f - b * g, C = b * f - c * e;
+    const float det = a * A + b * B + c * C;
+    const float id = 1.0f / det;
+    Vi[0] = A * id; Vi[1] = B * id; Vi[2] = C * id;
+    Vi[3] = (a * g - c * c) * id; Vi[4] = (b * c - a * f) * id; Vi[5] = (a * e - b * b) * id;
+}
+
 // The point block of the damped normal equations: Vi = (V + lambda diag V)^-1 (packed 3 x 3), Wm = Jc^T W Jp (5 x 3 row-major),
 // gp = Jp^T W r (3).  w1, w2: the per-view weights.
 SFM_HD void refine_point_block(const RefineJac &J, float w1, float w2, float lambda, float Vi[6], float Wm[15], float gp[3])
@@ -111,13 +124,7 @@ SFM_HD void refine_point_block(const RefineJac &J, float w1, float w2, float lam
         }
         gp[a] = w1 * (J.Jp[a] * J.r[0] + J.Jp[3 + a] * J.r[1]) + w2 * (J.Jp[6 + a] * J.r[2] + J.Jp[9 + a] * J.r[3]);
     }
-    const float d = 1.0f + lambda;
-    const float a = V[0] * d, b = V[1], c = V[2], e = V[3] * d, f = V[4], g = V[5] * d;
-    const float A = e * g - f * f, B = c * f - b * g, C = b * f - c * e;
-    const float det = a * A + b * B + c * C;
-    const float id = 1.0f / det;
-    Vi[0] = A * id; Vi[1] = B * id; Vi[2] = C * id;
-    Vi[3] = (a * g - c * c) * id; Vi[4] = (b * c - a * f) * id; Vi[5] = (a * e - b * b) * id;
+    refine_damped_inverse3(V, lambda, Vi);
 #pragma unroll
     for (int i = 0; i < 5; ++i)
 #pragma unroll

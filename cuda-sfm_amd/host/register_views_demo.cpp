@@ -4,7 +4,9 @@
 //   then MatchSiftData(1, 3) per triple and ONE register_views over all of them.
 // The feature sets come from files of raw SiftPoint records (as two_view_demo reads them), three per triple:
 //     register_views_demo <refine_iterations> <a1.bin> <a2.bin> <a3.bin> [<b1.bin> <b2.bin> <b3.bin> ...]
-// One line per triple: the view3 line sfm_main prints for that triple alone (same camera, same settings, the same refine_iterations).
+//   then ONE triangulate_views over all of them: every pair's points over its three views.
+// Two lines per triple: the view3 and view3 points lines sfm_main prints for that triple alone (same camera, same settings, the
+// same refine_iterations).
 // Plain C++: needs only the facade headers and libsfm_amd.so.
 #include <algorithm>
 #include <cmath>
@@ -72,6 +74,7 @@ int main(int argc, char **argv)
         records.push_back(sift[(size_t)3 * k].d_data);
     }
     const std::vector<sfm_register_report> reports = SfM::register_views(pairs.data(), records.data(), count);
+    const std::vector<SfM::ViewPoints> clouds = SfM::triangulate_views(pairs.data(), records.data(), count);
     for (int k = 0; k < count; ++k) {
         const sfm_register_report &vr = reports[(size_t)k];
         float P3[16];
@@ -83,6 +86,8 @@ int main(int argc, char **argv)
         }
         std::printf("view3: %d/%d inliers, rms %.4f -> %.4f px, |C3| %.4f\n", vr.num_inliers, vr.num_candidates, vr.initial_rms_px,
                     vr.final_rms_px, std::sqrt(nc));
+        const int32_t *c = clouds[(size_t)k].counts;
+        std::printf("view3 points: %d new, %d refined, %d kept, %d rejected\n", c[SFM_VP_NEW], c[SFM_VP_REFINED], c[SFM_VP_KEPT], c[SFM_VP_NEW_REJECTED]);
     }
     owned.clear();
     for (SiftData &s : sift) FreeSiftData(s);

@@ -16,11 +16,54 @@
 #define SFM_AMD_SFM_H
 
 #include <cstdint>
+#include <memory>
 #include <vector>
 
 #include "cudaSift.h"
 
 namespace SfM {
+
+// what triangulateView / triangulate_views return for one pair, in host memory
+struct ViewPoints {
+    std::vector<float> points;          // 4 x N: (X, Y, Z, 1) where flags is SFM_VP_NEW / SFM_VP_REFINED, else the refined point
+    std::vector<uint8_t> flags;         // N: SFM_VP_*
+    int32_t counts[8];                  // [0..4]: points per class
+};
+
+namespace detail {
+// device scratch of one triangulation result: points, flags and counts in ONE sfm_device_alloc block
+struct ViewPointsScratch {
+    char *block = nullptr;
+    size_t n = 0;
+    explicit ViewPointsScratch(int num_points) : n((size_t)num_points)
+    {
+        SFM_FACADE_CALL(sfm_device_alloc(sfm_facade::context(), 16 * n + 32 + flag_bytes(), reinterpret_cast<void **>(&block)));
+    }
+    ViewPointsScratch(const ViewPointsScratch &) = delete;
+    ViewPointsScratch &operator=(const ViewPointsScratch &) = delete;
+    ~ViewPointsScratch() { if (block) sfm_device_free(sfm_facade::context(), block); }
+    size_t flag_bytes() const { return (n + 15) / 16 * 16; }
+    sfm_view_points_out out() const
+    {
+        sfm_view_points_out o;
+        o.d_points = reinterpret_cast<float *>(block);
+        o.d_counts = reinterpret_cast<int32_t *>(block + 16 * n);
+        o.d_flags = reinterpret_cast<uint8_t *>(block + 16 * n + 32);
+        o.d_err = nullptr;
+        return o;
+    }
+    ViewPoints download() const          // synchronises
+    {
+        ViewPoints r;
+        r.points.resize(4 * n); r.flags.resize(n);
+        const sfm_view_points_out o = out();
+        SFM_FACADE_CALL(sfm_copy_to_host(sfm_facade::context(), r.points.data(), o.d_points, 16 * n));
+        SFM_FACADE_CALL(sfm_copy_to_host(sfm_facade::context(), r.flags.data(), o.d_flags, n));
+        SFM_FACADE_CALL(sfm_copy_to_host(sfm_facade::context(), r.counts, o.d_counts, 32));
+        return r;
+    }
+};
+} // namespace detail
 
 class Image_pair {
     sfm_pair *pair_ = nullptr;
@@ -147,6 +190,20 @@ public:
         SFM_FACADE_CALL(sfm_get_view_errors(pair_, e.data(), inlier ? inlier->data() : nullptr));
         return e;
     }
+    // the pair's points triangulated / refined over views 1, 2 and the registered view (sfm_triangulate_view): data = the
+    // records registerView took; nothing in the pair changes; returns points, flags and counts (synchronises)
+    ViewPoints triangulateView(SiftPoint *data, int max_iterations = 5, float threshold_px = 4.0f, float min_parallax_deg = 1.0f)
+    {
+        sfm_view_points_params p;
+        sfm_view_points_default_params(&p);
+        p.max_iterations = max_iterations;
+        p.threshold_px = threshold_px;
+        p.min_parallax_deg = min_parallax_deg;
+        const detail::ViewPointsScratch scratch(num_points_);
+        const sfm_view_points_out out = scratch.out();
+        SFM_FACADE_CALL(sfm_triangulate_view(pair_, reinterpret_cast<const sfm_sift_point *>(data), &p, &out));
+        return scratch.download();
+    }
     std::vector<float> getX(int image)      // 3 x N normalised coordinates of image 0 / 1
     {
         std::vector<float> x((size_t)3 * num_points_);
@@ -195,6 +252,32 @@ inline std::vector<sfm_register_report> register_views(Image_pair *const *pairs,
         reports.push_back(r);
     }
     return reports;
+}
+
+// triangulateView for each of many pairs in one batched call (sfm_triangulate_views): data[i] = the records register_views took
+// for pair i; returns one result per pair in the order of the list, each as its own triangulateView() gives it
+inline std::vector<ViewPoints> triangulate_views(Image_pair *const *pairs, SiftPoint *const *data, int count, int max_iterations = 5,
+                                                 float threshold_px = 4.0f, float min_parallax_deg = 1.0f)
+{
+    sfm_view_points_params p;
+    sfm_view_points_default_params(&p);
+    p.max_iterations = max_iterations;
+    p.threshold_px = threshold_px;
+    p.min_parallax_deg = min_parallax_deg;
+    std::vector<sfm_pair *> handles;
+    std::vector<const sfm_sift_point *> records;
+    std::vector<std::unique_ptr<detail::ViewPointsScratch>> scratch;
+    std::vector<sfm_view_points_out> outs;
+    for (int i = 0; i < count; ++i) {
+        handles.push_back(pairs[i] ? pairs[i]->handle() : nullptr);
+        records.push_back(reinterpret_cast<const sfm_sift_point *>(data[i]));
+        scratch.emplace_back(new detail::ViewPointsScratch(pairs[i] ? pairs[i]->numPoints() : 0));
+        outs.push_back(scratch.back()->out());
+    }
+    SFM_FACADE_CALL(sfm_triangulate_views(handles.data(), count, records.data(), &p, outs.data()));
+    std::vector<ViewPoints> results;
+    for (int i = 0; i < count; ++i) results.push_back(scratch[(size_t)i]->download());
+    return results;
 }
 
 } // namespace SfM

@@ -7,7 +7,10 @@
 // refine_iterations > 0 (default 0: nothing changes): two-view bundle adjustment after the pose chain; the PLY then holds the
 // refined points of the correspondences the refinement used, and one more line is printed.
 // img3 (with refine_iterations > 0): a third view of the same size, registered against the refined points (image 1 matched
-// against it, P3P RANSAC + pose LM); one more line: inliers / candidates, rms before -> after, |C3| = |-R3^T t3|.
+// against it, P3P RANSAC + pose LM); one more line: inliers / candidates, rms before -> after, |C3| = |-R3^T t3|.  Then the pair's
+// points are triangulated / refined over the three views; one more line: view3 points: <new> new, <refined> refined, <kept> kept,
+// <rejected> rejected; the PLY is then written again with the merged cloud (new and refined points from the three-view result, the
+// rest as before) and a last line says so: merged cloud: <count> points -> <file>.
 // result.bin (optional, for tests): int n, float E[9], int pose, uint hyp, uint count, float P[16] (chosen), float pts[4n], u8 mask[n]
 // Plain C++: facade headers + libsfm_amd.so only (no OpenCV, no GL).
 #include <cmath>
@@ -75,9 +78,9 @@ int main(int argc, char **argv)
     const int refine_iterations = argc > 10 ? std::atoi(argv[10]) : 0;
     int written = 0;
     sfm_refine_report rep = {};
+    std::vector<uint8_t> used;
     if (refine_iterations > 0) {
         rep = sfm.refine(refine_iterations);
-        std::vector<uint8_t> used;
         const std::vector<float> refined = sfm.getRefinedPoints();
         sfm.getReprojectionErrors(&used);
         written = WritePLY(argv[3], refined.data(), n, used.data());
@@ -116,6 +119,16 @@ int main(int argc, char **argv)
         }
         std::printf("view3: %d/%d inliers, rms %.4f -> %.4f px, |C3| %.4f\n", vr.num_inliers, vr.num_candidates, vr.initial_rms_px,
                     vr.final_rms_px, std::sqrt(nc));
+        // the intersection step behind the resection: the merged cloud replaces the two-view one in the PLY -- new and refined
+        // points from the three-view result, the rest as before
+        const SfM::ViewPoints cloud = sfm.triangulateView(siftData1.d_data);
+        std::printf("view3 points: %d new, %d refined, %d kept, %d rejected\n", cloud.counts[SFM_VP_NEW], cloud.counts[SFM_VP_REFINED],
+                    cloud.counts[SFM_VP_KEPT], cloud.counts[SFM_VP_NEW_REJECTED]);
+        std::vector<uint8_t> keep(used);
+        for (int32_t j = 0; j < n; ++j)
+            if (cloud.flags[(size_t)j] == SFM_VP_NEW || cloud.flags[(size_t)j] == SFM_VP_REFINED) keep[(size_t)j] = 1;
+        const int merged = WritePLY(argv[3], cloud.points.data(), n, keep.data());      // replaces the two-view file written above
+        std::printf("merged cloud: %d points -> %s\n", merged, argv[3]);
         FreeSiftData(siftData3);
     }
     if (argc > 4 && argv[4][0]) {

@@ -399,6 +399,54 @@ int sfm_get_view_errors(sfm_pair *pair, float *h_err, uint8_t *h_inlier);
 /* the inlier count of every hypothesis of the last registration (num_hypotheses int32) */
 int sfm_get_view_counts(sfm_pair *pair, int32_t *h_counts);
 
+/* ---- triangulating and refining the pair's points over its registered view ------------------------
+ * The intersection step behind the resection: with the cameras [I|0], [R|t] and [R3|t3] fixed, every record of view 1 that the
+ * new view sees (match >= 0, score > min_score, ambiguity < max_ambiguity: the registration's gate) gets a point from all the
+ * views that have one.  A record whose input point is usable (the registration's point test) starts at X / W and is refined over
+ * views 1, 2 and 3; one without a usable point -- a wrong match in view 2 -- is triangulated from views 1 and 3 (the DLT of
+ * sfm_triangulate) and refined over those two.  The refinement is a Levenberg-Marquardt on the three point coordinates, Huber
+ * loss on the pixel residuals, fp32, one lane per point.  A result is accepted when every view used passes the registration's
+ * inlier test at threshold_px (in front of the camera included) and, for a new point, the rays of cameras 1 and 3 subtend at
+ * least min_parallax_deg; otherwise the input column is kept.
+ * The call READS the pair and writes only the caller's buffers: no stage, buffer id or getter belongs to it, every SFM_BUF_* is
+ * the same afterwards.  Observations: views 1 and 2 from the pair's X0 / X1 (dehomogenised), view 3 as K^-1 (match_xpos,
+ * match_ypos, 1) of d_sift (sfm_register_view's records).  d_sift must be 16-byte aligned (SFM_E_INVALID otherwise): a record's
+ * fields are read with one 8-byte and one 16-byte load; every device allocation is. */
+#define SFM_VP_UNSEEN        0   /* view 3 does not see the record: input column copied, err = +inf                       */
+#define SFM_VP_NEW           1   /* no usable input point: triangulated from views 1 and 3, refined, accepted             */
+#define SFM_VP_REFINED       2   /* usable input point refined over views 1, 2 and 3, accepted                            */
+#define SFM_VP_NEW_REJECTED  3   /* as SFM_VP_NEW, but the result failed the acceptance test: input column copied         */
+#define SFM_VP_KEPT          4   /* as SFM_VP_REFINED, but the result failed the test (view 3 disagrees): input column copied */
+typedef struct sfm_view_points_params {
+    float   threshold_px;              /* acceptance: the registration's inlier test, default 4.0                          */
+    float   min_score, max_ambiguity;  /* the gate on view 3's match, defaults 0.85 / 0.95                                 */
+    float   min_parallax_deg;          /* SFM_VP_NEW only: angle between the rays of cameras 1 and 3; 0..90, default 1.0   */
+    int32_t max_iterations;            /* point LM, accepted + rejected, 0..50 (0 = start point only), default 5           */
+    float   huber_px, min_rel_decrease, initial_lambda;   /* as sfm_register_params; 1.0 / 1e-6 / 1e-3                     */
+    const float   *d_points;           /* optional DEVICE 4 x num_points; NULL = refined points + the refinement's used flags */
+    const uint8_t *d_valid;            /* optional DEVICE uint8[num_points], only with d_points (NULL: every point)        */
+    const float   *d_poses;            /* optional DEVICE float[24]: [R|t] of camera 2, then of camera 3, each row-major R (9)
+                                          then t (3); NULL = the refined pose and the registered view's refined pose        */
+    int32_t reserved[4];               /* must be zero (else SFM_E_INVALID)                                                */
+} sfm_view_points_params;
+typedef struct sfm_view_points_out {   /* DEVICE buffers of the caller; none may overlap an input or a buffer of the pair  */
+    float   *d_points;                 /* 4 x num_points, required: (X, Y, Z, 1) for SFM_VP_NEW / _REFINED, else the input column */
+    uint8_t *d_flags;                  /* num_points, required: SFM_VP_*                                                    */
+    float   *d_err;                    /* num_points, optional: the largest pixel error over the views used, at the point that
+                                          was attempted (also for the rejected classes; +inf where there is none)           */
+    int32_t *d_counts;                 /* 8, optional: [0..4] the number of points per class, [5..7] zero                    */
+} sfm_view_points_out;
+void sfm_view_points_default_params(sfm_view_points_params *p);
+/* Needs points; the refinement unless d_points AND d_poses are given; the registration unless d_poses is given (SFM_E_STATE). */
+int sfm_triangulate_view(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm_view_points_params *p,
+                         const sfm_view_points_out *out);                                          /* enqueue only */
+/* The same for many pairs of ONE context in one launch: every outs[i] ends byte for byte as after sfm_triangulate_view on
+ * pairs[i].  pairs, d_sifts, outs: HOST arrays of num_pairs (0..65535) entries, no pair twice; p: one parameter set,
+ * p->d_points, p->d_valid and p->d_poses must be NULL, so every pair needs its refinement and its registration.  Every check
+ * precedes the launch: on SFM_E_INVALID / SFM_E_STATE (the text names the first offending pair) nothing is written. */
+int sfm_triangulate_views(sfm_pair *const *pairs, int num_pairs, const sfm_sift_point *const *d_sifts,
+                          const sfm_view_points_params *p, const sfm_view_points_out *outs);     /* enqueue only */
+
 /* ---- accessors (the reference keeps these private; needed for parity checks) ------------------ */
 #define SFM_BUF_X0      0   /* float 3 x ld   normalised coords image 1 (ld = sfm_pair_ld)   */
 #define SFM_BUF_X1      1
