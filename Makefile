@@ -66,6 +66,9 @@ $(BUILD_AB)/ab_%.o: $(CSRC)/ab/%.hip $(HDRS)
 FLAGS_ransac := -fno-slp-vectorize
 # match_fused's two interleaved exact chains: paired into v_pk_fma_f32 they need a register move per operand
 FLAGS_match_fused := -fno-slp-vectorize
+# adjust.hip's solve kernel keeps both cameras in scalar registers: paired into v_pk_* the terms need scalar pairs that are moved and
+# spilled (256 VGPRs + 672 bytes of scratch with the vectoriser, no scratch without)
+FLAGS_adjust := -fno-slp-vectorize
 
 $(LIB): $(OBJS) $(CSRC)/exports.map
 	@mkdir -p $(PKG)/lib
@@ -111,7 +114,7 @@ $(GEOMTEST): tests/cpp/geom_test.cpp $(PKG)/host/geomFuncs.h $(PKG)/host/sfm_io.
 
 # CPU-only: the host-compiled arithmetic check of the non-GPU tests (the fakeccl target, which needs the gfx950 build and the RCCL
 # header, is a target of its own and part of `all`)
-hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so
+hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so
 
 # TEST HARNESS: comm.cpp linked against a shared-memory stand-in for the nine RCCL calls it makes, so that a 1-GPU box can run the
 # exchange code with two real ranks (tests/test_gpu_fakeccl.py); the product's libsfm_amd_rccl.so is linked against librccl
@@ -138,6 +141,11 @@ tests/hostcheck/libregistercheck.so: tests/hostcheck/registercheck.hip $(CSRC)/r
 tests/hostcheck/libviewpointscheck.so: tests/hostcheck/viewpointscheck.hip $(CSRC)/view_points_math.hpp $(CSRC)/register_math.hpp $(CSRC)/refine_math.hpp $(CSRC)/device_math.hpp include/sfm_amd.h
 	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
 
+# the arithmetic of sfm_adjust_view (adjust_math.hpp: view bits, Jacobians, Schur terms, camera step) and a serial driver of the
+# whole chain, for tests/test_adjust_host.py and the comparison of tests/test_gpu_adjust.py
+tests/hostcheck/libadjustcheck.so: tests/hostcheck/adjustcheck.hip $(CSRC)/adjust_math.hpp $(CSRC)/view_points_math.hpp $(CSRC)/register_math.hpp $(CSRC)/refine_math.hpp $(CSRC)/device_math.hpp include/sfm_amd.h
+	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
+
 # the scoring block's dynamic LDS size (prefilter_lds.hpp), host-compiled for tests/test_register_budget.py
 tests/hostcheck/libpfldscheck.so: tests/hostcheck/pfldscheck.hip $(CSRC)/prefilter_lds.hpp $(CSRC)/prefilter_record.hpp $(CSRC)/prefilter_math.hpp $(CSRC)/device_math.hpp
 	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
@@ -152,7 +160,7 @@ tests/hostcheck/libpairstatecheck.so: tests/hostcheck/pairstatecheck.cpp $(CSRC)
 	g++ -O2 -std=c++17 -Wall -fPIC -shared -o $@ $<
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
+	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all ab oracle hostcheck fakeccl clean

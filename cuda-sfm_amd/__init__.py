@@ -52,6 +52,7 @@ POSE_REFERENCE, POSE_CORRECT = 0, 1
  BUF_ECAND, BUF_PIND, BUF_REFINED_POSE, BUF_REFINED_POINTS, BUF_REPROJ, BUF_VIEW_POSE, BUF_VIEW_COUNTS, BUF_VIEW_REPROJ) = range(19)
 REFINE_CONVERGED, REFINE_MAX_ITER, REFINE_DEGENERATE = 0, 1, 2         # sfm_refine_report.status, sfm_register_report.status
 VP_UNSEEN, VP_NEW, VP_REFINED, VP_NEW_REJECTED, VP_KEPT = range(5)     # sfm_view_points_out.d_flags
+ADJ_VIEW1, ADJ_VIEW2, ADJ_VIEW3 = 1, 2, 4                              # bits of sfm_adjust_out.d_views
 
 SIFT_DTYPE = np.dtype([
     ("xpos", "<f4"), ("ypos", "<f4"), ("scale", "<f4"), ("sharpness", "<f4"),
@@ -78,6 +79,7 @@ EXPORTS = [
     "sfm_register_default_params", "sfm_register_view", "sfm_register_views", "sfm_get_register_report", "sfm_get_view_pose", "sfm_get_view_errors",
     "sfm_get_view_counts",
     "sfm_view_points_default_params", "sfm_triangulate_view", "sfm_triangulate_views",
+    "sfm_adjust_default_params", "sfm_adjust_view", "sfm_adjust_views",
 ]
 AB_EXPORTS = ["sfm_ransac_last_phases", "sfm_ransac_last_trace", "sfm_prefilter_probe", "sfm_prefilter_band_probe"]      # include/sfm_amd_ab.h
 if AB:
@@ -131,6 +133,29 @@ class ViewPointsParams(C.Structure):
 class ViewPointsOut(C.Structure):
     """sfm_view_points_out (include/sfm_amd.h): the caller's device buffers."""
     _fields_ = [("d_points", C.c_void_p), ("d_flags", C.c_void_p), ("d_err", C.c_void_p), ("d_counts", C.c_void_p)]
+
+
+class AdjustParams(C.Structure):
+    """sfm_adjust_params (include/sfm_amd.h)."""
+    _fields_ = [("max_iterations", C.c_int32), ("huber_px", C.c_float), ("min_rel_decrease", C.c_float), ("initial_lambda", C.c_float),
+                ("d_used2", C.c_void_p), ("d_poses", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class AdjustIn(C.Structure):
+    """sfm_adjust_in (include/sfm_amd.h): what sfm_triangulate_view read and wrote."""
+    _fields_ = [("d_sift", C.c_void_p), ("d_points", C.c_void_p), ("d_flags", C.c_void_p)]
+
+
+class AdjustReport(C.Structure):
+    """sfm_adjust_report (include/sfm_amd.h)."""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("accepted", C.c_int32), ("num_points", C.c_int32),
+                ("num_view2", C.c_int32), ("num_view3", C.c_int32), ("initial_rms_px", C.c_float), ("final_rms_px", C.c_float),
+                ("final_cost", C.c_float), ("lambda", C.c_float)]
+
+
+class AdjustOut(C.Structure):
+    """sfm_adjust_out (include/sfm_amd.h): the caller's device buffers."""
+    _fields_ = [("d_poses", C.c_void_p), ("d_points", C.c_void_p), ("d_views", C.c_void_p), ("d_err", C.c_void_p), ("d_report", C.c_void_p)]
 
 
 _vp = C.c_void_p
@@ -218,6 +243,10 @@ _lib.sfm_view_points_default_params.argtypes = [C.POINTER(ViewPointsParams)]
 _lib.sfm_view_points_default_params.restype = None
 _lib.sfm_triangulate_view.argtypes = [_vp, _vp, C.POINTER(ViewPointsParams), C.POINTER(ViewPointsOut)]
 _lib.sfm_triangulate_views.argtypes = [C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.POINTER(ViewPointsParams), C.POINTER(ViewPointsOut)]
+_lib.sfm_adjust_default_params.argtypes = [C.POINTER(AdjustParams)]
+_lib.sfm_adjust_default_params.restype = None
+_lib.sfm_adjust_view.argtypes = [_vp, C.POINTER(AdjustIn), C.POINTER(AdjustParams), C.POINTER(AdjustOut)]
+_lib.sfm_adjust_views.argtypes = [C.POINTER(_vp), C.c_int, C.POINTER(AdjustIn), C.POINTER(AdjustParams), C.POINTER(AdjustOut)]
 if AB:
     _lib.sfm_ransac_last_phases.argtypes = [_vp, C.POINTER(C.c_uint64)]
     _lib.sfm_ransac_last_trace.argtypes = [_vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_size_t)]
@@ -404,6 +433,68 @@ def triangulate_views(pairs, d_sifts, **kw):
     triangulate_views_enqueue(pairs, d_sifts, view_points_params(**kw), outs)
     pairs[0].ctx.synchronize()
     return [tuple(t.cpu().numpy() for t in out) for out in outs]
+
+
+_ADJUST_FIELDS = {f for f, _ in AdjustParams._fields_}
+
+
+def adjust_params(**kw):
+    """sfm_adjust_params with the library's defaults (20 iterations, Huber 1 px, 1e-6, lambda 1e-3), fields overridden by kw
+    (used2 / poses: device tensors / pointers)."""
+    p = AdjustParams()
+    _lib.sfm_adjust_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k in ("used2", "d_used2"):
+            p.d_used2 = _ptr(v)
+        elif k in ("poses", "d_poses"):
+            p.d_poses = _ptr(v)
+        elif k == "reserved":
+            for i, x in enumerate(v):
+                p.reserved[i] = int(x)
+        elif k in _ADJUST_FIELDS:
+            setattr(p, k, v)
+        else:
+            raise TypeError(f"adjust_params: no field {k!r} in sfm_adjust_params")
+    return p
+
+
+def _adjust_buffers(torch, device, n):
+    """Output tensors of one adjust_view call: poses 24, points 4 x n, views, err, report (bytes)."""
+    return (torch.empty(24, dtype=torch.float32, device=device), torch.empty((4, n), dtype=torch.float32, device=device),
+            torch.empty(n, dtype=torch.uint8, device=device), torch.empty(n, dtype=torch.float32, device=device),
+            torch.empty(C.sizeof(AdjustReport), dtype=torch.uint8, device=device))
+
+
+def _adjust_results(outs):
+    """(poses, points, views, err, report) tensors -> numpy arrays and the report as a dict."""
+    poses, points, views, err, rep = (t.cpu().numpy() for t in outs)
+    r = AdjustReport.from_buffer_copy(rep.tobytes())
+    return poses, points, views, err, {f: getattr(r, f) for f, _ in AdjustReport._fields_}
+
+
+def adjust_views_enqueue(pairs, ins, params, outs):
+    """sfm_adjust_views (enqueue only): ImagePair.adjust_view_enqueue for every pair of the list (one Context, none twice, each
+    refined and registered) in three launches.  ins: one (d_sift, points, flags) tuple per pair; outs: one (poses, points, views,
+    err, report) tuple of device tensors / pointers per pair (err may be None); params.d_used2 / d_poses must stay unset."""
+    n = len(pairs)
+    assert len(ins) == n and len(outs) == n, "one input set and one output set per pair"
+    handles = (_vp * n)(*[p._h.value for p in pairs])
+    i = (AdjustIn * n)(*[AdjustIn(*[_ptr(t) for t in x]) for x in ins])
+    o = (AdjustOut * n)(*[AdjustOut(*[_ptr(t) for t in x]) for x in outs])
+    _check(_lib.sfm_adjust_views(handles, n, i, C.byref(params), o), "sfm_adjust_views")
+
+
+def adjust_views(pairs, ins, **kw):
+    """ImagePair.adjust_view for a list of pairs in one batched call; kw are AdjustParams fields, the same for every pair.
+    Returns one (poses 24, points 4 x n, views, err, report dict) tuple per pair: one wait for the device."""
+    if not pairs:
+        adjust_views_enqueue([], [], adjust_params(**kw), [])
+        return []
+    dev = torch.device("cuda", pairs[0].ctx.device)
+    outs = [_adjust_buffers(torch, dev, p.num_points) for p in pairs]
+    adjust_views_enqueue(pairs, ins, adjust_params(**kw), outs)
+    pairs[0].ctx.synchronize()
+    return [_adjust_results(out) for out in outs]
 
 
 def sift_temp_layout(width, height, num_octaves=5, scale_up=False):
@@ -755,6 +846,24 @@ class ImagePair:
         self.triangulate_view_enqueue(d_sift, view_points_params(**kw), *outs)
         self.ctx.synchronize()
         return tuple(t.cpu().numpy() for t in outs)
+
+    # -- both cameras and the points adjusted over the pair's three views -------------------------------
+    def adjust_view_enqueue(self, d_sift, points, flags, params, out_poses, out_points, out_views, out_err, out_report):
+        """sfm_adjust_view with an AdjustParams (enqueue only): d_sift, points (4 x n) and flags (n) are what triangulate_view
+        read and wrote; out_poses (24 float32), out_points (4 x n), out_views (n uint8), out_err (n float32, optional) and
+        out_report (sizeof(AdjustReport) bytes) are the caller's device tensors / pointers.  Nothing in the pair changes."""
+        i = AdjustIn(_ptr(d_sift), _ptr(points), _ptr(flags))
+        o = AdjustOut(_ptr(out_poses), _ptr(out_points), _ptr(out_views), _ptr(out_err), _ptr(out_report))
+        _check(_lib.sfm_adjust_view(self._h, C.byref(i), C.byref(params), C.byref(o)), "sfm_adjust_view")
+
+    def adjust_view(self, d_sift, points, flags, **kw):
+        """Bundle adjustment of cameras 2 and 3 and of every used point over views 1, 2 and the registered view: points / flags
+        are triangulate_view's outputs (device tensors); kw are AdjustParams fields (used2 / poses: device tensors).  Returns
+        (poses 24 = [R|t] of cameras 2 and 3, points 4 x n, views, err px, report dict) as numpy (synchronises)."""
+        outs = _adjust_buffers(torch, torch.device("cuda", self.ctx.device), self.num_points)
+        self.adjust_view_enqueue(d_sift, points, flags, adjust_params(**kw), *outs)
+        self.ctx.synchronize()
+        return _adjust_results(outs)
 
     # -- accessors --------------------------------------------------------------------------------
     def device_ptr(self, which):

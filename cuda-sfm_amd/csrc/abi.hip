@@ -220,6 +220,7 @@ static int ctx_destroy_now(sfm_ctx *ctx)
     job_array_free(ctx->refine_jobs);
     job_array_free(ctx->register_jobs);
     job_array_free(ctx->view_points_jobs);
+    job_array_free(ctx->adjust_jobs);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     for (auto &t : ctx->tev) for (hipEvent_t e : t) if (e) (void)hipEventDestroy(e);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -555,7 +556,7 @@ int sfm_pair_destroy(sfm_pair *p)
     void *bufs[] = { p->d_K, p->d_Kinv, p->d_U[0], p->d_U[1], p->d_X[0], p->d_X[1], p->d_pts4, p->d_E, p->d_P, p->d_Pinv, p->d_Pind,
                      p->d_points, p->d_mask, p->d_key, p->d_best, p->d_counts, p->d_Ecand, p->d_clk, p->d_tick,
                      p->alt_counts, p->alt_Ecand, p->alt_tick, p->alt_key, p->d_pf, p->alt_pf, p->d_bound, p->d_cells, p->d_pts4s, p->d_tile_boxes, p->d_buckets,
-                     p->d_rstate, p->d_rpoints, p->d_rreproj, p->d_rwork, p->d_vstate, p->d_vreproj, p->d_vwork, p->d_vhyp, p->d_vcounts };
+                     p->d_rstate, p->d_rpoints, p->d_rreproj, p->d_rwork, p->d_vstate, p->d_vreproj, p->d_vwork, p->d_vhyp, p->d_vcounts, p->d_awork };
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (p->pipe_stream) { (void)hipStreamSynchronize(p->pipe_stream); (void)hipStreamDestroy(p->pipe_stream); }
     for (hipEvent_t e : p->pipe_final) if (e) (void)hipEventDestroy(e);
@@ -1151,6 +1152,156 @@ int sfm_triangulate_views(sfm_pair *const *pairs, int num_pairs, const sfm_sift_
     std::vector<ViewPointsInputs> in((size_t)num_pairs);
     for (int i = 0; i < num_pairs; ++i) in[(size_t)i] = view_points_inputs(pairs[i], d_sifts[i], *p);
     return launch_view_points_views(ctx, pairs, num_pairs, in.data(), *p, outs);
+}
+
+// ---- cameras 2 and 3 and the points adjusted over the pair's three views (adjust.hip) --------------
+void sfm_adjust_default_params(sfm_adjust_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->max_iterations = 20;
+    p->huber_px = 1.0f;
+    p->min_rel_decrease = 1e-6f;
+    p->initial_lambda = 1e-3f;
+}
+
+// The checks of one (in, out) set that need no device: required pointers, the alignment of d_sift, and no output on top of an
+// input or of another output.  n: the pair's record count, or 0 where the pair has not been looked at yet -- then the arrays
+// that grow with n count as one byte (the same address is caught, and anything inside the poses or the report).
+// who: "" or "pairs[i]: ".
+static int check_adjust_buffers(const sfm_adjust_in &in, const sfm_adjust_params &p, const sfm_adjust_out &out, int n, const char *who)
+{
+    SFM_REQUIRE(in.d_sift && in.d_points && in.d_flags, SFM_E_INVALID, "%ssfm_adjust_in.d_sift, d_points and d_flags are required", who);
+    SFM_REQUIRE(out.d_poses && out.d_points && out.d_views && out.d_report, SFM_E_INVALID,
+                "%ssfm_adjust_out.d_poses, d_points, d_views and d_report are required", who);
+    SFM_REQUIRE((reinterpret_cast<uintptr_t>(in.d_sift) & 15) == 0, SFM_E_INVALID,
+                "%sd_sift must be 16-byte aligned (the records are read with 16-byte loads)", who);
+    struct Range { const void *p; size_t bytes; const char *name; };
+    const size_t np = (size_t)n;
+    auto len = [np](size_t per_record) { return np ? np * per_record : (size_t)1; };
+    const Range ins[] = { { in.d_sift, len(sizeof(sfm_sift_point)), "in.d_sift" }, { in.d_points, len(16), "in.d_points" }, { in.d_flags, len(1), "in.d_flags" },
+                          { p.d_used2, len(1), "params.d_used2" }, { p.d_poses, 24 * sizeof(float), "params.d_poses" } };
+    const Range outs[] = { { out.d_poses, 24 * sizeof(float), "out.d_poses" }, { out.d_points, len(16), "out.d_points" }, { out.d_views, len(1), "out.d_views" },
+                           { out.d_err, len(4), "out.d_err" }, { out.d_report, sizeof(sfm_adjust_report), "out.d_report" } };
+    auto overlap = [](const Range &x, const Range &y) {
+        if (!x.p || !y.p) return false;
+        const uintptr_t a = reinterpret_cast<uintptr_t>(x.p), b = reinterpret_cast<uintptr_t>(y.p);
+        return a < b + y.bytes && b < a + x.bytes;
+    };
+    for (size_t o = 0; o < sizeof(outs) / sizeof(outs[0]); ++o) {
+        for (const Range &i : ins) SFM_REQUIRE(!overlap(outs[o], i), SFM_E_INVALID, "%s%s overlaps %s", who, outs[o].name, i.name);
+        for (size_t q = o + 1; q < sizeof(outs) / sizeof(outs[0]); ++q)
+            SFM_REQUIRE(!overlap(outs[o], outs[q]), SFM_E_INVALID, "%s%s overlaps %s", who, outs[o].name, outs[q].name);
+    }
+    return SFM_OK;
+}
+
+// the adjustment's work buffer, allocated at the first call and sized to the creation-time count
+static int adjust_buffers(sfm_pair *pair)
+{
+    if (pair->d_awork) return SFM_OK;
+    return alloc_group({ { &pair->d_awork, adjust_work_bytes(pair->cap_points) } });
+}
+
+// the inputs a call reads where the caller gave none: the refinement's used flags, the refined pose, the view's refined pose
+static AdjustInputs adjust_inputs(const sfm_pair *pair, const sfm_adjust_in &in, const sfm_adjust_params &p)
+{
+    AdjustInputs r;
+    r.sift = in.d_sift; r.points = in.d_points; r.flags = in.d_flags;
+    r.used2 = p.d_used2 ? p.d_used2 : reproj_flags(pair, pair->d_rreproj);
+    r.pose2 = p.d_poses ? p.d_poses : pair->d_rstate + refine_pose_offset();
+    r.pose3 = p.d_poses ? p.d_poses + 12 : pair->d_vstate + register_pose_offset();
+    r.pose_rows = p.d_poses ? 3 : 4;
+    return r;
+}
+
+int sfm_adjust_view(sfm_pair *pair, const sfm_adjust_in *in, const sfm_adjust_params *p, const sfm_adjust_out *out)
+{
+    SFM_REQUIRE(pair && in && p && out, SFM_E_INVALID, "null argument");
+    int rc = check_lm_params(*p, "sfm_adjust_params");
+    if (rc != SFM_OK) return rc;
+    rc = check_adjust_buffers(*in, *p, *out, 0, "");
+    if (rc != SFM_OK) return rc;
+    SFM_FLUSH(pair);
+    SFM_NEED(pair, kPoints | ((p->d_used2 && p->d_poses) ? 0u : (uint32_t)kRefined) | (p->d_poses ? 0u : (uint32_t)kView));
+    rc = check_adjust_buffers(*in, *p, *out, pair->n, "");                                  // the same with the arrays' real lengths
+    if (rc != SFM_OK) return rc;
+    SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
+    rc = adjust_buffers(pair);
+    if (rc != SFM_OK) return rc;
+    return launch_adjust(pair, adjust_inputs(pair, *in, *p), *p, *out);                    // reads the pair: no stage changes
+}
+
+int sfm_adjust_views(sfm_pair *const *pairs, int num_pairs, const sfm_adjust_in *ins, const sfm_adjust_params *p, const sfm_adjust_out *outs)
+{
+    // the checks that need no device first, all of them before anything is enqueued
+    SFM_REQUIRE(p, SFM_E_INVALID, "null params");
+    SFM_REQUIRE(num_pairs >= 0 && num_pairs <= 65535, SFM_E_INVALID, "num_pairs %d outside 0..65535", num_pairs);
+    SFM_REQUIRE(!p->d_used2 && !p->d_poses, SFM_E_INVALID,
+                "sfm_adjust_params.d_used2 / d_poses must be null here: every pair reads its own refinement and registration");
+    int rc = check_lm_params(*p, "sfm_adjust_params");
+    if (rc != SFM_OK) return rc;
+    if (num_pairs == 0) return SFM_OK;
+    SFM_REQUIRE(pairs && ins && outs, SFM_E_INVALID, "null pair list, ins list or outs list");
+    for (int i = 0; i < num_pairs; ++i) {
+        SFM_REQUIRE(pairs[i], SFM_E_INVALID, "pairs[%d] is null", i);
+        char who[32];
+        snprintf(who, sizeof(who), "pairs[%d]: ", i);
+        rc = check_adjust_buffers(ins[i], *p, outs[i], 0, who);
+        if (rc != SFM_OK) return rc;
+    }
+    sfm_ctx *ctx = pairs[0]->ctx;
+    for (int i = 1; i < num_pairs; ++i) SFM_REQUIRE(pairs[i]->ctx == ctx, SFM_E_INVALID, "pairs[%d] belongs to another context than pairs[0]", i);
+    {
+        std::vector<std::pair<const sfm_pair *, int>> sorted((size_t)num_pairs);
+        for (int i = 0; i < num_pairs; ++i) sorted[(size_t)i] = { pairs[i], i };
+        std::sort(sorted.begin(), sorted.end());
+        for (int k = 1; k < num_pairs; ++k)
+            SFM_REQUIRE(sorted[(size_t)k].first != sorted[(size_t)k - 1].first, SFM_E_INVALID,
+                        "pairs[%d]: the pair is listed twice (two blocks would write the same work buffer)", sorted[(size_t)k].second);
+    }
+    for (int i = 0; i < num_pairs; ++i) SFM_FLUSH(pairs[i]);
+    const uint32_t need = kPoints | kRefined | kView;
+    for (int i = 0; i < num_pairs; ++i)
+        SFM_REQUIRE(pairs[i]->state.has(need), SFM_E_STATE, "pairs[%d]: %s", i, pair_stage_hint(pairs[i]->state.missing(need)));
+    for (int i = 0; i < num_pairs; ++i) {
+        char who[32];
+        snprintf(who, sizeof(who), "pairs[%d]: ", i);
+        rc = check_adjust_buffers(ins[i], *p, outs[i], pairs[i]->n, who);                   // the same with the arrays' real lengths
+        if (rc != SFM_OK) return rc;
+    }
+    {
+        // across pairs: the blocks of different pairs run at the same time, so no output may lie on an output or an input of
+        // another pair either (inputs may be shared).  All ranges sorted by their start, one sweep.
+        struct Range { uintptr_t lo, hi; int pair; bool out; };
+        std::vector<Range> r;
+        r.reserve((size_t)num_pairs * 8);
+        auto add = [&r](const void *q, size_t bytes, int i, bool out) {
+            if (q && bytes) r.push_back({ reinterpret_cast<uintptr_t>(q), reinterpret_cast<uintptr_t>(q) + bytes, i, out });
+        };
+        for (int i = 0; i < num_pairs; ++i) {
+            const size_t np = (size_t)pairs[i]->n;
+            add(ins[i].d_sift, np * sizeof(sfm_sift_point), i, false); add(ins[i].d_points, 16 * np, i, false); add(ins[i].d_flags, np, i, false);
+            add(outs[i].d_poses, 24 * sizeof(float), i, true); add(outs[i].d_points, 16 * np, i, true); add(outs[i].d_views, np, i, true);
+            add(outs[i].d_err, 4 * np, i, true); add(outs[i].d_report, sizeof(sfm_adjust_report), i, true);
+        }
+        std::sort(r.begin(), r.end(), [](const Range &x, const Range &y) { return x.lo < y.lo; });
+        const Range *far_any = nullptr, *far_out = nullptr;     // the ranges seen so far that end last: any, and among the outputs
+        for (const Range &x : r) {
+            const Range *hit = x.out ? far_any : far_out;
+            if (hit && hit->hi > x.lo && hit->pair != x.pair) {
+                const int later = x.pair > hit->pair ? x.pair : hit->pair, other = x.pair > hit->pair ? hit->pair : x.pair;
+                SFM_REQUIRE(false, SFM_E_INVALID, "pairs[%d]: a buffer overlaps a buffer of pairs[%d], and one of the two is an output", later, other);
+            }
+            if (!far_any || x.hi > far_any->hi) far_any = &x;
+            if (x.out && (!far_out || x.hi > far_out->hi)) far_out = &x;
+        }
+    }
+    SFM_HIP_TRY(hipSetDevice(ctx->device));
+    for (int i = 0; i < num_pairs; ++i) { rc = adjust_buffers(pairs[i]); if (rc != SFM_OK) return rc; }
+    std::vector<AdjustInputs> in((size_t)num_pairs);
+    for (int i = 0; i < num_pairs; ++i) in[(size_t)i] = adjust_inputs(pairs[i], ins[i], *p);
+    return launch_adjust_views(ctx, pairs, num_pairs, in.data(), *p, outs);
 }
 
 // ---- accessors ------------------------------------------------------------------------------------

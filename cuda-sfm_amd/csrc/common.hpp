@@ -188,8 +188,8 @@ struct sfm_ctx {
     void *batch_ws = nullptr;          // sfm_process_pairs, batched path: the PairJob array + every pair's buffers (pairs_batch.hpp)
     size_t batch_ws_bytes = 0;
     // sfm_refine_pairs / sfm_register_views / sfm_triangulate_views: the RefineArgs (refine.hip) / RegisterArgs (register.hip) /
-    // ViewPointsArgs (view_points.hip) of a call
-    sfm::JobArray refine_jobs, register_jobs, view_points_jobs;
+    // ViewPointsArgs (view_points.hip) of a call; sfm_adjust_views: the AdjustArgs (adjust.hip)
+    sfm::JobArray refine_jobs, register_jobs, view_points_jobs, adjust_jobs;
     void *sift_job = nullptr;          // the extraction in flight (sift.hip: SiftJob), sfm_extract_sift_begin .. _end
     // kernels that already opted in to > 64 KiB of dynamic LDS on THIS context's device (function attributes are
     // per device; a context is used by one host thread at a time, so no process-wide flag)
@@ -289,6 +289,8 @@ struct sfm_pair {
     int *d_vcounts = nullptr;          // per hypothesis: inlier count
     size_t cap_vhyps = 0;
     uint32_t view_hyps = 0;            // num_hypotheses of the last registration
+    // sfm_adjust_view: allocated at the first call, sized to cap_points (adjust.hip)
+    void *d_awork = nullptr;           // per record: observations, start point, compact index; per used record: the same, compacted, and the points
     int last_kernel = 0, last_grid = 0, last_block = 0, last_lds = 0;
 };
 
@@ -367,6 +369,14 @@ int launch_view_points(sfm_pair *pair, const ViewPointsInputs &in, const sfm_vie
 // the same for many pairs of one context in one launch (grid = point blocks x pairs)
 int launch_view_points_views(sfm_ctx *ctx, sfm_pair *const *pairs, int num_pairs, const ViewPointsInputs *in, const sfm_view_points_params &p,
                              const sfm_view_points_out *outs);
+
+// adjust.hip: cameras 2 and 3 and the used points adjusted over the pair's three views; d_used2 / d_poses resolved by the caller
+// (pose_rows as in ViewPointsInputs)
+struct AdjustInputs { const sfm_sift_point *sift; const float *points; const uint8_t *flags, *used2; const float *pose2, *pose3; int pose_rows; };
+int launch_adjust(sfm_pair *pair, const AdjustInputs &in, const sfm_adjust_params &p, const sfm_adjust_out &out);      // gather (grid), LM solve (one block), scatter (grid)
+// the same three stages for many pairs of one context in three launches
+int launch_adjust_views(sfm_ctx *ctx, sfm_pair *const *pairs, int num_pairs, const AdjustInputs *in, const sfm_adjust_params &p, const sfm_adjust_out *outs);
+size_t adjust_work_bytes(int cap_points);                         // bytes of pair->d_awork
 
 // sift.hip
 void sift_layout(int width, int height, int num_octaves, int scale_up, sfm_sift_layout *L);

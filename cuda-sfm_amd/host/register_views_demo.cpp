@@ -5,8 +5,10 @@
 // The feature sets come from files of raw SiftPoint records (as two_view_demo reads them), three per triple:
 //     register_views_demo <refine_iterations> <a1.bin> <a2.bin> <a3.bin> [<b1.bin> <b2.bin> <b3.bin> ...]
 //   then ONE triangulate_views over all of them: every pair's points over its three views.
-// Two lines per triple: the view3 and view3 points lines sfm_main prints for that triple alone (same camera, same settings, the
-// same refine_iterations).
+//   then ONE adjust_views over all of them (both cameras and the points over the three views), and per triple one more
+//   triangulateView with its adjusted cameras.
+// Four lines per triple: the view3, view3 points, adjust and adjusted view3 points lines sfm_main prints for that triple alone
+// (same camera, same settings, the same refine_iterations).
 // Plain C++: needs only the facade headers and libsfm_amd.so.
 #include <algorithm>
 #include <cmath>
@@ -75,6 +77,7 @@ int main(int argc, char **argv)
     }
     const std::vector<sfm_register_report> reports = SfM::register_views(pairs.data(), records.data(), count);
     const std::vector<SfM::ViewPoints> clouds = SfM::triangulate_views(pairs.data(), records.data(), count);
+    const std::vector<SfM::ViewAdjust> adjusted = SfM::adjust_views(pairs.data(), records.data(), clouds.data(), count);
     for (int k = 0; k < count; ++k) {
         const sfm_register_report &vr = reports[(size_t)k];
         float P3[16];
@@ -88,6 +91,12 @@ int main(int argc, char **argv)
                     vr.final_rms_px, std::sqrt(nc));
         const int32_t *c = clouds[(size_t)k].counts;
         std::printf("view3 points: %d new, %d refined, %d kept, %d rejected\n", c[SFM_VP_NEW], c[SFM_VP_REFINED], c[SFM_VP_KEPT], c[SFM_VP_NEW_REJECTED]);
+        const SfM::ViewAdjust &adj = adjusted[(size_t)k];
+        std::printf("adjust: %d points (%d / %d in views 2 / 3), rms %.4f -> %.4f px, %d iterations\n", adj.report.num_points, adj.report.num_view2,
+                    adj.report.num_view3, adj.report.initial_rms_px, adj.report.final_rms_px, adj.report.iterations);
+        const SfM::ViewPoints again = pairs[(size_t)k]->triangulateView(records[(size_t)k], 5, 4.0f, 1.0f, adj.poses);
+        std::printf("adjusted view3 points: %d new, %d refined, %d kept, %d rejected\n", again.counts[SFM_VP_NEW], again.counts[SFM_VP_REFINED],
+                    again.counts[SFM_VP_KEPT], again.counts[SFM_VP_NEW_REJECTED]);
     }
     owned.clear();
     for (SiftData &s : sift) FreeSiftData(s);

@@ -30,7 +30,24 @@ struct ViewPoints {
     int32_t counts[8];                  // [0..4]: points per class
 };
 
+// what adjustView / adjust_views return for one pair, in host memory
+struct ViewAdjust {
+    float poses[24];                    // adjusted [R|t] of cameras 2 and 3: R (9, row-major) then t (3), each
+    std::vector<float> points;          // 4 x N: (X, Y, Z, 1) for used records, the input column otherwise
+    std::vector<uint8_t> views;         // N: bit 0 / 1 / 2 = views 1 / 2 / 3 used, 0 = record not used
+    sfm_adjust_report report;
+};
+
 namespace detail {
+// a device allocation that is freed when it goes out of scope, also when a facade call throws (SFM_FACADE_THROW)
+struct DeviceBlock {
+    char *p = nullptr;
+    explicit DeviceBlock(size_t bytes) { SFM_FACADE_CALL(sfm_device_alloc(sfm_facade::context(), bytes, reinterpret_cast<void **>(&p))); }
+    DeviceBlock(const DeviceBlock &) = delete;
+    DeviceBlock &operator=(const DeviceBlock &) = delete;
+    ~DeviceBlock() { if (p) sfm_device_free(sfm_facade::context(), p); }
+};
+
 // device scratch of one triangulation result: points, flags and counts in ONE sfm_device_alloc block
 struct ViewPointsScratch {
     char *block = nullptr;
@@ -60,6 +77,52 @@ struct ViewPointsScratch {
         SFM_FACADE_CALL(sfm_copy_to_host(sfm_facade::context(), r.points.data(), o.d_points, 16 * n));
         SFM_FACADE_CALL(sfm_copy_to_host(sfm_facade::context(), r.flags.data(), o.d_flags, n));
         SFM_FACADE_CALL(sfm_copy_to_host(sfm_facade::context(), r.counts, o.d_counts, 32));
+        return r;
+    }
+};
+// device scratch of one adjustment: the triangulation's points and flags uploaded, the outputs, in ONE sfm_device_alloc block
+struct AdjustScratch {
+    size_t n = 0;
+    DeviceBlock mem;
+    char *block = nullptr;
+    // vp must be the triangulation of this pair: 4 x num_points points and num_points flags (SFM_E_INVALID otherwise)
+    AdjustScratch(int num_points, const ViewPoints &vp) : n((size_t)num_points), mem(32 * n + 96 + 48 + 2 * flag_bytes()), block(mem.p)
+    {
+        if (vp.points.size() != 4 * n || vp.flags.size() != n)
+            sfm_facade::fail("adjustView: the ViewPoints do not have the pair's number of points", SFM_E_INVALID);
+        if (n) {
+            SFM_FACADE_CALL(sfm_copy_to_device(sfm_facade::context(), block, vp.points.data(), 16 * n));
+            SFM_FACADE_CALL(sfm_copy_to_device(sfm_facade::context(), block + 32 * n + 144, vp.flags.data(), n));
+        }
+    }
+    size_t flag_bytes() const { return (n + 16) / 16 * 16; }      // never 0: the flags and the view bits get addresses of their own
+    sfm_adjust_in in(const SiftPoint *data) const
+    {
+        sfm_adjust_in i;
+        i.d_sift = reinterpret_cast<const sfm_sift_point *>(data);
+        i.d_points = reinterpret_cast<const float *>(block);
+        i.d_flags = reinterpret_cast<const uint8_t *>(block + 32 * n + 144);
+        return i;
+    }
+    sfm_adjust_out out() const
+    {
+        sfm_adjust_out o;
+        o.d_points = reinterpret_cast<float *>(block + 16 * n);
+        o.d_poses = reinterpret_cast<float *>(block + 32 * n);
+        o.d_report = reinterpret_cast<sfm_adjust_report *>(block + 32 * n + 96);
+        o.d_views = reinterpret_cast<uint8_t *>(block + 32 * n + 144 + flag_bytes());
+        o.d_err = nullptr;
+        return o;
+    }
+    ViewAdjust download() const          // synchronises
+    {
+        ViewAdjust r;
+        r.points.resize(4 * n); r.views.resize(n);
+        const sfm_adjust_out o = out();
+        SFM_FACADE_CALL(sfm_copy_to_host(sfm_facade::context(), r.points.data(), o.d_points, 16 * n));
+        SFM_FACADE_CALL(sfm_copy_to_host(sfm_facade::context(), r.views.data(), o.d_views, n));
+        SFM_FACADE_CALL(sfm_copy_to_host(sfm_facade::context(), r.poses, o.d_poses, sizeof(r.poses)));
+        SFM_FACADE_CALL(sfm_copy_to_host(sfm_facade::context(), &r.report, o.d_report, sizeof(r.report)));
         return r;
     }
 };
@@ -192,7 +255,10 @@ public:
     }
     // the pair's points triangulated / refined over views 1, 2 and the registered view (sfm_triangulate_view): data = the
     // records registerView took; nothing in the pair changes; returns points, flags and counts (synchronises)
-    ViewPoints triangulateView(SiftPoint *data, int max_iterations = 5, float threshold_px = 4.0f, float min_parallax_deg = 1.0f)
+    // poses: null, or 24 floats in HOST memory -- [R|t] of cameras 2 and 3 as ViewAdjust::poses holds them -- instead of the
+    // refined pose and the registered view's
+    ViewPoints triangulateView(SiftPoint *data, int max_iterations = 5, float threshold_px = 4.0f, float min_parallax_deg = 1.0f,
+                               const float *poses = nullptr)
     {
         sfm_view_points_params p;
         sfm_view_points_default_params(&p);
@@ -201,7 +267,28 @@ public:
         p.min_parallax_deg = min_parallax_deg;
         const detail::ViewPointsScratch scratch(num_points_);
         const sfm_view_points_out out = scratch.out();
+        std::unique_ptr<detail::DeviceBlock> d_poses;
+        if (poses) {
+            d_poses.reset(new detail::DeviceBlock(24 * sizeof(float)));
+            SFM_FACADE_CALL(sfm_copy_to_device(sfm_facade::context(), d_poses->p, poses, 24 * sizeof(float)));
+            p.d_poses = reinterpret_cast<const float *>(d_poses->p);
+        }
         SFM_FACADE_CALL(sfm_triangulate_view(pair_, reinterpret_cast<const sfm_sift_point *>(data), &p, &out));
+        return scratch.download();
+    }
+    // both cameras and every used point adjusted over views 1, 2 and the registered view (sfm_adjust_view): data = the records
+    // registerView took, vp = what triangulateView returned for them; nothing in the pair changes; returns the adjusted poses,
+    // points, view bits and the report (synchronises)
+    ViewAdjust adjustView(SiftPoint *data, const ViewPoints &vp, int max_iterations = 20, float huber_px = 1.0f)
+    {
+        sfm_adjust_params p;
+        sfm_adjust_default_params(&p);
+        p.max_iterations = max_iterations;
+        p.huber_px = huber_px;
+        const detail::AdjustScratch scratch(num_points_, vp);
+        const sfm_adjust_in in = scratch.in(data);
+        const sfm_adjust_out out = scratch.out();
+        SFM_FACADE_CALL(sfm_adjust_view(pair_, &in, &p, &out));
         return scratch.download();
     }
     std::vector<float> getX(int image)      // 3 x N normalised coordinates of image 0 / 1
@@ -276,6 +363,31 @@ inline std::vector<ViewPoints> triangulate_views(Image_pair *const *pairs, SiftP
     }
     SFM_FACADE_CALL(sfm_triangulate_views(handles.data(), count, records.data(), &p, outs.data()));
     std::vector<ViewPoints> results;
+    for (int i = 0; i < count; ++i) results.push_back(scratch[(size_t)i]->download());
+    return results;
+}
+
+// adjustView for each of many pairs in one batched call (sfm_adjust_views): data[i] and vps[i] as adjustView takes them; returns
+// one result per pair in the order of the list, each as its own adjustView() gives it
+inline std::vector<ViewAdjust> adjust_views(Image_pair *const *pairs, SiftPoint *const *data, const ViewPoints *vps, int count,
+                                            int max_iterations = 20, float huber_px = 1.0f)
+{
+    sfm_adjust_params p;
+    sfm_adjust_default_params(&p);
+    p.max_iterations = max_iterations;
+    p.huber_px = huber_px;
+    std::vector<sfm_pair *> handles;
+    std::vector<std::unique_ptr<detail::AdjustScratch>> scratch;
+    std::vector<sfm_adjust_in> ins;
+    std::vector<sfm_adjust_out> outs;
+    for (int i = 0; i < count; ++i) {
+        handles.push_back(pairs[i] ? pairs[i]->handle() : nullptr);
+        scratch.emplace_back(new detail::AdjustScratch(pairs[i] ? pairs[i]->numPoints() : 0, vps[i]));
+        ins.push_back(scratch.back()->in(data[i]));
+        outs.push_back(scratch.back()->out());
+    }
+    SFM_FACADE_CALL(sfm_adjust_views(handles.data(), count, ins.data(), &p, outs.data()));
+    std::vector<ViewAdjust> results;
     for (int i = 0; i < count; ++i) results.push_back(scratch[(size_t)i]->download());
     return results;
 }

@@ -10,7 +10,10 @@
 // against it, P3P RANSAC + pose LM); one more line: inliers / candidates, rms before -> after, |C3| = |-R3^T t3|.  Then the pair's
 // points are triangulated / refined over the three views; one more line: view3 points: <new> new, <refined> refined, <kept> kept,
 // <rejected> rejected; the PLY is then written again with the merged cloud (new and refined points from the three-view result, the
-// rest as before) and a last line says so: merged cloud: <count> points -> <file>.
+// rest as before) and a last line says so: merged cloud: <count> points -> <file>.  In front of that line both cameras and the
+// points are adjusted over the three views (sfm_adjust_view) and the points triangulated once more with the adjusted cameras; two
+// lines: adjust: <points> points (<v2> / <v3> in views 2 / 3), rms <a> -> <b> px, <k> iterations, and adjusted view3 points:
+// with the four counts again.  The PLY holds the records of the first triangulation at their adjusted positions.
 // result.bin (optional, for tests): int n, float E[9], int pose, uint hyp, uint count, float P[16] (chosen), float pts[4n], u8 mask[n]
 // Plain C++: facade headers + libsfm_amd.so only (no OpenCV, no GL).
 #include <cmath>
@@ -124,10 +127,18 @@ int main(int argc, char **argv)
         const SfM::ViewPoints cloud = sfm.triangulateView(siftData1.d_data);
         std::printf("view3 points: %d new, %d refined, %d kept, %d rejected\n", cloud.counts[SFM_VP_NEW], cloud.counts[SFM_VP_REFINED],
                     cloud.counts[SFM_VP_KEPT], cloud.counts[SFM_VP_NEW_REJECTED]);
+        const SfM::ViewAdjust adj = sfm.adjustView(siftData1.d_data, cloud);
+        std::printf("adjust: %d points (%d / %d in views 2 / 3), rms %.4f -> %.4f px, %d iterations\n", adj.report.num_points, adj.report.num_view2,
+                    adj.report.num_view3, adj.report.initial_rms_px, adj.report.final_rms_px, adj.report.iterations);
+        const SfM::ViewPoints again = sfm.triangulateView(siftData1.d_data, 5, 4.0f, 1.0f, adj.poses);
+        std::printf("adjusted view3 points: %d new, %d refined, %d kept, %d rejected\n", again.counts[SFM_VP_NEW], again.counts[SFM_VP_REFINED],
+                    again.counts[SFM_VP_KEPT], again.counts[SFM_VP_NEW_REJECTED]);
         std::vector<uint8_t> keep(used);
         for (int32_t j = 0; j < n; ++j)
             if (cloud.flags[(size_t)j] == SFM_VP_NEW || cloud.flags[(size_t)j] == SFM_VP_REFINED) keep[(size_t)j] = 1;
-        const int merged = WritePLY(argv[3], cloud.points.data(), n, keep.data());      // replaces the two-view file written above
+        // the records are those of the first triangulation; their positions are the adjusted ones (a record the adjustment did not
+        // use keeps the triangulation's column, and so does every record when the adjustment is degenerate)
+        const int merged = WritePLY(argv[3], adj.points.data(), n, keep.data());        // replaces the two-view file written above
         std::printf("merged cloud: %d points -> %s\n", merged, argv[3]);
         FreeSiftData(siftData3);
     }

@@ -447,6 +447,56 @@ int sfm_triangulate_view(sfm_pair *pair, const sfm_sift_point *d_sift, const sfm
 int sfm_triangulate_views(sfm_pair *const *pairs, int num_pairs, const sfm_sift_point *const *d_sifts,
                           const sfm_view_points_params *p, const sfm_view_points_out *outs);     /* enqueue only */
 
+/* ---- adjusting both cameras and all points over the pair's three views ---------------------------
+ * A Levenberg-Marquardt bundle adjustment over views 1, 2 and the registered view: camera 1 stays [I|0]; camera 2 moves with the
+ * two-view refinement's 5 degrees of freedom (R <- exp([w]x) R, t on the unit sphere, which fixes the scale); camera 3 with the
+ * registration's 6 (R3 <- exp([w]x) R3, t3 <- t3 + dt); and the 3-D point of every used record.  Residuals (pixels), Huber loss,
+ * damping, accept test and stop rules are sfm_refine_two_view's.  in->d_points / in->d_flags are what sfm_triangulate_view wrote
+ * (SFM_VP_*), in->d_sift the same records (16-byte aligned).  View 3 sees a record whose flag is NEW or REFINED; view 2 sees it
+ * when its used2 flag is set and the flag is UNSEEN, REFINED or KEPT; view 1 always.  A record is used when view 2 or 3 sees it,
+ * its input column passes the registration's point test and X / W lies in front of every camera that sees it at the start poses.
+ * Fewer than 16 records in view 2 or fewer than 6 in view 3: SFM_REFINE_DEGENERATE -- the start poses and the input columns are
+ * returned with d_views filled; not an error.
+ * The call READS the pair and writes only the caller's buffers: no stage, buffer id or getter belongs to it. */
+typedef struct sfm_adjust_params {
+    int32_t max_iterations;            /* 0..200, 0 = evaluate the start only; default 20                                   */
+    float   huber_px, min_rel_decrease, initial_lambda;   /* 1.0 / 1e-6 / 1e-3, as sfm_refine_params                        */
+    const uint8_t *d_used2;            /* optional DEVICE uint8[num_points]: records with an observation in view 2; NULL = the
+                                          two-view refinement's used flags (needs the refinement)                           */
+    const float   *d_poses;            /* optional DEVICE float[24], layout of sfm_view_points_params.d_poses: the start; NULL =
+                                          the refined pose and the registered view's refined pose                           */
+    int32_t reserved[4];               /* must be zero (else SFM_E_INVALID)                                                */
+} sfm_adjust_params;
+typedef struct sfm_adjust_in {         /* DEVICE, all required */
+    const sfm_sift_point *d_sift;      /* view 1's records re-matched against view 3, 16-byte aligned                       */
+    const float   *d_points;           /* 4 x num_points: sfm_view_points_out.d_points                                      */
+    const uint8_t *d_flags;            /* num_points: sfm_view_points_out.d_flags                                           */
+} sfm_adjust_in;
+typedef struct sfm_adjust_report {
+    int32_t status;                    /* SFM_REFINE_*                                                                      */
+    int32_t iterations, accepted;
+    int32_t num_points, num_view2, num_view3;    /* used records; those view 2 / view 3 sees                                */
+    float   initial_rms_px, final_rms_px;        /* sqrt(sum of squares / (2 (num_points + num_view2 + num_view3)))         */
+    float   final_cost, lambda;
+} sfm_adjust_report;
+typedef struct sfm_adjust_out {        /* DEVICE buffers of the caller; none may overlap an input or another output          */
+    float   *d_poses;                  /* 24, required: adjusted [R|t] of cameras 2 and 3, the layout d_poses accepts        */
+    float   *d_points;                 /* 4 x num_points, required: (X, Y, Z, 1) for used records, the input column otherwise */
+    uint8_t *d_views;                  /* num_points, required: bit 0 / 1 / 2 = views 1 / 2 / 3 used, 0 = record not used    */
+    float   *d_err;                    /* num_points, optional: the largest pixel error over the record's views at the final
+                                          state, +inf where unused                                                          */
+    sfm_adjust_report *d_report;       /* required, DEVICE                                                                   */
+} sfm_adjust_out;
+void sfm_adjust_default_params(sfm_adjust_params *p);
+/* Needs points; the refinement unless d_used2 AND d_poses are given; the registration unless d_poses is given (SFM_E_STATE). */
+int sfm_adjust_view(sfm_pair *pair, const sfm_adjust_in *in, const sfm_adjust_params *p, const sfm_adjust_out *out);   /* enqueue only */
+/* The same for many pairs of ONE context in three launches: every outs[i] ends byte for byte as after sfm_adjust_view on
+ * pairs[i].  pairs, ins, outs: HOST arrays of num_pairs (0..65535) entries, no pair twice; p->d_used2 and p->d_poses must be
+ * NULL.  Every check precedes the launches: on SFM_E_INVALID / SFM_E_STATE (the text names the first offending pair) nothing
+ * is written. */
+int sfm_adjust_views(sfm_pair *const *pairs, int num_pairs, const sfm_adjust_in *ins, const sfm_adjust_params *p,
+                     const sfm_adjust_out *outs);                                                     /* enqueue only */
+
 /* ---- accessors (the reference keeps these private; needed for parity checks) ------------------ */
 #define SFM_BUF_X0      0   /* float 3 x ld   normalised coords image 1 (ld = sfm_pair_ld)   */
 #define SFM_BUF_X1      1
