@@ -29,11 +29,12 @@ SDEMO    := $(PKG)/host/sift_demo
 MAINAPP  := $(PKG)/host/sfm_main
 RPDEMO   := $(PKG)/host/refine_pairs_demo
 RVDEMO   := $(PKG)/host/register_views_demo
+APDEMO   := $(PKG)/host/align_pairs_demo
 
 IOTEST   := tests/cpp/io_test
 GEOMTEST := tests/cpp/geom_test
 
-all: $(LIB) $(LIB_AB) $(COMMLIB) $(BUILD)/ransac.s $(BUILD)/view_points.s oracle hostcheck fakeccl $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(IOTEST) $(GEOMTEST)
+all: $(LIB) $(LIB_AB) $(COMMLIB) $(BUILD)/ransac.s $(BUILD)/view_points.s oracle hostcheck fakeccl $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(APDEMO) $(IOTEST) $(GEOMTEST)
 
 # the product's objects come with the compiler's resource-usage report (registers, scratch, LDS of every kernel) next to them:
 # $(BUILD)/<source>.usage.txt, read by tests/test_register_budget.py; warnings and errors of the compile are still shown
@@ -69,6 +70,9 @@ FLAGS_match_fused := -fno-slp-vectorize
 # adjust.hip's solve kernel keeps both cameras in scalar registers: paired into v_pk_* the terms need scalar pairs that are moved and
 # spilled (256 VGPRs + 672 bytes of scratch with the vectoriser, no scratch without)
 FLAGS_adjust := -fno-slp-vectorize
+# align.hip's lane solve sits at the 64-register boundary with the vectoriser's register pairs (64 single, 66 batched: 7 waves per
+# SIMD instead of 8); without it the four kernels need 52 / 55 / 92 / 250 VGPRs, the batched ones the same as their twins
+FLAGS_align := -fno-slp-vectorize
 
 $(LIB): $(OBJS) $(CSRC)/exports.map
 	@mkdir -p $(PKG)/lib
@@ -106,6 +110,9 @@ $(RPDEMO): $(PKG)/host/refine_pairs_demo.cpp $(PKG)/host/sfm.h $(PKG)/host/sfm_i
 $(RVDEMO): $(PKG)/host/register_views_demo.cpp $(PKG)/host/sfm.h $(PKG)/host/sfm_io.h $(PKG)/host/cudaSift.h include/sfm_amd.h $(LIB)
 	g++ -O2 -std=c++14 -Wall -o $@ $< -L$(PKG)/lib -lsfm_amd -Wl,-rpath,'$$ORIGIN/../lib' -Wl,-rpath,/opt/rocm/lib
 
+$(APDEMO): $(PKG)/host/align_pairs_demo.cpp $(PKG)/host/sfm.h $(PKG)/host/sfm_io.h $(PKG)/host/cudaSift.h include/sfm_amd.h $(LIB)
+	g++ -O2 -std=c++14 -Wall -o $@ $< -L$(PKG)/lib -lsfm_amd -Wl,-rpath,'$$ORIGIN/../lib' -Wl,-rpath,/opt/rocm/lib
+
 $(IOTEST): tests/cpp/io_test.cpp $(PKG)/host/sfm_io.h $(PKG)/host/cudaSift.h include/sfm_amd.h
 	g++ -O2 -std=c++14 -Wall -o $@ $<
 
@@ -114,7 +121,7 @@ $(GEOMTEST): tests/cpp/geom_test.cpp $(PKG)/host/geomFuncs.h $(PKG)/host/sfm_io.
 
 # CPU-only: the host-compiled arithmetic check of the non-GPU tests (the fakeccl target, which needs the gfx950 build and the RCCL
 # header, is a target of its own and part of `all`)
-hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so
+hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so
 
 # TEST HARNESS: comm.cpp linked against a shared-memory stand-in for the nine RCCL calls it makes, so that a 1-GPU box can run the
 # exchange code with two real ranks (tests/test_gpu_fakeccl.py); the product's libsfm_amd_rccl.so is linked against librccl
@@ -146,6 +153,11 @@ tests/hostcheck/libviewpointscheck.so: tests/hostcheck/viewpointscheck.hip $(CSR
 tests/hostcheck/libadjustcheck.so: tests/hostcheck/adjustcheck.hip $(CSRC)/adjust_math.hpp $(CSRC)/view_points_math.hpp $(CSRC)/register_math.hpp $(CSRC)/refine_math.hpp $(CSRC)/device_math.hpp include/sfm_amd.h
 	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
 
+# the arithmetic of sfm_align_pair (align_math.hpp: gate, triad solver, two-way inlier test, Jacobians, step) and a serial driver
+# of the whole call, for tests/test_align_host.py and the comparison of tests/test_gpu_align.py
+tests/hostcheck/libaligncheck.so: tests/hostcheck/aligncheck.hip $(CSRC)/align_math.hpp $(CSRC)/view_points_math.hpp $(CSRC)/register_math.hpp $(CSRC)/refine_math.hpp $(CSRC)/device_math.hpp include/sfm_amd.h
+	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
+
 # the scoring block's dynamic LDS size (prefilter_lds.hpp), host-compiled for tests/test_register_budget.py
 tests/hostcheck/libpfldscheck.so: tests/hostcheck/pfldscheck.hip $(CSRC)/prefilter_lds.hpp $(CSRC)/prefilter_record.hpp $(CSRC)/prefilter_math.hpp $(CSRC)/device_math.hpp
 	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
@@ -160,7 +172,7 @@ tests/hostcheck/libpairstatecheck.so: tests/hostcheck/pairstatecheck.cpp $(CSRC)
 	g++ -O2 -std=c++17 -Wall -fPIC -shared -o $@ $<
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
+	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(APDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all ab oracle hostcheck fakeccl clean

@@ -80,6 +80,7 @@ EXPORTS = [
     "sfm_get_view_counts",
     "sfm_view_points_default_params", "sfm_triangulate_view", "sfm_triangulate_views",
     "sfm_adjust_default_params", "sfm_adjust_view", "sfm_adjust_views",
+    "sfm_align_default_params", "sfm_align_index_from_matches", "sfm_align_pair", "sfm_align_pairs",
 ]
 AB_EXPORTS = ["sfm_ransac_last_phases", "sfm_ransac_last_trace", "sfm_prefilter_probe", "sfm_prefilter_band_probe"]      # include/sfm_amd_ab.h
 if AB:
@@ -156,6 +157,26 @@ class AdjustReport(C.Structure):
 class AdjustOut(C.Structure):
     """sfm_adjust_out (include/sfm_amd.h): the caller's device buffers."""
     _fields_ = [("d_poses", C.c_void_p), ("d_points", C.c_void_p), ("d_views", C.c_void_p), ("d_err", C.c_void_p), ("d_report", C.c_void_p)]
+
+
+class AlignParams(C.Structure):
+    """sfm_align_params (include/sfm_amd.h)."""
+    _fields_ = [("num_hypotheses", C.c_uint32), ("seed", C.c_uint32), ("threshold_px", C.c_float), ("max_iterations", C.c_int32),
+                ("huber_px", C.c_float), ("min_rel_decrease", C.c_float), ("initial_lambda", C.c_float),
+                ("d_points_a", C.c_void_p), ("d_valid_a", C.c_void_p), ("d_points_b", C.c_void_p), ("d_valid_b", C.c_void_p),
+                ("reserved", C.c_int32 * 4)]
+
+
+class AlignReport(C.Structure):
+    """sfm_align_report (include/sfm_amd.h)."""
+    _fields_ = [("status", C.c_int32), ("num_candidates", C.c_int32), ("ransac_inliers", C.c_int32), ("num_inliers", C.c_int32),
+                ("best_hypothesis", C.c_uint32), ("iterations", C.c_int32), ("accepted", C.c_int32),
+                ("initial_rms_px", C.c_float), ("final_rms_px", C.c_float), ("final_cost", C.c_float), ("lambda", C.c_float)]
+
+
+class AlignOut(C.Structure):
+    """sfm_align_out (include/sfm_amd.h): the caller's device buffers."""
+    _fields_ = [("d_sim", C.c_void_p), ("d_inlier", C.c_void_p), ("d_err", C.c_void_p), ("d_counts", C.c_void_p), ("d_report", C.c_void_p)]
 
 
 _vp = C.c_void_p
@@ -247,6 +268,11 @@ _lib.sfm_adjust_default_params.argtypes = [C.POINTER(AdjustParams)]
 _lib.sfm_adjust_default_params.restype = None
 _lib.sfm_adjust_view.argtypes = [_vp, C.POINTER(AdjustIn), C.POINTER(AdjustParams), C.POINTER(AdjustOut)]
 _lib.sfm_adjust_views.argtypes = [C.POINTER(_vp), C.c_int, C.POINTER(AdjustIn), C.POINTER(AdjustParams), C.POINTER(AdjustOut)]
+_lib.sfm_align_default_params.argtypes = [C.POINTER(AlignParams)]
+_lib.sfm_align_default_params.restype = None
+_lib.sfm_align_index_from_matches.argtypes = [_vp, _vp, C.c_int, C.c_float, C.c_float, _vp]
+_lib.sfm_align_pair.argtypes = [_vp, _vp, _vp, C.POINTER(AlignParams), C.POINTER(AlignOut)]
+_lib.sfm_align_pairs.argtypes = [C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.POINTER(AlignParams), C.POINTER(AlignOut)]
 if AB:
     _lib.sfm_ransac_last_phases.argtypes = [_vp, C.POINTER(C.c_uint64)]
     _lib.sfm_ransac_last_trace.argtypes = [_vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_size_t)]
@@ -495,6 +521,94 @@ def adjust_views(pairs, ins, **kw):
     adjust_views_enqueue(pairs, ins, adjust_params(**kw), outs)
     pairs[0].ctx.synchronize()
     return [_adjust_results(out) for out in outs]
+
+
+_ALIGN_FIELDS = {f for f, _ in AlignParams._fields_}
+_ALIGN_POINTERS = {"points_a": "d_points_a", "valid_a": "d_valid_a", "points_b": "d_points_b", "valid_b": "d_valid_b"}
+
+
+def align_params(**kw):
+    """sfm_align_params with the library's defaults (4096 hypotheses, 4 px, 10 iterations, Huber 1 px, 1e-6, lambda 1e-3), fields
+    overridden by kw (points_a / valid_a / points_b / valid_b: device tensors / pointers)."""
+    p = AlignParams()
+    _lib.sfm_align_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k in _ALIGN_POINTERS or k in _ALIGN_POINTERS.values():
+            setattr(p, _ALIGN_POINTERS.get(k, k), _ptr(v))
+        elif k == "reserved":
+            for i, x in enumerate(v):
+                p.reserved[i] = int(x)
+        elif k in _ALIGN_FIELDS:
+            setattr(p, k, v)
+        else:
+            raise TypeError(f"align_params: no field {k!r} in sfm_align_params")
+    return p
+
+
+def _align_buffers(torch, device, n, num_hypotheses):
+    """Output tensors of one align_to call: sim 26, inlier n, err n, counts, report (bytes)."""
+    return (torch.empty(26, dtype=torch.float32, device=device), torch.empty(n, dtype=torch.uint8, device=device),
+            torch.empty(n, dtype=torch.float32, device=device), torch.empty(int(num_hypotheses), dtype=torch.int32, device=device),
+            torch.empty(C.sizeof(AlignReport), dtype=torch.uint8, device=device))
+
+
+def _align_results(outs):
+    """(sim, inlier, err, counts, report) tensors -> numpy arrays and the report as a dict."""
+    sim, inlier, err, counts, rep = (t.cpu().numpy() for t in outs)
+    r = AlignReport.from_buffer_copy(rep.tobytes())
+    return sim, inlier, err, counts, {f: getattr(r, f) for f, _ in AlignReport._fields_}
+
+
+def align_index_from_matches(ctx, d_sift, n, d_index, min_score=0.85, max_ambiguity=0.95):
+    """sfm_align_index_from_matches (enqueue only): d_index[j] = match of record j where it passes the registration's gate, else
+    -1.  d_sift: n records of pair A's first view matched against its second view; d_index: a device int32 tensor / pointer."""
+    _check(_lib.sfm_align_index_from_matches(ctx._h, _ptr(d_sift), int(n), float(min_score), float(max_ambiguity), _ptr(d_index)),
+           "sfm_align_index_from_matches")
+
+
+def align_pairs_enqueue(as_, bs, indices, params, outs):
+    """sfm_align_pairs (enqueue only): ImagePair.align_to_enqueue for every link (as_[i], bs[i]) of the list (one Context, every
+    pair refined, none twice in as_) in four launches.  indices: one device int32 tensor / pointer per link; outs: one (sim,
+    inlier, err, counts, report) tuple of device tensors / pointers per link (err and counts may be None); the overrides of
+    params must stay unset."""
+    n = len(as_)
+    assert len(bs) == n and len(indices) == n and len(outs) == n, "one b, one index and one output set per link"
+    ha = (_vp * n)(*[p._h.value for p in as_])
+    hb = (_vp * n)(*[p._h.value for p in bs])
+    idx = (_vp * n)(*[_ptr(t) for t in indices])
+    o = (AlignOut * n)(*[AlignOut(*[_ptr(t) for t in x]) for x in outs])
+    _check(_lib.sfm_align_pairs(ha, hb, n, idx, C.byref(params), o), "sfm_align_pairs")
+
+
+def align_pairs(as_, bs, indices, **kw):
+    """ImagePair.align_to for a list of links in one batched call; kw are AlignParams fields, the same for every link.  Returns
+    one (sim 26, inlier, err px, counts, report dict) tuple per link: one wait for the device."""
+    params = align_params(**kw)
+    if not as_:
+        align_pairs_enqueue([], [], [], params, [])
+        return []
+    dev = torch.device("cuda", as_[0].ctx.device)
+    outs = [_align_buffers(torch, dev, p.num_points, params.num_hypotheses) for p in as_]
+    align_pairs_enqueue(as_, bs, indices, params, outs)
+    as_[0].ctx.synchronize()
+    return [_align_results(out) for out in outs]
+
+
+def chain_links(sims):
+    """Composes a list of links into every pair's transform to the first pair's frame (host arithmetic, float64).  sims[i] is
+    (s, R, t) -- or the first 13 floats of an align_to result -- with X_{i+1} = s R X_i + t.  Returns len(sims) + 1 tuples
+    (s, R, t) with X_0 = s R X_i + t: the identity for pair 0, then the composed inverses."""
+    out = [(1.0, np.eye(3), np.zeros(3))]
+    for link in sims:
+        if not isinstance(link, tuple):
+            v = np.asarray(link, np.float64).ravel()
+            link = (v[0], v[1:10].reshape(3, 3), v[10:13])
+        s, R, t = float(link[0]), np.asarray(link[1], np.float64).reshape(3, 3), np.asarray(link[2], np.float64).reshape(3)
+        # X_i = (1 / s) R^T (X_{i+1} - t), then pair i's transform to pair 0
+        si, Ri, ti = 1.0 / s, R.T, -(R.T @ t) / s
+        s0, R0, t0 = out[-1]
+        out.append((s0 * si, R0 @ Ri, s0 * (R0 @ ti) + t0))
+    return out
 
 
 def sift_temp_layout(width, height, num_octaves=5, scale_up=False):
@@ -864,6 +978,25 @@ class ImagePair:
         self.adjust_view_enqueue(d_sift, points, flags, adjust_params(**kw), *outs)
         self.ctx.synchronize()
         return _adjust_results(outs)
+
+    # -- the similarity that carries this pair's frame into an overlapping pair's ----------------------
+    def align_to_enqueue(self, other, index, params, out_sim, out_inlier, out_err, out_counts, out_report):
+        """sfm_align_pair with an AlignParams (enqueue only): index (device int32, one entry per record of this pair) names the
+        record of `other` that is the same feature; out_sim (26 float32), out_inlier (n uint8), out_err (n float32, optional),
+        out_counts (num_hypotheses int32, optional) and out_report (sizeof(AlignReport) bytes) are the caller's device tensors /
+        pointers.  Nothing in either pair changes."""
+        o = AlignOut(_ptr(out_sim), _ptr(out_inlier), _ptr(out_err), _ptr(out_counts), _ptr(out_report))
+        _check(_lib.sfm_align_pair(self._h, other._h, _ptr(index), C.byref(params), C.byref(o)), "sfm_align_pair")
+
+    def align_to(self, other, index, **kw):
+        """The link (s, R, t) with X_other = s R X_self + t from the points the two pairs share, by 3-point RANSAC and a
+        7-parameter refinement; kw are AlignParams fields (points_a / valid_a / points_b / valid_b: device tensors).  Returns
+        (sim 26 = refined s, R, t then the RANSAC winner's, inlier, err px, counts, report dict) as numpy (synchronises)."""
+        params = align_params(**kw)
+        outs = _align_buffers(torch, torch.device("cuda", self.ctx.device), self.num_points, params.num_hypotheses)
+        self.align_to_enqueue(other, index, params, *outs)
+        self.ctx.synchronize()
+        return _align_results(outs)
 
     # -- accessors --------------------------------------------------------------------------------
     def device_ptr(self, which):

@@ -221,6 +221,7 @@ static int ctx_destroy_now(sfm_ctx *ctx)
     job_array_free(ctx->register_jobs);
     job_array_free(ctx->view_points_jobs);
     job_array_free(ctx->adjust_jobs);
+    job_array_free(ctx->align_jobs);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     for (auto &t : ctx->tev) for (hipEvent_t e : t) if (e) (void)hipEventDestroy(e);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -556,7 +557,8 @@ int sfm_pair_destroy(sfm_pair *p)
     void *bufs[] = { p->d_K, p->d_Kinv, p->d_U[0], p->d_U[1], p->d_X[0], p->d_X[1], p->d_pts4, p->d_E, p->d_P, p->d_Pinv, p->d_Pind,
                      p->d_points, p->d_mask, p->d_key, p->d_best, p->d_counts, p->d_Ecand, p->d_clk, p->d_tick,
                      p->alt_counts, p->alt_Ecand, p->alt_tick, p->alt_key, p->d_pf, p->alt_pf, p->d_bound, p->d_cells, p->d_pts4s, p->d_tile_boxes, p->d_buckets,
-                     p->d_rstate, p->d_rpoints, p->d_rreproj, p->d_rwork, p->d_vstate, p->d_vreproj, p->d_vwork, p->d_vhyp, p->d_vcounts, p->d_awork };
+                     p->d_rstate, p->d_rpoints, p->d_rreproj, p->d_rwork, p->d_vstate, p->d_vreproj, p->d_vwork, p->d_vhyp, p->d_vcounts, p->d_awork,
+                     p->d_lwork, p->d_lhyp };
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (p->pipe_stream) { (void)hipStreamSynchronize(p->pipe_stream); (void)hipStreamDestroy(p->pipe_stream); }
     for (hipEvent_t e : p->pipe_final) if (e) (void)hipEventDestroy(e);
@@ -1302,6 +1304,201 @@ int sfm_adjust_views(sfm_pair *const *pairs, int num_pairs, const sfm_adjust_in 
     std::vector<AdjustInputs> in((size_t)num_pairs);
     for (int i = 0; i < num_pairs; ++i) in[(size_t)i] = adjust_inputs(pairs[i], ins[i], *p);
     return launch_adjust_views(ctx, pairs, num_pairs, in.data(), *p, outs);
+}
+
+// ---- the similarity between two overlapping pairs' frames (align.hip) ------------------------------
+void sfm_align_default_params(sfm_align_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->num_hypotheses = 4096;
+    p->seed = 0x5EED5F3Du;
+    p->threshold_px = 4.0f;
+    p->max_iterations = 10;
+    p->huber_px = 1.0f;
+    p->min_rel_decrease = 1e-6f;
+    p->initial_lambda = 1e-3f;
+}
+
+// the parameter checks of sfm_align_pair and sfm_align_pairs (none needs a device)
+static int check_align_params(const sfm_align_params &p)
+{
+    const int rc = check_lm_params(p, "sfm_align_params");
+    if (rc != SFM_OK) return rc;
+    SFM_REQUIRE(p.num_hypotheses >= 1 && p.num_hypotheses <= (1u << 20), SFM_E_INVALID, "num_hypotheses %u outside 1..2^20", p.num_hypotheses);
+    SFM_REQUIRE(isfinite(p.threshold_px) && p.threshold_px > 0.0f, SFM_E_INVALID, "threshold_px must be finite and > 0");
+    SFM_REQUIRE(p.d_points_a || !p.d_valid_a, SFM_E_INVALID, "d_valid_a needs d_points_a");
+    SFM_REQUIRE(p.d_points_b || !p.d_valid_b, SFM_E_INVALID, "d_valid_b needs d_points_b");
+    return SFM_OK;
+}
+
+struct AlignRange { const void *p; size_t bytes; const char *name; };
+// the caller's buffers of one link: inputs, then outputs.  na, nb: the pairs' record counts, or 0 where the pairs have not been
+// looked at yet -- then the arrays that grow with them count as one byte (check_adjust_buffers' rule).
+static void align_ranges(const int32_t *d_index, const sfm_align_params &p, const sfm_align_out &out, int na, int nb, AlignRange ins[5], AlignRange outs[5])
+{
+    auto len = [](int n, size_t per) { return n ? (size_t)n * per : (size_t)1; };
+    ins[0] = { d_index, len(na, 4), "d_index" };
+    ins[1] = { p.d_points_a, len(na, 16), "params.d_points_a" }; ins[2] = { p.d_valid_a, len(na, 1), "params.d_valid_a" };
+    ins[3] = { p.d_points_b, len(nb, 16), "params.d_points_b" }; ins[4] = { p.d_valid_b, len(nb, 1), "params.d_valid_b" };
+    outs[0] = { out.d_sim, 26 * sizeof(float), "out.d_sim" }; outs[1] = { out.d_inlier, len(na, 1), "out.d_inlier" };
+    outs[2] = { out.d_err, len(na, 4), "out.d_err" }; outs[3] = { out.d_counts, (size_t)p.num_hypotheses * 4, "out.d_counts" };
+    outs[4] = { out.d_report, sizeof(sfm_align_report), "out.d_report" };
+}
+
+// The checks of one link's buffers that need no device: required pointers, no output on top of an input or of another output.
+// who: "" or "links[i]: ".
+static int check_align_buffers(const int32_t *d_index, const sfm_align_params &p, const sfm_align_out &out, int na, int nb, const char *who)
+{
+    SFM_REQUIRE(d_index, SFM_E_INVALID, "%sd_index is required", who);
+    SFM_REQUIRE(out.d_sim && out.d_inlier && out.d_report, SFM_E_INVALID, "%ssfm_align_out.d_sim, d_inlier and d_report are required", who);
+    AlignRange ins[5], outs[5];
+    align_ranges(d_index, p, out, na, nb, ins, outs);
+    auto overlap = [](const AlignRange &x, const AlignRange &y) {
+        if (!x.p || !y.p) return false;
+        const uintptr_t a = reinterpret_cast<uintptr_t>(x.p), b = reinterpret_cast<uintptr_t>(y.p);
+        return a < b + y.bytes && b < a + x.bytes;
+    };
+    for (int o = 0; o < 5; ++o) {
+        for (int i = 0; i < 5; ++i) SFM_REQUIRE(!overlap(outs[o], ins[i]), SFM_E_INVALID, "%s%s overlaps %s", who, outs[o].name, ins[i].name);
+        for (int q = o + 1; q < 5; ++q) SFM_REQUIRE(!overlap(outs[o], outs[q]), SFM_E_INVALID, "%s%s overlaps %s", who, outs[o].name, outs[q].name);
+    }
+    return SFM_OK;
+}
+
+// the work buffers of pair `a`: the per-record one allocated at the first call, the per-hypothesis one grown on demand
+static int align_buffers(sfm_pair *pair, uint32_t num_hypotheses)
+{
+    int rc = SFM_OK;
+    if (!pair->d_lwork) {                               // sized to the creation-time count: sfm_pair_reset needs no reallocation
+        rc = alloc_group({ { &pair->d_lwork, align_work_bytes(pair->cap_points) } });
+        if (rc != SFM_OK) return rc;
+    }
+    if (num_hypotheses > pair->cap_lhyps) {             // grows with the largest num_hypotheses seen (the old buffer may be in use)
+        pair->cap_lhyps = 0;
+        size_t have = 0;
+        rc = grow(&pair->d_lhyp, &have, align_hyp_bytes(num_hypotheses), pair->ctx->stream);
+        if (rc == SFM_OK) pair->cap_lhyps = num_hypotheses;
+    }
+    return rc;
+}
+
+// the inputs a call reads where the caller gave none: each pair's refined points and the refinement's used flags
+static AlignInputs align_inputs(const sfm_pair *a, const sfm_pair *b, const int32_t *d_index, const sfm_align_params &p)
+{
+    AlignInputs in;
+    in.points_a = p.d_points_a ? p.d_points_a : a->d_rpoints;
+    in.valid_a = p.d_points_a ? p.d_valid_a : reproj_flags(a, a->d_rreproj);
+    in.points_b = p.d_points_b ? p.d_points_b : b->d_rpoints;
+    in.valid_b = p.d_points_b ? p.d_valid_b : reproj_flags(b, b->d_rreproj);
+    in.index = d_index;
+    return in;
+}
+
+int sfm_align_index_from_matches(sfm_ctx *ctx, const sfm_sift_point *d_sift, int n, float min_score, float max_ambiguity, int32_t *d_index)
+{
+    SFM_REQUIRE(ctx && d_sift && d_index, SFM_E_INVALID, "null argument");
+    SFM_REQUIRE(n >= 0, SFM_E_INVALID, "n %d is negative", n);
+    SFM_REQUIRE(isfinite(min_score) && isfinite(max_ambiguity), SFM_E_INVALID, "min_score / max_ambiguity must be finite");
+    if (n == 0) return SFM_OK;
+    SFM_HIP_TRY(hipSetDevice(ctx->device));
+    return launch_align_index(ctx, d_sift, n, min_score, max_ambiguity, d_index);
+}
+
+int sfm_align_pair(sfm_pair *a, sfm_pair *b, const int32_t *d_index, const sfm_align_params *p, const sfm_align_out *out)
+{
+    SFM_REQUIRE(a && b && p && out, SFM_E_INVALID, "null argument");
+    int rc = check_align_params(*p);
+    if (rc != SFM_OK) return rc;
+    rc = check_align_buffers(d_index, *p, *out, 0, 0, "");
+    if (rc != SFM_OK) return rc;
+    SFM_REQUIRE(a != b, SFM_E_INVALID, "a and b are the same pair");
+    SFM_REQUIRE(a->ctx == b->ctx, SFM_E_INVALID, "a and b belong to different contexts");
+    SFM_FLUSH(a);
+    SFM_FLUSH(b);
+    SFM_NEED(a, p->d_points_a ? kPoints : kPoints | kRefined);
+    SFM_NEED(b, p->d_points_b ? kPoints : kPoints | kRefined);
+    rc = check_align_buffers(d_index, *p, *out, a->n, b->n, "");                            // the same with the arrays' real lengths
+    if (rc != SFM_OK) return rc;
+    SFM_HIP_TRY(hipSetDevice(a->ctx->device));
+    rc = align_buffers(a, p->num_hypotheses);
+    if (rc != SFM_OK) return rc;
+    return launch_align(a, b, align_inputs(a, b, d_index, *p), *p, *out);                  // reads the pairs: no stage changes
+}
+
+int sfm_align_pairs(sfm_pair *const *as, sfm_pair *const *bs, int num_links, const int32_t *const *d_indices, const sfm_align_params *p,
+                    const sfm_align_out *outs)
+{
+    // the checks that need no device first, all of them before anything is enqueued
+    SFM_REQUIRE(p, SFM_E_INVALID, "null params");
+    SFM_REQUIRE(num_links >= 0 && num_links <= 65535, SFM_E_INVALID, "num_links %d outside 0..65535", num_links);
+    SFM_REQUIRE(!p->d_points_a && !p->d_valid_a && !p->d_points_b && !p->d_valid_b, SFM_E_INVALID,
+                "sfm_align_params.d_points_* / d_valid_* must be null here: every pair reads its own refinement");
+    int rc = check_align_params(*p);
+    if (rc != SFM_OK) return rc;
+    if (num_links == 0) return SFM_OK;
+    SFM_REQUIRE(as && bs && d_indices && outs, SFM_E_INVALID, "null pair list, d_indices list or outs list");
+    char who[32];
+    for (int i = 0; i < num_links; ++i) {
+        SFM_REQUIRE(as[i] && bs[i], SFM_E_INVALID, "links[%d]: null pair", i);
+        SFM_REQUIRE(as[i] != bs[i], SFM_E_INVALID, "links[%d]: a and b are the same pair", i);
+        snprintf(who, sizeof(who), "links[%d]: ", i);
+        rc = check_align_buffers(d_indices[i], *p, outs[i], 0, 0, who);
+        if (rc != SFM_OK) return rc;
+    }
+    sfm_ctx *ctx = as[0]->ctx;
+    for (int i = 0; i < num_links; ++i)
+        SFM_REQUIRE(as[i]->ctx == ctx && bs[i]->ctx == ctx, SFM_E_INVALID, "links[%d]: a pair belongs to another context than links[0]'s a", i);
+    {
+        std::vector<std::pair<const sfm_pair *, int>> sorted((size_t)num_links);
+        for (int i = 0; i < num_links; ++i) sorted[(size_t)i] = { as[i], i };
+        std::sort(sorted.begin(), sorted.end());
+        for (int k = 1; k < num_links; ++k)
+            SFM_REQUIRE(sorted[(size_t)k].first != sorted[(size_t)k - 1].first, SFM_E_INVALID,
+                        "links[%d]: the pair is listed twice as a (two blocks would write the same work buffer)", sorted[(size_t)k].second);
+    }
+    for (int i = 0; i < num_links; ++i) { SFM_FLUSH(as[i]); SFM_FLUSH(bs[i]); }
+    const uint32_t need = kPoints | kRefined;
+    for (int i = 0; i < num_links; ++i) {
+        SFM_REQUIRE(as[i]->state.has(need), SFM_E_STATE, "links[%d]: a: %s", i, pair_stage_hint(as[i]->state.missing(need)));
+        SFM_REQUIRE(bs[i]->state.has(need), SFM_E_STATE, "links[%d]: b: %s", i, pair_stage_hint(bs[i]->state.missing(need)));
+    }
+    for (int i = 0; i < num_links; ++i) {
+        snprintf(who, sizeof(who), "links[%d]: ", i);
+        rc = check_align_buffers(d_indices[i], *p, outs[i], as[i]->n, bs[i]->n, who);      // the same with the arrays' real lengths
+        if (rc != SFM_OK) return rc;
+    }
+    {
+        // across links: the blocks of different links run at the same time, so no output may lie on an output or an input of
+        // another link either (inputs may be shared).  All ranges sorted by their start, one sweep (sfm_adjust_views').
+        struct Range { uintptr_t lo, hi; int link; bool out; };
+        std::vector<Range> r;
+        r.reserve((size_t)num_links * 6);
+        for (int i = 0; i < num_links; ++i) {
+            AlignRange ins[5], os[5];
+            align_ranges(d_indices[i], *p, outs[i], as[i]->n, bs[i]->n, ins, os);
+            for (int k = 0; k < 5; ++k) {
+                if (ins[k].p && ins[k].bytes) r.push_back({ reinterpret_cast<uintptr_t>(ins[k].p), reinterpret_cast<uintptr_t>(ins[k].p) + ins[k].bytes, i, false });
+                if (os[k].p && os[k].bytes) r.push_back({ reinterpret_cast<uintptr_t>(os[k].p), reinterpret_cast<uintptr_t>(os[k].p) + os[k].bytes, i, true });
+            }
+        }
+        std::sort(r.begin(), r.end(), [](const Range &x, const Range &y) { return x.lo < y.lo; });
+        const Range *far_any = nullptr, *far_out = nullptr;     // the ranges seen so far that end last: any, and among the outputs
+        for (const Range &x : r) {
+            const Range *hit = x.out ? far_any : far_out;
+            if (hit && hit->hi > x.lo && hit->link != x.link) {
+                const int later = x.link > hit->link ? x.link : hit->link, other = x.link > hit->link ? hit->link : x.link;
+                SFM_REQUIRE(false, SFM_E_INVALID, "links[%d]: a buffer overlaps a buffer of links[%d], and one of the two is an output", later, other);
+            }
+            if (!far_any || x.hi > far_any->hi) far_any = &x;
+            if (x.out && (!far_out || x.hi > far_out->hi)) far_out = &x;
+        }
+    }
+    SFM_HIP_TRY(hipSetDevice(ctx->device));
+    for (int i = 0; i < num_links; ++i) { rc = align_buffers(as[i], p->num_hypotheses); if (rc != SFM_OK) return rc; }
+    std::vector<AlignInputs> in((size_t)num_links);
+    for (int i = 0; i < num_links; ++i) in[(size_t)i] = align_inputs(as[i], bs[i], d_indices[i], *p);
+    return launch_align_pairs(ctx, as, bs, num_links, in.data(), *p, outs);
 }
 
 // ---- accessors ------------------------------------------------------------------------------------

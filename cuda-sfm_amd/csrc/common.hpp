@@ -188,8 +188,9 @@ struct sfm_ctx {
     void *batch_ws = nullptr;          // sfm_process_pairs, batched path: the PairJob array + every pair's buffers (pairs_batch.hpp)
     size_t batch_ws_bytes = 0;
     // sfm_refine_pairs / sfm_register_views / sfm_triangulate_views: the RefineArgs (refine.hip) / RegisterArgs (register.hip) /
-    // ViewPointsArgs (view_points.hip) of a call; sfm_adjust_views: the AdjustArgs (adjust.hip)
-    sfm::JobArray refine_jobs, register_jobs, view_points_jobs, adjust_jobs;
+    // ViewPointsArgs (view_points.hip) of a call; sfm_adjust_views: the AdjustArgs (adjust.hip); sfm_align_pairs: the AlignArgs
+    // (align.hip)
+    sfm::JobArray refine_jobs, register_jobs, view_points_jobs, adjust_jobs, align_jobs;
     void *sift_job = nullptr;          // the extraction in flight (sift.hip: SiftJob), sfm_extract_sift_begin .. _end
     // kernels that already opted in to > 64 KiB of dynamic LDS on THIS context's device (function attributes are
     // per device; a context is used by one host thread at a time, so no process-wide flag)
@@ -291,6 +292,11 @@ struct sfm_pair {
     uint32_t view_hyps = 0;            // num_hypotheses of the last registration
     // sfm_adjust_view: allocated at the first call, sized to cap_points (adjust.hip)
     void *d_awork = nullptr;           // per record: observations, start point, compact index; per used record: the same, compacted, and the points
+    // sfm_align_pair with this pair as `a`: allocated at the first call (per-record buffer sized to cap_points, per-hypothesis
+    // buffer grown on demand) (align.hip)
+    void *d_lwork = nullptr;           // key, candidate count; candidates (both points, both observations), record -> candidate map, winner's inlier flags
+    void *d_lhyp = nullptr;            // per hypothesis: accumulator (uint64), link (13 floats, SoA)
+    size_t cap_lhyps = 0;
     int last_kernel = 0, last_grid = 0, last_block = 0, last_lds = 0;
 };
 
@@ -377,6 +383,16 @@ int launch_adjust(sfm_pair *pair, const AdjustInputs &in, const sfm_adjust_param
 // the same three stages for many pairs of one context in three launches
 int launch_adjust_views(sfm_ctx *ctx, sfm_pair *const *pairs, int num_pairs, const AdjustInputs *in, const sfm_adjust_params &p, const sfm_adjust_out *outs);
 size_t adjust_work_bytes(int cap_points);                         // bytes of pair->d_awork
+
+// align.hip: the similarity that carries pair a's frame into pair b's; points / valid resolved by the caller
+struct AlignInputs { const float *points_a; const uint8_t *valid_a; const float *points_b; const uint8_t *valid_b; const int32_t *index; };
+int launch_align(sfm_pair *a, sfm_pair *b, const AlignInputs &in, const sfm_align_params &p, const sfm_align_out &out);   // gate, solve, score, refine
+// the same four stages for many links of one context in four launches
+int launch_align_pairs(sfm_ctx *ctx, sfm_pair *const *as, sfm_pair *const *bs, int num_links, const AlignInputs *in, const sfm_align_params &p,
+                       const sfm_align_out *outs);
+int launch_align_index(sfm_ctx *ctx, const sfm_sift_point *d_sift, int n, float min_score, float max_ambiguity, int32_t *d_index);
+size_t align_work_bytes(int cap_points);                          // bytes of pair->d_lwork
+size_t align_hyp_bytes(size_t num_hypotheses);                    // bytes of pair->d_lhyp
 
 // sift.hip
 void sift_layout(int width, int height, int num_octaves, int scale_up, sfm_sift_layout *L);

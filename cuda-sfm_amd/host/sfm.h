@@ -38,6 +38,51 @@ struct ViewAdjust {
     sfm_adjust_report report;
 };
 
+// A similarity X' = s R X + t (R row-major), host arithmetic in double: the link between two pairs' frames and its compositions.
+struct Sim3 {
+    double s = 1.0;
+    double R[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 };
+    double t[3] = { 0, 0, 0 };
+    static Sim3 from(const float sim[13])              // s, R (9), t (3) as sfm_align_out.d_sim holds them
+    {
+        Sim3 r;
+        r.s = sim[0];
+        for (int k = 0; k < 9; ++k) r.R[k] = sim[1 + k];
+        for (int k = 0; k < 3; ++k) r.t[k] = sim[10 + k];
+        return r;
+    }
+    void apply(const double X[3], double Y[3]) const
+    {
+        for (int r = 0; r < 3; ++r) Y[r] = s * (R[3 * r] * X[0] + R[3 * r + 1] * X[1] + R[3 * r + 2] * X[2]) + t[r];
+    }
+    // this after first: X -> s R (s1 R1 X + t1) + t
+    Sim3 compose(const Sim3 &first) const
+    {
+        Sim3 r;
+        r.s = s * first.s;
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) r.R[3 * i + j] = R[3 * i] * first.R[j] + R[3 * i + 1] * first.R[3 + j] + R[3 * i + 2] * first.R[6 + j];
+        apply(first.t, r.t);
+        return r;
+    }
+    Sim3 inverse() const                               // X = (1 / s) R^T (X' - t)
+    {
+        Sim3 r;
+        r.s = 1.0 / s;
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) r.R[3 * i + j] = R[3 * j + i];
+        for (int i = 0; i < 3; ++i) r.t[i] = -r.s * (r.R[3 * i] * t[0] + r.R[3 * i + 1] * t[1] + r.R[3 * i + 2] * t[2]);
+        return r;
+    }
+};
+
+// what alignTo / align_pairs return for one link, in host memory
+struct PairLink {
+    Sim3 sim, ransac;                   // X_other = s R X_this + t: refined, and the RANSAC winner's
+    std::vector<uint8_t> inlier;        // N of this pair: the final mask
+    sfm_align_report report;
+};
+
 namespace detail {
 // a device allocation that is freed when it goes out of scope, also when a facade call throws (SFM_FACADE_THROW)
 struct DeviceBlock {
@@ -123,6 +168,36 @@ struct AdjustScratch {
         SFM_FACADE_CALL(sfm_copy_to_host(sfm_facade::context(), r.views.data(), o.d_views, n));
         SFM_FACADE_CALL(sfm_copy_to_host(sfm_facade::context(), r.poses, o.d_poses, sizeof(r.poses)));
         SFM_FACADE_CALL(sfm_copy_to_host(sfm_facade::context(), &r.report, o.d_report, sizeof(r.report)));
+        return r;
+    }
+};
+// device scratch of one link: the index built from the records, the outputs, in ONE sfm_device_alloc block
+struct AlignScratch {
+    size_t n = 0;
+    DeviceBlock mem;
+    explicit AlignScratch(int num_points) : n((size_t)num_points), mem(4 * n + 112 + 48 + n + 16) {}
+    int32_t *index() const { return reinterpret_cast<int32_t *>(mem.p + 160); }
+    sfm_align_out out() const
+    {
+        sfm_align_out o;
+        o.d_sim = reinterpret_cast<float *>(mem.p);
+        o.d_report = reinterpret_cast<sfm_align_report *>(mem.p + 112);
+        o.d_inlier = reinterpret_cast<uint8_t *>(mem.p + 160 + 4 * n);
+        o.d_err = nullptr;
+        o.d_counts = nullptr;
+        return o;
+    }
+    PairLink download() const            // synchronises
+    {
+        PairLink r;
+        float sim[26];
+        r.inlier.resize(n);
+        const sfm_align_out o = out();
+        SFM_FACADE_CALL(sfm_copy_to_host(sfm_facade::context(), sim, o.d_sim, sizeof(sim)));
+        if (n) SFM_FACADE_CALL(sfm_copy_to_host(sfm_facade::context(), r.inlier.data(), o.d_inlier, n));
+        SFM_FACADE_CALL(sfm_copy_to_host(sfm_facade::context(), &r.report, o.d_report, sizeof(r.report)));
+        r.sim = Sim3::from(sim);
+        r.ransac = Sim3::from(sim + 13);
         return r;
     }
 };
@@ -291,6 +366,22 @@ public:
         SFM_FACADE_CALL(sfm_adjust_view(pair_, &in, &p, &out));
         return scratch.download();
     }
+    // the similarity that carries this pair's frame into `other`'s (sfm_align_pair): data = the records fillXU took (image 1
+    // matched against image 2, which is image 1 of `other`); both pairs refined; nothing in either pair changes; returns the
+    // link, the final mask and the report (synchronises)
+    PairLink alignTo(Image_pair &other, SiftPoint *data, int max_iterations = 10, float threshold_px = 4.0f)
+    {
+        sfm_align_params p;
+        sfm_align_default_params(&p);
+        p.max_iterations = max_iterations;
+        p.threshold_px = threshold_px;
+        const detail::AlignScratch scratch(num_points_);
+        const sfm_align_out out = scratch.out();
+        SFM_FACADE_CALL(sfm_align_index_from_matches(sfm_facade::context(), reinterpret_cast<const sfm_sift_point *>(data), num_points_, 0.85f, 0.95f,
+                                                     scratch.index()));
+        SFM_FACADE_CALL(sfm_align_pair(pair_, other.pair_, scratch.index(), &p, &out));
+        return scratch.download();
+    }
     std::vector<float> getX(int image)      // 3 x N normalised coordinates of image 0 / 1
     {
         std::vector<float> x((size_t)3 * num_points_);
@@ -388,6 +479,36 @@ inline std::vector<ViewAdjust> adjust_views(Image_pair *const *pairs, SiftPoint 
     }
     SFM_FACADE_CALL(sfm_adjust_views(handles.data(), count, ins.data(), &p, outs.data()));
     std::vector<ViewAdjust> results;
+    for (int i = 0; i < count; ++i) results.push_back(scratch[(size_t)i]->download());
+    return results;
+}
+
+// alignTo for each of many links in one batched call (sfm_align_pairs): link i carries as[i]'s frame into bs[i]'s, data[i] = the
+// records as[i]'s fillXU took; no pair twice in as (a pair may be b of one link and a of the next: the ring); returns one result
+// per link in the order of the list, each as its own alignTo() gives it
+inline std::vector<PairLink> align_pairs(Image_pair *const *as, Image_pair *const *bs, SiftPoint *const *data, int count, int max_iterations = 10,
+                                         float threshold_px = 4.0f)
+{
+    sfm_align_params p;
+    sfm_align_default_params(&p);
+    p.max_iterations = max_iterations;
+    p.threshold_px = threshold_px;
+    std::vector<sfm_pair *> ha, hb;
+    std::vector<std::unique_ptr<detail::AlignScratch>> scratch;
+    std::vector<const int32_t *> indices;
+    std::vector<sfm_align_out> outs;
+    for (int i = 0; i < count; ++i) {
+        ha.push_back(as[i] ? as[i]->handle() : nullptr);
+        hb.push_back(bs[i] ? bs[i]->handle() : nullptr);
+        const int n = as[i] ? as[i]->numPoints() : 0;
+        scratch.emplace_back(new detail::AlignScratch(n));
+        SFM_FACADE_CALL(sfm_align_index_from_matches(sfm_facade::context(), reinterpret_cast<const sfm_sift_point *>(data[i]), n, 0.85f, 0.95f,
+                                                     scratch.back()->index()));
+        indices.push_back(scratch.back()->index());
+        outs.push_back(scratch.back()->out());
+    }
+    SFM_FACADE_CALL(sfm_align_pairs(ha.data(), hb.data(), count, indices.data(), &p, outs.data()));
+    std::vector<PairLink> results;
     for (int i = 0; i < count; ++i) results.push_back(scratch[(size_t)i]->download());
     return results;
 }

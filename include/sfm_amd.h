@@ -497,6 +497,71 @@ int sfm_adjust_view(sfm_pair *pair, const sfm_adjust_in *in, const sfm_adjust_pa
 int sfm_adjust_views(sfm_pair *const *pairs, int num_pairs, const sfm_adjust_in *ins, const sfm_adjust_params *p,
                      const sfm_adjust_out *outs);                                                     /* enqueue only */
 
+/* ---- aligning two overlapping pairs: the similarity between their frames -------------------------
+ * Pair A = (view i, view i+1) and pair B = (view i+1, view i+2) each live in their own gauge (camera 1 = [I|0], |t| = 1).  A
+ * link is (s, R, t), s > 0, with X_B = s R X_A + t: with exact data R and t / s are A's camera-2 pose and s the ratio of the two
+ * gauges.  Correspondences: point j of A is record j of view i; d_index[j] is the index of the same feature among view i+1's
+ * records, which is B's point index (sfm_align_index_from_matches builds it from A's records), or any value outside
+ * [0, num_points of B) for none.  Record j is a candidate when d_index[j] is in range and both points are usable (the
+ * registration's point test: finite, W != 0, Z / W > 0, valid flag set).
+ * 3-point RANSAC (orthonormal triads of the sample in both frames, one hypothesis per lane), then Levenberg-Marquardt over 7
+ * parameters (R <- exp([w]x) R, t <- t + dt, s <- s exp(dsigma)) on the winner's inliers, Huber loss per residual pair.
+ * Residuals and the inlier test are pixels, never 3-D distances: forward, Y = s R X_A + t against B's view-1 observation (B's X0,
+ * dehomogenised) through B's K; backward, Z = R^T (X_B - t) against A's view-1 observation through A's K.  A candidate is an
+ * inlier iff both pass sfm_register_view's division-free test at threshold_px (in front of the camera included); scoring, the
+ * LM's point set and the final mask share it.
+ * Fewer than 3 candidates or a winner with fewer than 6 inliers: status SFM_REFINE_DEGENERATE (not an error), the winner's link
+ * unrefined (the identity, s = 1, if no sample gave one), zero masks.
+ * The calls READ both pairs and write only the caller's buffers: no stage, buffer id or getter belongs to them. */
+typedef struct sfm_align_params {
+    uint32_t num_hypotheses;    /* 1..2^20, default 4096                                                               */
+    uint32_t seed;              /* sampler seed, default 0x5EED5F3D                                                     */
+    float    threshold_px;      /* both pixel errors below this (test above), default 4.0                               */
+    int32_t  max_iterations;    /* LM, accepted + rejected, 0..200 (0 = RANSAC winner only), default 10                 */
+    float    huber_px, min_rel_decrease, initial_lambda;   /* as sfm_register_params; 1.0 / 1e-6 / 1e-3                 */
+    const float   *d_points_a;  /* optional DEVICE 4 x num_points of A; NULL = A's refined points + the refinement's used flags */
+    const uint8_t *d_valid_a;   /* optional DEVICE uint8[num_points of A], only with d_points_a (NULL: every point)     */
+    const float   *d_points_b;  /* the same for B                                                                       */
+    const uint8_t *d_valid_b;
+    int32_t  reserved[4];       /* must be zero (else SFM_E_INVALID)                                                    */
+} sfm_align_params;
+typedef struct sfm_align_report {
+    int32_t  status;            /* SFM_REFINE_CONVERGED / _MAX_ITER / _DEGENERATE                                      */
+    int32_t  num_candidates;    /* records that passed the gate                                                        */
+    int32_t  ransac_inliers;    /* the winner's count: the candidates the LM runs over                                 */
+    int32_t  num_inliers;       /* final mask: candidates that pass the test under the refined link                    */
+    uint32_t best_hypothesis;   /* first maximum of the counts                                                         */
+    int32_t  iterations, accepted;
+    float    initial_rms_px, final_rms_px;  /* sqrt(sum of squared pixel residuals / (4 ransac_inliers)) over the winner's
+                                               inliers, both directions, at the winner's and at the refined link        */
+    float    final_cost;        /* robust cost at the end                                                              */
+    float    lambda;
+} sfm_align_report;
+typedef struct sfm_align_out {  /* DEVICE buffers of the caller; none may overlap an input or another output            */
+    float   *d_sim;             /* 26, required: s, R (9, row-major), t (3) refined, then the RANSAC winner's           */
+    uint8_t *d_inlier;          /* num_points of A, required: the final mask                                            */
+    float   *d_err;             /* num_points of A, optional: the larger of the two pixel errors under the refined link,
+                                   +inf for non-candidates and behind a camera                                          */
+    int32_t *d_counts;          /* num_hypotheses, optional: every hypothesis' inlier count                             */
+    sfm_align_report *d_report; /* required, DEVICE                                                                     */
+} sfm_align_out;
+void sfm_align_default_params(sfm_align_params *p);
+/* d_index[j] = match of record j where match >= 0, score > min_score and ambiguity < max_ambiguity (the registration's gate),
+ * else -1.  d_sift: DEVICE, n records of A's first view matched against A's second view; enqueue only. */
+int sfm_align_index_from_matches(sfm_ctx *ctx, const sfm_sift_point *d_sift, int n, float min_score, float max_ambiguity,
+                                 int32_t *d_index);
+/* Needs, in both pairs: points; the refinement unless that side's d_points_* is given (SFM_E_STATE).  a and b belong to one
+ * context, a != b.  d_index: DEVICE int32[num_points of A].  The work buffer belongs to pair a. */
+int sfm_align_pair(sfm_pair *a, sfm_pair *b, const int32_t *d_index, const sfm_align_params *p, const sfm_align_out *out);   /* enqueue only */
+/* The same for many links of ONE context in four launches: every outs[i] ends byte for byte as after
+ * sfm_align_pair(as[i], bs[i], d_indices[i], p, &outs[i]), wherever the link stands in the list.  as, bs, d_indices, outs: HOST
+ * arrays of num_links (0..65535) entries; the overrides in p must be NULL.  No pair may be listed twice as `a` (its work buffer
+ * serves one link); a pair may be `a` of one link and `b` of another.  No output may overlap an input, another output, or a
+ * buffer of another link.  Every check precedes the launches: on SFM_E_INVALID / SFM_E_STATE (the text names the first offending
+ * link as links[i]) nothing is written. */
+int sfm_align_pairs(sfm_pair *const *as, sfm_pair *const *bs, int num_links, const int32_t *const *d_indices,
+                    const sfm_align_params *p, const sfm_align_out *outs);                           /* enqueue only */
+
 /* ---- accessors (the reference keeps these private; needed for parity checks) ------------------ */
 #define SFM_BUF_X0      0   /* float 3 x ld   normalised coords image 1 (ld = sfm_pair_ld)   */
 #define SFM_BUF_X1      1
