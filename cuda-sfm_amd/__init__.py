@@ -53,6 +53,7 @@ POSE_REFERENCE, POSE_CORRECT = 0, 1
 REFINE_CONVERGED, REFINE_MAX_ITER, REFINE_DEGENERATE = 0, 1, 2         # sfm_refine_report.status, sfm_register_report.status
 VP_UNSEEN, VP_NEW, VP_REFINED, VP_NEW_REJECTED, VP_KEPT = range(5)     # sfm_view_points_out.d_flags
 ADJ_VIEW1, ADJ_VIEW2, ADJ_VIEW3 = 1, 2, 4                              # bits of sfm_adjust_out.d_views
+FUSE_REFINED, FUSE_KEPT = 1, 2                                         # sfm_fuse_out.d_flags
 
 SIFT_DTYPE = np.dtype([
     ("xpos", "<f4"), ("ypos", "<f4"), ("scale", "<f4"), ("sharpness", "<f4"),
@@ -81,6 +82,7 @@ EXPORTS = [
     "sfm_view_points_default_params", "sfm_triangulate_view", "sfm_triangulate_views",
     "sfm_adjust_default_params", "sfm_adjust_view", "sfm_adjust_views",
     "sfm_align_default_params", "sfm_align_index_from_matches", "sfm_align_pair", "sfm_align_pairs",
+    "sfm_fuse_default_params", "sfm_fuse_chain",
 ]
 AB_EXPORTS = ["sfm_ransac_last_phases", "sfm_ransac_last_trace", "sfm_prefilter_probe", "sfm_prefilter_band_probe"]      # include/sfm_amd_ab.h
 if AB:
@@ -179,6 +181,31 @@ class AlignOut(C.Structure):
     _fields_ = [("d_sim", C.c_void_p), ("d_inlier", C.c_void_p), ("d_err", C.c_void_p), ("d_counts", C.c_void_p), ("d_report", C.c_void_p)]
 
 
+class FuseParams(C.Structure):
+    """sfm_fuse_params (include/sfm_amd.h)."""
+    _fields_ = [("threshold_px", C.c_float), ("max_iterations", C.c_int32), ("huber_px", C.c_float), ("min_rel_decrease", C.c_float),
+                ("initial_lambda", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+class FusePairIn(C.Structure):
+    """sfm_fuse_pair_in (include/sfm_amd.h): one pair of the chain and its optional overrides."""
+    _fields_ = [("pair", C.c_void_p), ("d_points", C.c_void_p), ("d_valid", C.c_void_p), ("d_pose", C.c_void_p)]
+
+
+class FuseLinkIn(C.Structure):
+    """sfm_fuse_link_in (include/sfm_amd.h): what sfm_align_pairs took and gave for one link."""
+    _fields_ = [("d_index", C.c_void_p), ("d_sim", C.c_void_p), ("d_inlier", C.c_void_p), ("d_err", C.c_void_p), ("d_report", C.c_void_p)]
+
+
+class FuseOut(C.Structure):
+    """sfm_fuse_out (include/sfm_amd.h): the caller's device buffers."""
+    _fields_ = [("d_frames", C.c_void_p), ("d_root", C.c_void_p), ("d_cams", C.c_void_p), ("d_track", C.c_void_p),
+                ("d_track_offset", C.c_void_p), ("d_obs_cam", C.c_void_p), ("d_obs_record", C.c_void_p), ("d_points", C.c_void_p),
+                ("d_flags", C.c_void_p), ("d_err", C.c_void_p), ("d_counts", C.c_void_p)]
+
+
+FUSE_COUNTS = ("tracks", "observations", "refined", "kept", "segments", "longest_track")      # sfm_fuse_out.d_counts[0..5]
+
 _vp = C.c_void_p
 _lib.sfm_last_error.restype = C.c_char_p
 _lib.sfm_ctx_create.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -273,6 +300,9 @@ _lib.sfm_align_default_params.restype = None
 _lib.sfm_align_index_from_matches.argtypes = [_vp, _vp, C.c_int, C.c_float, C.c_float, _vp]
 _lib.sfm_align_pair.argtypes = [_vp, _vp, _vp, C.POINTER(AlignParams), C.POINTER(AlignOut)]
 _lib.sfm_align_pairs.argtypes = [C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.POINTER(AlignParams), C.POINTER(AlignOut)]
+_lib.sfm_fuse_default_params.argtypes = [C.POINTER(FuseParams)]
+_lib.sfm_fuse_default_params.restype = None
+_lib.sfm_fuse_chain.argtypes = [_vp, C.POINTER(FusePairIn), C.c_int, C.POINTER(FuseLinkIn), C.POINTER(FuseParams), C.POINTER(FuseOut)]
 if AB:
     _lib.sfm_ransac_last_phases.argtypes = [_vp, C.POINTER(C.c_uint64)]
     _lib.sfm_ransac_last_trace.argtypes = [_vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_size_t)]
@@ -609,6 +639,78 @@ def chain_links(sims):
         s0, R0, t0 = out[-1]
         out.append((s0 * si, R0 @ Ri, s0 * (R0 @ ti) + t0))
     return out
+
+
+_FUSE_FIELDS = {f for f, _ in FuseParams._fields_}
+
+
+def fuse_params(**kw):
+    """sfm_fuse_params with the library's defaults (4 px, 5 iterations, Huber 1 px, 1e-6, lambda 1e-3), fields overridden by kw."""
+    p = FuseParams()
+    _lib.sfm_fuse_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "reserved":
+            for i, x in enumerate(v):
+                p.reserved[i] = int(x)
+        elif k in _FUSE_FIELDS:
+            setattr(p, k, v)
+        else:
+            raise TypeError(f"fuse_params: no field {k!r} in sfm_fuse_params")
+    return p
+
+
+def _fuse_buffers(torch, device, k, N):
+    """Output tensors of one fuse_chain call in the order of sfm_fuse_out, for k pairs with N records in all."""
+    e = lambda n, dt: torch.empty(int(n), dtype=dt, device=device)
+    i32, f32 = torch.int32, torch.float32
+    return (e(13 * k, f32), e(k, i32), e(24 * k, f32), e(N, i32), e(N + 1, i32), e(2 * N, i32), e(2 * N, i32), e(4 * N, f32),
+            e(N, torch.uint8), e(N, f32), e(8, i32))
+
+
+def fuse_chain_enqueue(ctx, pairs, links, params, outs):
+    """sfm_fuse_chain (enqueue only).  pairs: one ImagePair, or one (ImagePair, points, valid, pose) tuple of device tensors /
+    pointers / None, per pair of the chain; links: one (index, sim, inlier, err, report) tuple of device tensors / pointers per
+    link (len(pairs) - 1 of them); outs: device tensors / pointers in the order of sfm_fuse_out (err may be None)."""
+    k = len(pairs)
+    assert len(links) == max(k - 1, 0), "one link between every two neighbours"
+    pin = (FusePairIn * max(k, 1))()
+    for i, x in enumerate(pairs):
+        x = x if isinstance(x, tuple) else (x, None, None, None)
+        pin[i] = FusePairIn(x[0]._h.value, *[_ptr(t) for t in x[1:]])
+    lin = (FuseLinkIn * max(k - 1, 1))(*[FuseLinkIn(*[_ptr(t) for t in x]) for x in links])
+    o = FuseOut(*[_ptr(t) for t in outs]) if outs is not None else None
+    _check(_lib.sfm_fuse_chain(ctx._h if ctx is not None else None, pin, k, lin, C.byref(params), C.byref(o) if o is not None else None), "sfm_fuse_chain")
+
+
+def fuse_chain(pairs, indices, align_outs, overrides=None, **kw):
+    """A chain of aligned pairs fused into tracks and one point per track.  pairs: the ImagePairs of the chain (pair i = views i,
+    i + 1); indices: the device index tensor of every link; align_outs: per link the device tensors (sim, inlier, err, counts,
+    report) an align_to_enqueue / align_pairs_enqueue call filled (counts is not read); overrides: None, or per pair a (points,
+    valid, pose) tuple of device tensors / None; kw are FuseParams fields.  Allocates the outputs, waits once and returns a dict
+    of numpy arrays trimmed to the T tracks and M observations: frames (k, 13), root (k), cams (k, 2, 12), track (N),
+    track_offset (T + 1), obs_cam (M), obs_record (M), points (4, T), flags (T), err (T), and counts as a dict."""
+    params = fuse_params(**kw)
+    k = len(pairs)
+    if k == 0:                                                                 # no pair, no context: nothing to enqueue
+        return dict(counts=dict.fromkeys(FUSE_COUNTS, 0))
+    ctx = pairs[0].ctx
+    dev = torch.device("cuda", ctx.device)
+    N = sum(p.num_points for p in pairs)
+    outs = _fuse_buffers(torch, dev, k, N)
+    pin = [(p,) + tuple(overrides[i]) if overrides is not None and overrides[i] is not None else p for i, p in enumerate(pairs)]
+    links = [(indices[i], a[0], a[1], a[2], a[4]) for i, a in enumerate(align_outs)]
+    fuse_chain_enqueue(ctx, pin, links, params, outs)
+    ctx.synchronize()
+    return _fuse_results(outs, k, N)
+
+
+def _fuse_results(outs, k, N):
+    """The tensors of _fuse_buffers -> the dict fuse_chain returns."""
+    frames, root, cams, track, off, ocam, orec, pts, flags, err, counts = (t.cpu().numpy() for t in outs)
+    T, M = int(counts[0]), int(counts[1])
+    return dict(frames=frames.reshape(k, 13), root=root, cams=cams.reshape(k, 2, 12), track=track, track_offset=off[:T + 1].copy(),
+                obs_cam=ocam[:M].copy(), obs_record=orec[:M].copy(), points=pts.reshape(4, N)[:, :T].copy(), flags=flags[:T].copy(),
+                err=err[:T].copy(), counts={name: int(counts[i]) for i, name in enumerate(FUSE_COUNTS)})
 
 
 def sift_temp_layout(width, height, num_octaves=5, scale_up=False):

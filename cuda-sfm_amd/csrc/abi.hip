@@ -1,6 +1,7 @@
 // abi.hip -- implementation of the C ABI declared in include/sfm_amd.h (its two host-side drivers: views.hip, pairs.hip).
 #include "common.hpp"
 #include "device_math.hpp"
+#include "fuse_math.hpp"
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -222,6 +223,8 @@ static int ctx_destroy_now(sfm_ctx *ctx)
     job_array_free(ctx->view_points_jobs);
     job_array_free(ctx->adjust_jobs);
     job_array_free(ctx->align_jobs);
+    job_array_free(ctx->fuse_jobs);
+    if (ctx->fuse_ws) (void)hipFree(ctx->fuse_ws);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     for (auto &t : ctx->tev) for (hipEvent_t e : t) if (e) (void)hipEventDestroy(e);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -1499,6 +1502,113 @@ int sfm_align_pairs(sfm_pair *const *as, sfm_pair *const *bs, int num_links, con
     std::vector<AlignInputs> in((size_t)num_links);
     for (int i = 0; i < num_links; ++i) in[(size_t)i] = align_inputs(as[i], bs[i], d_indices[i], *p);
     return launch_align_pairs(ctx, as, bs, num_links, in.data(), *p, outs);
+}
+
+// ---- a chain of aligned pairs fused into tracks and one point per track (fuse.hip) -----------------
+void sfm_fuse_default_params(sfm_fuse_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->threshold_px = 4.0f;
+    p->max_iterations = 5;
+    p->huber_px = 1.0f;
+    p->min_rel_decrease = 1e-6f;
+    p->initial_lambda = 1e-3f;
+}
+
+int sfm_fuse_chain(sfm_ctx *ctx, const sfm_fuse_pair_in *pairs, int num_pairs, const sfm_fuse_link_in *links, const sfm_fuse_params *p,
+                   const sfm_fuse_out *out)
+{
+    // the checks that need no device first, all of them before anything is enqueued
+    SFM_REQUIRE(p, SFM_E_INVALID, "null params");
+    SFM_REQUIRE(num_pairs >= 0 && num_pairs <= 4096, SFM_E_INVALID, "num_pairs %d outside 0..4096", num_pairs);
+    int rc = check_lm_params(*p, "sfm_fuse_params");
+    if (rc != SFM_OK) return rc;
+    SFM_REQUIRE(p->max_iterations <= 50, SFM_E_INVALID, "max_iterations %d outside 0..50", p->max_iterations);
+    SFM_REQUIRE(isfinite(p->threshold_px) && p->threshold_px > 0.0f, SFM_E_INVALID, "threshold_px must be finite and > 0");
+    if (num_pairs == 0) return SFM_OK;
+    SFM_REQUIRE(ctx && pairs && out, SFM_E_INVALID, "null context, pair list or out");
+    SFM_REQUIRE(links || num_pairs == 1, SFM_E_INVALID, "null link list");
+    SFM_REQUIRE(out->d_frames && out->d_root && out->d_cams && out->d_track && out->d_track_offset && out->d_obs_cam && out->d_obs_record &&
+                out->d_points && out->d_flags && out->d_counts, SFM_E_INVALID, "every buffer of sfm_fuse_out but d_err is required");
+    long long total = 0;
+    for (int i = 0; i < num_pairs; ++i) {
+        SFM_REQUIRE(pairs[i].pair, SFM_E_INVALID, "pairs[%d]: null pair", i);
+        SFM_REQUIRE(pairs[i].pair->ctx == ctx, SFM_E_INVALID, "pairs[%d]: the pair belongs to another context", i);
+        SFM_REQUIRE(pairs[i].d_points || !pairs[i].d_valid, SFM_E_INVALID, "pairs[%d]: d_valid needs d_points", i);
+        total += pairs[i].pair->n;
+    }
+    SFM_REQUIRE(total <= (1ll << 26), SFM_E_INVALID, "%lld records in all: more than 2^26", total);
+    for (int i = 0; i + 1 < num_pairs; ++i)
+        SFM_REQUIRE(links[i].d_index && links[i].d_sim && links[i].d_inlier && links[i].d_err && links[i].d_report, SFM_E_INVALID,
+                    "links[%d]: d_index, d_sim, d_inlier, d_err and d_report are required", i);
+    {
+        std::vector<std::pair<const sfm_pair *, int>> sorted((size_t)num_pairs);
+        for (int i = 0; i < num_pairs; ++i) sorted[(size_t)i] = { pairs[i].pair, i };
+        std::sort(sorted.begin(), sorted.end());
+        for (int k = 1; k < num_pairs; ++k)
+            SFM_REQUIRE(sorted[(size_t)k].first != sorted[(size_t)k - 1].first, SFM_E_INVALID, "pairs[%d]: the pair is listed twice", sorted[(size_t)k].second);
+    }
+    {
+        // no output on an input or on another output: all ranges sorted by their start, one sweep (sfm_adjust_views')
+        struct Range { uintptr_t lo, hi; bool out; int who; const char *name; };
+        std::vector<Range> r;
+        r.reserve((size_t)num_pairs * 8 + 11);
+        auto add = [&](const void *ptr, size_t bytes, bool is_out, int who, const char *name) {
+            if (ptr && bytes) r.push_back({ reinterpret_cast<uintptr_t>(ptr), reinterpret_cast<uintptr_t>(ptr) + bytes, is_out, who, name });
+        };
+        const size_t N = (size_t)total, k = (size_t)num_pairs;
+        for (int i = 0; i < num_pairs; ++i) {
+            const size_t n = (size_t)pairs[i].pair->n;
+            add(pairs[i].d_points, n * 16, false, i, "pairs[%d].d_points"); add(pairs[i].d_valid, n, false, i, "pairs[%d].d_valid");
+            add(pairs[i].d_pose, 48, false, i, "pairs[%d].d_pose");
+            if (i + 1 < num_pairs) {
+                add(links[i].d_index, n * 4, false, i, "links[%d].d_index"); add(links[i].d_sim, 52, false, i, "links[%d].d_sim");
+                add(links[i].d_inlier, n, false, i, "links[%d].d_inlier"); add(links[i].d_err, n * 4, false, i, "links[%d].d_err");
+                add(links[i].d_report, sizeof(sfm_align_report), false, i, "links[%d].d_report");
+            }
+        }
+        add(out->d_frames, k * 52, true, -1, "out.d_frames"); add(out->d_root, k * 4, true, -1, "out.d_root");
+        add(out->d_cams, k * 96, true, -1, "out.d_cams"); add(out->d_track, N * 4, true, -1, "out.d_track");
+        add(out->d_track_offset, (N + 1) * 4, true, -1, "out.d_track_offset"); add(out->d_obs_cam, N * 8, true, -1, "out.d_obs_cam");
+        add(out->d_obs_record, N * 8, true, -1, "out.d_obs_record"); add(out->d_points, N * 16, true, -1, "out.d_points");
+        add(out->d_flags, N, true, -1, "out.d_flags"); add(out->d_err, N * 4, true, -1, "out.d_err");
+        add(out->d_counts, 32, true, -1, "out.d_counts");
+        std::sort(r.begin(), r.end(), [](const Range &x, const Range &y) { return x.lo < y.lo; });
+        const Range *far_any = nullptr, *far_out = nullptr;     // the ranges seen so far that end last: any, and among the outputs
+        for (const Range &x : r) {
+            const Range *hit = x.out ? far_any : far_out;
+            if (hit && hit->hi > x.lo) {
+                char a[48], b[48];
+                snprintf(a, sizeof(a), x.name, x.who); snprintf(b, sizeof(b), hit->name, hit->who);
+                SFM_REQUIRE(false, SFM_E_INVALID, "%s overlaps %s", x.out ? a : b, x.out ? b : a);
+            }
+            if (!far_any || x.hi > far_any->hi) far_any = &x;
+            if (x.out && (!far_out || x.hi > far_out->hi)) far_out = &x;
+        }
+    }
+    for (int i = 0; i < num_pairs; ++i) SFM_FLUSH(pairs[i].pair);
+    for (int i = 0; i < num_pairs; ++i) {
+        const uint32_t need = (pairs[i].d_points && pairs[i].d_pose) ? kPoints : kPoints | kRefined;
+        SFM_REQUIRE(pairs[i].pair->state.has(need), SFM_E_STATE, "pairs[%d]: %s", i, pair_stage_hint(pairs[i].pair->state.missing(need)));
+    }
+    SFM_HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<FusePair> fp((size_t)num_pairs);
+    for (int i = 0; i < num_pairs; ++i) {
+        const sfm_pair *pr = pairs[i].pair;
+        FusePair &f = fp[(size_t)i];
+        memset(&f, 0, sizeof(f));
+        f.points = pairs[i].d_points ? pairs[i].d_points : pr->d_rpoints;
+        f.valid = pairs[i].d_points ? pairs[i].d_valid : reproj_flags(pr, pr->d_rreproj);
+        f.X0 = pr->d_X[0]; f.X1 = pr->d_X[1]; f.K = pr->d_K;
+        f.pose = pairs[i].d_pose ? pairs[i].d_pose : pr->d_rstate + refine_pose_offset();
+        f.pose_rows = pairs[i].d_pose ? 3 : 4;
+        f.n = pr->n; f.ld = pr->ld;
+        if (i + 1 < num_pairs) {
+            f.index = links[i].d_index; f.sim = links[i].d_sim; f.inlier = links[i].d_inlier; f.err = links[i].d_err; f.report = links[i].d_report;
+        }
+    }
+    return launch_fuse_chain(ctx, fp.data(), num_pairs, *p, *out);                           // reads the pairs: no stage changes
 }
 
 // ---- accessors ------------------------------------------------------------------------------------

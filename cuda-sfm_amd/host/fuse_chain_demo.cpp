@@ -1,0 +1,103 @@
+// fuse_chain_demo.cpp -- a chain of overlapping view pairs fused into tracks and one point per track (SfM::fuse_chain of sfm.h:
+// sfm_align_pairs, then sfm_fuse_chain):
+//   per pair: features -> MatchSiftData -> SfM::Image_pair -> fillXU -> estimateE; ONE refine_pairs over all of them; ONE
+//   fuse_chain over the chain (pair i -> pair i + 1).
+// The arguments are align_pairs_demo's:
+//     fuse_chain_demo <k> <a1.bin> .. <ak.bin> <b1.bin> .. <bk.bin> [cloud.ply]
+// a_i / b_i: files of raw SiftPoint records of pair i's first / second view; a_{i+1} must hold the records of b_i's view.
+// One `fuse:` line, then the fused cloud of the first segment -- one point per track, where align_pairs_demo writes a feature
+// once per pair that sees it -- as a PLY (default fused_cloud.ply).  Plain C++: needs only the facade headers and libsfm_amd.so.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <memory>
+#include <vector>
+
+#include "sfm.h"
+#include "sfm_io.h"
+
+static std::vector<SiftPoint> read_sift(const char *path)
+{
+    FILE *f = std::fopen(path, "rb");
+    if (!f) { std::perror(path); std::exit(2); }
+    std::fseek(f, 0, SEEK_END);
+    const long bytes = std::ftell(f);
+    std::fseek(f, 0, SEEK_SET);
+    std::vector<SiftPoint> v((size_t)bytes / sizeof(SiftPoint));
+    if (!v.empty() && std::fread(v.data(), sizeof(SiftPoint), v.size(), f) != v.size()) { std::perror("fread"); std::exit(2); }
+    std::fclose(f);
+    return v;
+}
+
+static void upload(SiftData &data, const std::vector<SiftPoint> &f, const char *path)
+{
+    InitSiftData(data, 32768, true, true);
+    if (f.size() > 32768) { std::fprintf(stderr, "%s: more than 32768 records\n", path); std::exit(2); }
+    data.numPts = (int)f.size();
+    std::copy(f.begin(), f.end(), data.h_data);
+    UploadSiftData(data);                                   // stands in for ExtractSift
+}
+
+int main(int argc, char **argv)
+{
+    const int count = argc > 1 ? std::atoi(argv[1]) : 0;
+    if (count < 1 || (argc != 2 + 2 * count && argc != 3 + 2 * count)) {
+        std::fprintf(stderr, "usage: %s k a1.bin .. ak.bin b1.bin .. bk.bin [cloud.ply]   (k >= 1)\n", argv[0]);
+        return 2;
+    }
+    const char *ply = argc == 3 + 2 * count ? argv[2 + 2 * count] : "fused_cloud.ply";
+    const unsigned w = 720, h = 576;                        // the dino frames
+    float K[9] = { 2360.0f, 0, (float)(w / 2.0), 0, 2360, (float)(h / 2.0), 0, 0, 1 };
+    float inv_K[9] = { (float)(1.0 / 2360), 0, (float)(-(w / 2.0) / 2360), 0, (float)(1.0 / 2360), (float)(-(h / 2.0) / 2360), 0, 0, 1 };
+
+    std::vector<std::vector<SiftPoint>> fa, fb;
+    for (int k = 0; k < count; ++k) { fa.push_back(read_sift(argv[2 + k])); fb.push_back(read_sift(argv[2 + count + k])); }
+    for (int k = 0; k + 1 < count; ++k) {                   // a link follows match indices: b_k and a_{k+1} are one view's records
+        const std::vector<SiftPoint> &x = fb[(size_t)k], &y = fa[(size_t)k + 1];
+        bool same = x.size() == y.size();
+        for (size_t j = 0; same && j < x.size(); ++j) same = x[j].xpos == y[j].xpos && x[j].ypos == y[j].ypos;
+        if (!same) {
+            std::fprintf(stderr, "%s and %s are not the records of one view (count or positions differ)\n", argv[2 + count + k], argv[3 + k]);
+            return 2;
+        }
+    }
+
+    InitCuda(0);
+    std::vector<SiftData> sift((size_t)2 * count);
+    std::vector<std::unique_ptr<SfM::Image_pair>> owned;
+    std::vector<SfM::Image_pair *> pairs;
+    std::vector<SiftPoint *> records;
+    for (int k = 0; k < count; ++k) {
+        SiftData &s1 = sift[(size_t)2 * k], &s2 = sift[(size_t)2 * k + 1];
+        upload(s1, fa[(size_t)k], argv[2 + k]);
+        upload(s2, fb[(size_t)k], argv[2 + count + k]);
+        MatchSiftData(s1, s2);
+        owned.emplace_back(new SfM::Image_pair(K, inv_K, 2, s1.numPts));
+        owned.back()->fillXU(s1.d_data);
+        owned.back()->estimateE();
+        pairs.push_back(owned.back().get());
+        records.push_back(s1.d_data);
+    }
+    SfM::refine_pairs(pairs.data(), count);
+    const SfM::FusedModel model = SfM::fuse_chain(pairs.data(), records.data(), count);
+    std::printf("fuse: %d tracks, %d observations, %d refined, %d kept, %d segments, longest track %d views\n", model.tracks, model.observations,
+                model.refined, model.kept, model.segments, model.longest_track);
+
+    // the first segment's tracks: one point each
+    const int T = model.tracks;
+    std::vector<float> cloud;                               // x, y, z per point
+    for (int t = 0; t < T; ++t) {
+        const int pair = model.obs_cam[(size_t)model.track_offset[(size_t)t]] >> 1;
+        if (model.root[(size_t)pair] != 0) continue;
+        for (int c = 0; c < 3; ++c) cloud.push_back(model.points[(size_t)c * T + t]);
+    }
+    const int total = (int)(cloud.size() / 3);
+    std::vector<float> cols((size_t)4 * total, 1.0f);       // WritePLY's 4 x N layout
+    for (int j = 0; j < total; ++j)
+        for (int c = 0; c < 3; ++c) cols[(size_t)c * total + j] = cloud[(size_t)3 * j + c];
+    const int written = WritePLY(ply, cols.data(), total);
+    std::printf("fused cloud: %d points -> %s\n", written, ply);
+    owned.clear();
+    for (SiftData &s : sift) FreeSiftData(s);
+    return 0;
+}

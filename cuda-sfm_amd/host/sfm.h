@@ -513,6 +513,107 @@ inline std::vector<PairLink> align_pairs(Image_pair *const *as, Image_pair *cons
     return results;
 }
 
+// what fuse_chain returns, in host memory: the chain of pairs (pair i = views i, i + 1) as one model per segment
+struct FusedModel {
+    std::vector<PairLink> links;        // count - 1: the links the chain was fused over, as align_pairs gives them
+    std::vector<Sim3> frames;           // count: pair i's frame into its segment's root frame
+    std::vector<int32_t> root;          // count: the first pair of pair i's segment
+    std::vector<float> cams;            // 24 x count: [R|t] of pair i's camera 1, then camera 2, in the root frame
+    std::vector<int32_t> track;         // N = sum of the pairs' records: the track of node (pair, record), -1 = none
+    std::vector<int32_t> track_offset;  // T + 1: CSR offsets into obs_cam / obs_record
+    std::vector<int32_t> obs_cam;       // M: 2 * pair + (0 | 1)
+    std::vector<int32_t> obs_record;    // M: the record of that pair
+    std::vector<float> points;          // 4 x T (leading dimension T): one point per track in its segment's root frame
+    std::vector<uint8_t> flags;         // T: SFM_FUSE_REFINED / SFM_FUSE_KEPT
+    std::vector<float> err;             // T: largest pixel error over the track's views
+    int tracks = 0, observations = 0, refined = 0, kept = 0, segments = 0, longest_track = 0;
+};
+
+// A chain of `count` refined pairs, pair i + 1's first view being pair i's second, fused into tracks and one point per track
+// (sfm_align_pairs over the count - 1 links, then sfm_fuse_chain): data[i] = the records pairs[i]'s fillXU took.  One wait at
+// the end.
+inline FusedModel fuse_chain(Image_pair *const *pairs, SiftPoint *const *data, int count, int max_iterations = 5, float threshold_px = 4.0f)
+{
+    FusedModel r;
+    if (count <= 0) return r;
+    sfm_ctx *ctx = sfm_facade::context();
+    sfm_align_params ap;
+    sfm_align_default_params(&ap);
+    sfm_fuse_params fp;
+    sfm_fuse_default_params(&fp);
+    fp.max_iterations = max_iterations;
+    fp.threshold_px = threshold_px;
+    const int nl = count - 1;
+    size_t N = 0;
+    for (int i = 0; i < count; ++i) N += pairs[i] ? (size_t)pairs[i]->numPoints() : 0;
+    std::vector<sfm_pair *> ha, hb;
+    std::vector<std::unique_ptr<detail::AlignScratch>> scratch;
+    std::vector<std::unique_ptr<detail::DeviceBlock>> errs;
+    std::vector<const int32_t *> indices;
+    std::vector<sfm_align_out> aouts;
+    for (int i = 0; i < nl; ++i) {
+        ha.push_back(pairs[i] ? pairs[i]->handle() : nullptr);
+        hb.push_back(pairs[i + 1] ? pairs[i + 1]->handle() : nullptr);
+        const int n = pairs[i] ? pairs[i]->numPoints() : 0;
+        scratch.emplace_back(new detail::AlignScratch(n));
+        errs.emplace_back(new detail::DeviceBlock(4 * (size_t)n + 16));
+        SFM_FACADE_CALL(sfm_align_index_from_matches(ctx, reinterpret_cast<const sfm_sift_point *>(data[i]), n, 0.85f, 0.95f, scratch.back()->index()));
+        indices.push_back(scratch.back()->index());
+        sfm_align_out o = scratch.back()->out();
+        o.d_err = reinterpret_cast<float *>(errs.back()->p);
+        aouts.push_back(o);
+    }
+    if (nl > 0) SFM_FACADE_CALL(sfm_align_pairs(ha.data(), hb.data(), nl, indices.data(), &ap, aouts.data()));
+    std::vector<sfm_fuse_pair_in> pin((size_t)count);
+    std::vector<sfm_fuse_link_in> lin((size_t)(nl > 0 ? nl : 1));
+    for (int i = 0; i < count; ++i) { pin[(size_t)i].pair = pairs[i] ? pairs[i]->handle() : nullptr; pin[(size_t)i].d_points = nullptr; pin[(size_t)i].d_valid = nullptr; pin[(size_t)i].d_pose = nullptr; }
+    for (int i = 0; i < nl; ++i) {
+        lin[(size_t)i].d_index = indices[(size_t)i]; lin[(size_t)i].d_sim = aouts[(size_t)i].d_sim; lin[(size_t)i].d_inlier = aouts[(size_t)i].d_inlier;
+        lin[(size_t)i].d_err = aouts[(size_t)i].d_err; lin[(size_t)i].d_report = aouts[(size_t)i].d_report;
+    }
+    // the outputs in ONE block, every array at a multiple of 16 bytes
+    const size_t k = (size_t)count;
+    auto up = [](size_t b) { return (b + 15) / 16 * 16; };
+    const size_t sizes[11] = { 52 * k, 4 * k, 96 * k, 4 * N, 4 * (N + 1), 8 * N, 8 * N, 16 * N, N, 4 * N, 32 };
+    size_t at[12];
+    at[0] = 0;
+    for (int q = 0; q < 11; ++q) at[q + 1] = at[q] + up(sizes[q] + 1);
+    detail::DeviceBlock mem(at[11]);
+    sfm_fuse_out o;
+    o.d_frames = reinterpret_cast<float *>(mem.p + at[0]); o.d_root = reinterpret_cast<int32_t *>(mem.p + at[1]);
+    o.d_cams = reinterpret_cast<float *>(mem.p + at[2]); o.d_track = reinterpret_cast<int32_t *>(mem.p + at[3]);
+    o.d_track_offset = reinterpret_cast<int32_t *>(mem.p + at[4]); o.d_obs_cam = reinterpret_cast<int32_t *>(mem.p + at[5]);
+    o.d_obs_record = reinterpret_cast<int32_t *>(mem.p + at[6]); o.d_points = reinterpret_cast<float *>(mem.p + at[7]);
+    o.d_flags = reinterpret_cast<uint8_t *>(mem.p + at[8]); o.d_err = reinterpret_cast<float *>(mem.p + at[9]);
+    o.d_counts = reinterpret_cast<int32_t *>(mem.p + at[10]);
+    SFM_FACADE_CALL(sfm_fuse_chain(ctx, pin.data(), count, lin.data(), &fp, &o));
+    for (int i = 0; i < nl; ++i) r.links.push_back(scratch[(size_t)i]->download());        // (the first download waits for everything)
+    int32_t counts[8];
+    SFM_FACADE_CALL(sfm_copy_to_host(ctx, counts, o.d_counts, sizeof(counts)));
+    r.tracks = counts[0]; r.observations = counts[1]; r.refined = counts[2]; r.kept = counts[3]; r.segments = counts[4]; r.longest_track = counts[5];
+    const size_t T = (size_t)r.tracks, M = (size_t)r.observations;
+    std::vector<float> frames(13 * k), pts(4 * N);
+    r.root.resize(k); r.cams.resize(24 * k); r.track.resize(N); r.track_offset.resize(T + 1); r.obs_cam.resize(M); r.obs_record.resize(M);
+    r.points.resize(4 * T); r.flags.resize(T); r.err.resize(T);
+    SFM_FACADE_CALL(sfm_copy_to_host(ctx, frames.data(), o.d_frames, 52 * k));
+    SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.root.data(), o.d_root, 4 * k));
+    SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.cams.data(), o.d_cams, 96 * k));
+    if (N) SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.track.data(), o.d_track, 4 * N));
+    SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.track_offset.data(), o.d_track_offset, 4 * (T + 1)));
+    if (M) {
+        SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.obs_cam.data(), o.d_obs_cam, 4 * M));
+        SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.obs_record.data(), o.d_obs_record, 4 * M));
+    }
+    if (T) {
+        SFM_FACADE_CALL(sfm_copy_to_host(ctx, pts.data(), o.d_points, 16 * N));
+        for (int c = 0; c < 4; ++c) std::copy(pts.begin() + (size_t)c * N, pts.begin() + (size_t)c * N + T, r.points.begin() + (size_t)c * T);
+        SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.flags.data(), o.d_flags, T));
+        SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.err.data(), o.d_err, 4 * T));
+    }
+    for (size_t i = 0; i < k; ++i) r.frames.push_back(Sim3::from(frames.data() + 13 * i));
+    return r;
+}
+
 } // namespace SfM
 
 #endif

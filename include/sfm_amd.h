@@ -562,6 +562,65 @@ int sfm_align_pair(sfm_pair *a, sfm_pair *b, const int32_t *d_index, const sfm_a
 int sfm_align_pairs(sfm_pair *const *as, sfm_pair *const *bs, int num_links, const int32_t *const *d_indices,
                     const sfm_align_params *p, const sfm_align_out *outs);                           /* enqueue only */
 
+/* ---- fusing a chain of aligned pairs: tracks and one point per track ------------------------------
+ * Pairs 0 .. k-1, pair i = (view i, view i + 1), and the k - 1 links between neighbours (what sfm_align_pairs took and gave).
+ * A link is valid when its report's status is not SFM_REFINE_DEGENERATE, its 13 floats are finite and s > 0; an invalid link
+ * cuts the chain: pair i + 1 starts a new segment whose root frame is its own, and no track crosses the cut.  d_frames carries
+ * every pair into its segment's root frame (the links' inverses composed in fp64 along the chain, rounded once), d_cams holds
+ * both cameras of every pair in that frame.
+ * Node (i, j) = record j of pair i, live when its point is usable (the registration's point test).  Record j of pair i is joined
+ * to record d_index[j] of pair i + 1 when the link is valid, d_inlier[j] != 0, the index is in range, d_err[j] is finite and
+ * both nodes are live; where several records name the same target, the smallest d_err wins, then the lowest record.  The
+ * tracks are the resulting paths, numbered by their first node (by pair, then by record).  A track over pairs i .. i + L - 1
+ * has L + 1 observations ordered by view: the X0 column of its record in each pair (slot 0), then the X1 column of its last
+ * record (slot 1).  Its point starts at the mean of its pairs' points in the root frame and is refined by sfm_triangulate_view's
+ * point Levenberg-Marquardt over all its views; it is stored when every view passes sfm_register_view's inlier test at
+ * threshold_px, else the start point is.
+ * The call READS the pairs and writes only the caller's buffers: no stage, buffer id or getter belongs to it.  Integer atomics
+ * only: two calls give the same bytes. */
+#define SFM_FUSE_REFINED 1   /* the LM result passed the test in every view of the track: stored                   */
+#define SFM_FUSE_KEPT    2   /* it failed in some view: the start point (above) is stored                          */
+typedef struct sfm_fuse_params {
+    float   threshold_px;                                 /* acceptance, the registration's inlier test; default 4.0 */
+    int32_t max_iterations;                               /* point LM, accepted + rejected, 0..50; default 5         */
+    float   huber_px, min_rel_decrease, initial_lambda;   /* 1.0 / 1e-6 / 1e-3                                        */
+    int32_t reserved[4];                                  /* must be zero (else SFM_E_INVALID)                        */
+} sfm_fuse_params;
+typedef struct sfm_fuse_pair_in {      /* HOST array, one per pair; pair i = (view i, view i + 1)                    */
+    sfm_pair      *pair;
+    const float   *d_points;           /* optional DEVICE 4 x n_i; NULL = refined points + the refinement's used flags */
+    const uint8_t *d_valid;            /* optional, only with d_points (NULL: every point)                            */
+    const float   *d_pose;             /* optional DEVICE float[12], R row-major then t: camera 2; NULL = refined pose */
+} sfm_fuse_pair_in;
+typedef struct sfm_fuse_link_in {      /* HOST array, one per link i: pair i -> pair i + 1; all DEVICE, all required  */
+    const int32_t *d_index;            /* what sfm_align_pairs took                                                   */
+    const float   *d_sim;              /* first 13 floats of sfm_align_out.d_sim                                      */
+    const uint8_t *d_inlier;           /* sfm_align_out.d_inlier                                                      */
+    const float   *d_err;              /* sfm_align_out.d_err                                                         */
+    const sfm_align_report *d_report;
+} sfm_fuse_link_in;
+typedef struct sfm_fuse_out {          /* DEVICE buffers of the caller, N = sum of n_i; all required unless marked    */
+    float   *d_frames;     /* 13 x k: (s, R, t) carrying pair i's frame into its segment's root frame                 */
+    int32_t *d_root;       /* k: the first pair of pair i's segment                                                   */
+    float   *d_cams;       /* 24 x k: [R|t] (R 9 row-major, t 3) of pair i's camera 1, then camera 2, in the root frame */
+    int32_t *d_track;      /* N: track of node (pair i, record j) at offset(i) + j, -1 = none                         */
+    int32_t *d_track_offset;   /* N + 1: CSR offsets, entries [0 .. T] written                                        */
+    int32_t *d_obs_cam;    /* 2N: per observation 2 * pair + (0 | 1): the slot of d_cams                              */
+    int32_t *d_obs_record; /* 2N: the record of that pair whose X0 (slot 0) or X1 (slot 1) column is the observation  */
+    float   *d_points;     /* 4 x N, leading dimension N: column t = (X, Y, Z, 1) of track t in its segment's root frame */
+    uint8_t *d_flags;      /* N: SFM_FUSE_* per track                                                                 */
+    float   *d_err;        /* N, optional: largest pixel error over the track's views at the LM result                */
+    int32_t *d_counts;     /* 8: tracks T, observations M, REFINED, KEPT, segments, longest track (views), 0, 0       */
+} sfm_fuse_out;
+void sfm_fuse_default_params(sfm_fuse_params *p);
+/* pairs: HOST array of num_pairs (0..4096) entries, N at most 2^26; links: HOST array of num_pairs - 1 entries (may be NULL for
+ * fewer than two pairs).  Zero pairs is SFM_OK and writes nothing.  Every pair belongs to ctx and is listed once; each needs
+ * points, and the refinement unless both d_points and d_pose are given (SFM_E_STATE).  No output may overlap an input or another
+ * output.  Every check precedes the first enqueue: on SFM_E_INVALID / SFM_E_STATE (the text names pairs[i] or links[i]) nothing
+ * is written.  The work buffers belong to the context. */
+int  sfm_fuse_chain(sfm_ctx *ctx, const sfm_fuse_pair_in *pairs, int num_pairs, const sfm_fuse_link_in *links,
+                    const sfm_fuse_params *p, const sfm_fuse_out *out);          /* enqueue only */
+
 /* ---- accessors (the reference keeps these private; needed for parity checks) ------------------ */
 #define SFM_BUF_X0      0   /* float 3 x ld   normalised coords image 1 (ld = sfm_pair_ld)   */
 #define SFM_BUF_X1      1
