@@ -125,7 +125,7 @@ $(GEOMTEST): tests/cpp/geom_test.cpp $(PKG)/host/geomFuncs.h $(PKG)/host/sfm_io.
 
 # CPU-only: the host-compiled arithmetic check of the non-GPU tests (the fakeccl target, which needs the gfx950 build and the RCCL
 # header, is a target of its own and part of `all`)
-hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so
+hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so
 
 # TEST HARNESS: comm.cpp linked against a shared-memory stand-in for the nine RCCL calls it makes, so that a 1-GPU box can run the
 # exchange code with two real ranks (tests/test_gpu_fakeccl.py); the product's libsfm_amd_rccl.so is linked against librccl
@@ -180,8 +180,13 @@ tests/hostcheck/libpairsplancheck.so: tests/hostcheck/pairsplancheck.hip $(CSRC)
 tests/hostcheck/libpairstatecheck.so: tests/hostcheck/pairstatecheck.cpp $(CSRC)/pair_state.hpp
 	g++ -O2 -std=c++17 -Wall -fPIC -shared -o $@ $<
 
+# the buffer-range rules of the batched calls (buffer_ranges.hpp) and the job order of their launches (job_order.hpp), built by
+# the plain host compiler for tests/test_buffer_ranges_host.py
+tests/hostcheck/libbufferrangescheck.so: tests/hostcheck/bufferrangescheck.cpp $(CSRC)/buffer_ranges.hpp $(CSRC)/job_order.hpp
+	g++ -O2 -std=c++17 -Wall -fPIC -shared -o $@ $<
+
 clean:
-	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(APDEMO) $(FCDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
+	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(APDEMO) $(FCDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all ab oracle hostcheck fakeccl clean

@@ -1,5 +1,6 @@
 // abi.hip -- implementation of the C ABI declared in include/sfm_amd.h (its two host-side drivers: views.hip, pairs.hip).
 #include "common.hpp"
+#include "buffer_ranges.hpp"
 #include "device_math.hpp"
 #include "fuse_math.hpp"
 #include <stdarg.h>
@@ -10,7 +11,6 @@
 #include <utility>
 #include <vector>
 #include <algorithm>
-#include <functional>
 #include <initializer_list>
 
 namespace sfm {
@@ -68,12 +68,12 @@ static int alloc_group(std::initializer_list<BufSpec> bufs)
 static size_t reproj_bytes(size_t points) { return points * 5; }
 static const uint8_t *reproj_flags(const sfm_pair *pair, const float *reproj) { return reinterpret_cast<const uint8_t *>(reproj + pair->n); }
 
-// the Levenberg-Marquardt fields sfm_refine_params and sfm_register_params share
+// the Levenberg-Marquardt fields every params struct of a solver shares; most: the largest max_iterations the call takes
 template <typename Params>
-static int check_lm_params(const Params &p, const char *name)
+static int check_lm_params(const Params &p, const char *name, int most = 200)
 {
     SFM_REQUIRE(p.reserved[0] == 0 && p.reserved[1] == 0 && p.reserved[2] == 0 && p.reserved[3] == 0, SFM_E_INVALID, "%s.reserved[] must be zero", name);
-    SFM_REQUIRE(p.max_iterations >= 0 && p.max_iterations <= 200, SFM_E_INVALID, "max_iterations %d outside 0..200", p.max_iterations);
+    SFM_REQUIRE(p.max_iterations >= 0 && p.max_iterations <= most, SFM_E_INVALID, "max_iterations %d outside 0..%d", p.max_iterations, most);
     SFM_REQUIRE(p.huber_px >= 0.0f && isfinite(p.huber_px), SFM_E_INVALID, "huber_px must be finite and >= 0");
     SFM_REQUIRE(isfinite(p.min_rel_decrease) && p.min_rel_decrease >= 0.0f, SFM_E_INVALID, "min_rel_decrease must be finite and >= 0");
     SFM_REQUIRE(isfinite(p.initial_lambda) && p.initial_lambda >= 0.0f, SFM_E_INVALID, "initial_lambda must be finite and >= 0");
@@ -85,6 +85,77 @@ static int copy_out(sfm_pair *pair, void *h_dst, const void *d_src, size_t bytes
     SFM_FLUSH(pair);
     SFM_HIP_TRY(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, pair->ctx->stream));
     SFM_HIP_TRY(hipStreamSynchronize(pair->ctx->stream));
+    return SFM_OK;
+}
+
+// ---- the pair list of a batched call: ONE gate for sfm_refine_pairs, sfm_register_views, sfm_triangulate_views, sfm_adjust_views,
+// sfm_align_pairs (two lists, its entries are links[i]) and sfm_fuse_chain.  Two phases that every caller keeps apart:
+// list_entries_present looks at the list alone and goes with the checks that read no pair; the three below it read the pairs and
+// come after all of those.  The messages that differ between the calls are arguments: a format that takes the entry's index.
+static int list_entries_present(sfm_pair *const *pairs, int count, const char *null_fmt)
+{
+    for (int i = 0; i < count; ++i) SFM_REQUIRE(pairs[i], SFM_E_INVALID, null_fmt, i);
+    return SFM_OK;
+}
+
+// one context and -- with `why`, what would go wrong, given -- no handle twice: the later of the two entries is named.
+// label: "pairs" / "links", as: "" / " as a".
+static int list_one_context_each_once(sfm_pair *const *pairs, int count, const sfm_ctx *ctx, const char *other_fmt, const char *label,
+                                      const char *as, const char *why)
+{
+    for (int i = 0; i < count; ++i) SFM_REQUIRE(pairs[i]->ctx == ctx, SFM_E_INVALID, other_fmt, i);
+    std::vector<std::pair<const sfm_pair *, int>> sorted((size_t)(why ? count : 0));
+    for (size_t i = 0; i < sorted.size(); ++i) sorted[i] = { pairs[i], (int)i };
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t k = 1; k < sorted.size(); ++k)
+        SFM_REQUIRE(sorted[k].first != sorted[k - 1].first, SFM_E_INVALID, "%s[%d]: the pair is listed twice%s (%s)", label, sorted[k].second, as, why);
+    return SFM_OK;
+}
+
+static int list_flush(sfm_pair *const *pairs, int count)
+{
+    for (int i = 0; i < count; ++i) SFM_FLUSH(pairs[i]);
+    return SFM_OK;
+}
+
+// every entry has the stages need(i); role: "" / "a: " / "b: "
+template <typename Need>
+static int list_stages(sfm_pair *const *pairs, int count, const char *label, const char *role, Need need)
+{
+    for (int i = 0; i < count; ++i) {
+        const uint32_t stages = need(i);
+        SFM_REQUIRE(pairs[i]->state.has(stages), SFM_E_STATE, "%s[%d]: %s%s", label, i, role, pair_stage_hint(pairs[i]->state.missing(stages)));
+    }
+    return SFM_OK;
+}
+
+// ---- no output on an input or on another output (buffer_ranges.hpp), as SFM_E_INVALID with the two names -----------------------
+// inside one set; who: "" or "pairs[i]: " / "links[i]: "
+static int check_ranges_in_set(const BufferRange *r, size_t count, const char *who)
+{
+    const RangeConflict c = first_conflict_in_set(r, count);
+    SFM_REQUIRE(!c, SFM_E_INVALID, "%s%s overlaps %s", who, c.a->name, c.b->name);
+    return SFM_OK;
+}
+
+// The entries of a batched call with the arrays' real lengths; table(i, r) writes entry i's per_entry ranges, owner i.  Inside
+// every entry first, then across them: the blocks of different entries run at the same time, so no output may lie on an output
+// or an input of another entry either (inputs may be shared).  This order is first_conflict_across_owners' precondition.
+template <typename Table>
+static int check_ranges_of_entries(int count, int per_entry, const char *label, Table table)
+{
+    std::vector<BufferRange> all((size_t)count * per_entry);
+    char who[32];
+    for (int i = 0; i < count; ++i) {
+        BufferRange *r = &all[(size_t)i * per_entry];
+        table(i, r);
+        snprintf(who, sizeof(who), "%s[%d]: ", label, i);
+        const int rc = check_ranges_in_set(r, (size_t)per_entry, who);
+        if (rc != SFM_OK) return rc;
+    }
+    const RangeConflict c = first_conflict_across_owners(all);
+    SFM_REQUIRE(!c, SFM_E_INVALID, "%s[%d]: a buffer overlaps a buffer of %s[%d], and one of the two is an output", label,
+                std::max(c.a->owner, c.b->owner), label, std::min(c.a->owner, c.b->owner));
     return SFM_OK;
 }
 
@@ -862,24 +933,18 @@ int sfm_refine_pairs(sfm_pair *const *pairs, int num_pairs, const sfm_refine_par
     // the checks that need no device first, all of them before anything is enqueued or any pair changes
     SFM_REQUIRE(p, SFM_E_INVALID, "null params");
     SFM_REQUIRE(num_pairs >= 0 && num_pairs <= 65535, SFM_E_INVALID, "num_pairs %d outside 0..65535", num_pairs);
-    if (num_pairs == 0) return SFM_OK;
+    if (num_pairs == 0) return SFM_OK;          // (the five later batched calls check the parameters whatever the count; this one never did)
     SFM_REQUIRE(pairs, SFM_E_INVALID, "null pair list");
-    for (int i = 0; i < num_pairs; ++i) SFM_REQUIRE(pairs[i], SFM_E_INVALID, "pairs[%d] is null", i);
+    int rc = list_entries_present(pairs, num_pairs, "pairs[%d] is null");
+    if (rc != SFM_OK) return rc;
     SFM_REQUIRE(!p->d_mask, SFM_E_INVALID, "sfm_refine_params.d_mask must be null here: per-pair masks go through d_masks");
-    int rc = check_lm_params(*p, "sfm_refine_params");
+    rc = check_lm_params(*p, "sfm_refine_params");
     if (rc != SFM_OK) return rc;
     sfm_ctx *ctx = pairs[0]->ctx;
-    for (int i = 1; i < num_pairs; ++i) SFM_REQUIRE(pairs[i]->ctx == ctx, SFM_E_INVALID, "pairs[%d] belongs to another context than pairs[0]", i);
-    {
-        std::vector<const sfm_pair *> sorted(pairs, pairs + num_pairs);
-        std::sort(sorted.begin(), sorted.end(), std::less<const sfm_pair *>());
-        SFM_REQUIRE(std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end(), SFM_E_INVALID,
-                    "a pair is listed twice (two blocks would write the same buffers)");
-    }
-    for (int i = 0; i < num_pairs; ++i) {
-        SFM_FLUSH(pairs[i]);
-        SFM_REQUIRE(pairs[i]->state.has(kE), SFM_E_STATE, "pairs[%d]: %s", i, pair_stage_hint(pairs[i]->state.missing(kE)));
-    }
+    rc = list_one_context_each_once(pairs, num_pairs, ctx, "pairs[%d] belongs to another context than pairs[0]", "pairs", "", "two blocks would write the same buffers");
+    if (rc == SFM_OK) rc = list_flush(pairs, num_pairs);
+    if (rc == SFM_OK) rc = list_stages(pairs, num_pairs, "pairs", "", [](int) { return (uint32_t)kE; });
+    if (rc != SFM_OK) return rc;
     SFM_HIP_TRY(hipSetDevice(ctx->device));
     for (int i = 0; i < num_pairs; ++i) { rc = refine_buffers(pairs[i]); if (rc != SFM_OK) return rc; }
     rc = launch_refine_pairs(ctx, pairs, num_pairs, *p, d_masks);
@@ -999,24 +1064,18 @@ int sfm_register_views(sfm_pair *const *pairs, int num_pairs, const sfm_sift_poi
     if (rc != SFM_OK) return rc;
     if (num_pairs == 0) return SFM_OK;
     SFM_REQUIRE(pairs && d_sifts, SFM_E_INVALID, "null pair list or null d_sifts list");
+    rc = list_entries_present(pairs, num_pairs, "pairs[%d] is null");
+    if (rc != SFM_OK) return rc;
     for (int i = 0; i < num_pairs; ++i) {
-        SFM_REQUIRE(pairs[i], SFM_E_INVALID, "pairs[%d] is null", i);
         SFM_REQUIRE(d_sifts[i], SFM_E_INVALID, "d_sifts[%d] is null", i);
         SFM_REQUIRE(!(d_valid && d_valid[i]) || (d_points && d_points[i]), SFM_E_INVALID, "d_valid[%d] needs d_points[%d]", i, i);
     }
     sfm_ctx *ctx = pairs[0]->ctx;
-    for (int i = 1; i < num_pairs; ++i) SFM_REQUIRE(pairs[i]->ctx == ctx, SFM_E_INVALID, "pairs[%d] belongs to another context than pairs[0]", i);
-    {
-        std::vector<const sfm_pair *> sorted(pairs, pairs + num_pairs);
-        std::sort(sorted.begin(), sorted.end(), std::less<const sfm_pair *>());
-        SFM_REQUIRE(std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end(), SFM_E_INVALID,
-                    "a pair is listed twice (a pair holds one registered view)");
-    }
-    for (int i = 0; i < num_pairs; ++i) SFM_FLUSH(pairs[i]);
-    for (int i = 0; i < num_pairs; ++i) {
-        const uint32_t need = (d_points && d_points[i]) ? kPoints : kPoints | kRefined;      // without points: the refined ones, on the current points
-        SFM_REQUIRE(pairs[i]->state.has(need), SFM_E_STATE, "pairs[%d]: %s", i, pair_stage_hint(pairs[i]->state.missing(need)));
-    }
+    rc = list_one_context_each_once(pairs, num_pairs, ctx, "pairs[%d] belongs to another context than pairs[0]", "pairs", "", "a pair holds one registered view");
+    if (rc == SFM_OK) rc = list_flush(pairs, num_pairs);
+    // without points: the refined ones, on the current points
+    if (rc == SFM_OK) rc = list_stages(pairs, num_pairs, "pairs", "", [&](int i) { return (uint32_t)((d_points && d_points[i]) ? kPoints : kPoints | kRefined); });
+    if (rc != SFM_OK) return rc;
     SFM_HIP_TRY(hipSetDevice(ctx->device));
     for (int i = 0; i < num_pairs; ++i) { rc = register_buffers(pairs[i], p->num_hypotheses); if (rc != SFM_OK) return rc; }
     std::vector<const float *> points((size_t)num_pairs);
@@ -1084,12 +1143,8 @@ void sfm_view_points_default_params(sfm_view_points_params *p)
 // the parameter checks of sfm_triangulate_view and sfm_triangulate_views (none needs a device)
 static int check_view_points_params(const sfm_view_points_params &p)
 {
-    SFM_REQUIRE(p.reserved[0] == 0 && p.reserved[1] == 0 && p.reserved[2] == 0 && p.reserved[3] == 0, SFM_E_INVALID,
-                "sfm_view_points_params.reserved[] must be zero");
-    SFM_REQUIRE(p.max_iterations >= 0 && p.max_iterations <= 50, SFM_E_INVALID, "max_iterations %d outside 0..50", p.max_iterations);
-    SFM_REQUIRE(p.huber_px >= 0.0f && isfinite(p.huber_px), SFM_E_INVALID, "huber_px must be finite and >= 0");
-    SFM_REQUIRE(isfinite(p.min_rel_decrease) && p.min_rel_decrease >= 0.0f, SFM_E_INVALID, "min_rel_decrease must be finite and >= 0");
-    SFM_REQUIRE(isfinite(p.initial_lambda) && p.initial_lambda >= 0.0f, SFM_E_INVALID, "initial_lambda must be finite and >= 0");
+    const int rc = check_lm_params(p, "sfm_view_points_params", 50);
+    if (rc != SFM_OK) return rc;
     SFM_REQUIRE(isfinite(p.threshold_px) && p.threshold_px > 0.0f, SFM_E_INVALID, "threshold_px must be finite and > 0");
     SFM_REQUIRE(isfinite(p.min_score) && isfinite(p.max_ambiguity), SFM_E_INVALID, "min_score / max_ambiguity must be finite");
     SFM_REQUIRE(p.min_parallax_deg >= 0.0f && p.min_parallax_deg <= 90.0f, SFM_E_INVALID, "min_parallax_deg outside 0..90");
@@ -1136,23 +1191,18 @@ int sfm_triangulate_views(sfm_pair *const *pairs, int num_pairs, const sfm_sift_
     if (rc != SFM_OK) return rc;
     if (num_pairs == 0) return SFM_OK;
     SFM_REQUIRE(pairs && d_sifts && outs, SFM_E_INVALID, "null pair list, d_sifts list or outs list");
+    rc = list_entries_present(pairs, num_pairs, "pairs[%d] is null");
+    if (rc != SFM_OK) return rc;
     for (int i = 0; i < num_pairs; ++i) {
-        SFM_REQUIRE(pairs[i], SFM_E_INVALID, "pairs[%d] is null", i);
         SFM_REQUIRE(d_sifts[i], SFM_E_INVALID, "d_sifts[%d] is null", i);
         SFM_REQUIRE((reinterpret_cast<uintptr_t>(d_sifts[i]) & 15) == 0, SFM_E_INVALID, "d_sifts[%d] must be 16-byte aligned", i);
         SFM_REQUIRE(outs[i].d_points && outs[i].d_flags, SFM_E_INVALID, "outs[%d]: d_points and d_flags are required", i);
     }
     sfm_ctx *ctx = pairs[0]->ctx;
-    for (int i = 1; i < num_pairs; ++i) SFM_REQUIRE(pairs[i]->ctx == ctx, SFM_E_INVALID, "pairs[%d] belongs to another context than pairs[0]", i);
-    {
-        std::vector<const sfm_pair *> sorted(pairs, pairs + num_pairs);
-        std::sort(sorted.begin(), sorted.end(), std::less<const sfm_pair *>());
-        SFM_REQUIRE(std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end(), SFM_E_INVALID, "a pair is listed twice");
-    }
-    for (int i = 0; i < num_pairs; ++i) SFM_FLUSH(pairs[i]);
-    const uint32_t need = kPoints | kRefined | kView;
-    for (int i = 0; i < num_pairs; ++i)
-        SFM_REQUIRE(pairs[i]->state.has(need), SFM_E_STATE, "pairs[%d]: %s", i, pair_stage_hint(pairs[i]->state.missing(need)));
+    rc = list_one_context_each_once(pairs, num_pairs, ctx, "pairs[%d] belongs to another context than pairs[0]", "pairs", "", "one entry, one set of outputs, per pair");
+    if (rc == SFM_OK) rc = list_flush(pairs, num_pairs);
+    if (rc == SFM_OK) rc = list_stages(pairs, num_pairs, "pairs", "", [](int) { return (uint32_t)(kPoints | kRefined | kView); });
+    if (rc != SFM_OK) return rc;
     SFM_HIP_TRY(hipSetDevice(ctx->device));
     std::vector<ViewPointsInputs> in((size_t)num_pairs);
     for (int i = 0; i < num_pairs; ++i) in[(size_t)i] = view_points_inputs(pairs[i], d_sifts[i], *p);
@@ -1170,10 +1220,22 @@ void sfm_adjust_default_params(sfm_adjust_params *p)
     p->initial_lambda = 1e-3f;
 }
 
+// the caller's buffers of one (in, out) set: inputs, then outputs.  n: the pair's record count, or 0 where the pair has not been
+// looked at yet (bytes_until_known)
+constexpr int kAdjustRanges = 10;
+static void adjust_ranges(const sfm_adjust_in &in, const sfm_adjust_params &p, const sfm_adjust_out &out, int n, int owner, BufferRange r[kAdjustRanges])
+{
+    auto len = [n](size_t per_record) { return bytes_until_known(n, per_record); };
+    r[0] = { in.d_sift, len(sizeof(sfm_sift_point)), false, owner, "in.d_sift" };
+    r[1] = { in.d_points, len(16), false, owner, "in.d_points" }; r[2] = { in.d_flags, len(1), false, owner, "in.d_flags" };
+    r[3] = { p.d_used2, len(1), false, owner, "params.d_used2" }; r[4] = { p.d_poses, 24 * sizeof(float), false, owner, "params.d_poses" };
+    r[5] = { out.d_poses, 24 * sizeof(float), true, owner, "out.d_poses" }; r[6] = { out.d_points, len(16), true, owner, "out.d_points" };
+    r[7] = { out.d_views, len(1), true, owner, "out.d_views" }; r[8] = { out.d_err, len(4), true, owner, "out.d_err" };
+    r[9] = { out.d_report, sizeof(sfm_adjust_report), true, owner, "out.d_report" };
+}
+
 // The checks of one (in, out) set that need no device: required pointers, the alignment of d_sift, and no output on top of an
-// input or of another output.  n: the pair's record count, or 0 where the pair has not been looked at yet -- then the arrays
-// that grow with n count as one byte (the same address is caught, and anything inside the poses or the report).
-// who: "" or "pairs[i]: ".
+// input or of another output (buffer_ranges.hpp).  who: "" or "pairs[i]: ".
 static int check_adjust_buffers(const sfm_adjust_in &in, const sfm_adjust_params &p, const sfm_adjust_out &out, int n, const char *who)
 {
     SFM_REQUIRE(in.d_sift && in.d_points && in.d_flags, SFM_E_INVALID, "%ssfm_adjust_in.d_sift, d_points and d_flags are required", who);
@@ -1181,24 +1243,9 @@ static int check_adjust_buffers(const sfm_adjust_in &in, const sfm_adjust_params
                 "%ssfm_adjust_out.d_poses, d_points, d_views and d_report are required", who);
     SFM_REQUIRE((reinterpret_cast<uintptr_t>(in.d_sift) & 15) == 0, SFM_E_INVALID,
                 "%sd_sift must be 16-byte aligned (the records are read with 16-byte loads)", who);
-    struct Range { const void *p; size_t bytes; const char *name; };
-    const size_t np = (size_t)n;
-    auto len = [np](size_t per_record) { return np ? np * per_record : (size_t)1; };
-    const Range ins[] = { { in.d_sift, len(sizeof(sfm_sift_point)), "in.d_sift" }, { in.d_points, len(16), "in.d_points" }, { in.d_flags, len(1), "in.d_flags" },
-                          { p.d_used2, len(1), "params.d_used2" }, { p.d_poses, 24 * sizeof(float), "params.d_poses" } };
-    const Range outs[] = { { out.d_poses, 24 * sizeof(float), "out.d_poses" }, { out.d_points, len(16), "out.d_points" }, { out.d_views, len(1), "out.d_views" },
-                           { out.d_err, len(4), "out.d_err" }, { out.d_report, sizeof(sfm_adjust_report), "out.d_report" } };
-    auto overlap = [](const Range &x, const Range &y) {
-        if (!x.p || !y.p) return false;
-        const uintptr_t a = reinterpret_cast<uintptr_t>(x.p), b = reinterpret_cast<uintptr_t>(y.p);
-        return a < b + y.bytes && b < a + x.bytes;
-    };
-    for (size_t o = 0; o < sizeof(outs) / sizeof(outs[0]); ++o) {
-        for (const Range &i : ins) SFM_REQUIRE(!overlap(outs[o], i), SFM_E_INVALID, "%s%s overlaps %s", who, outs[o].name, i.name);
-        for (size_t q = o + 1; q < sizeof(outs) / sizeof(outs[0]); ++q)
-            SFM_REQUIRE(!overlap(outs[o], outs[q]), SFM_E_INVALID, "%s%s overlaps %s", who, outs[o].name, outs[q].name);
-    }
-    return SFM_OK;
+    BufferRange r[kAdjustRanges];
+    adjust_ranges(in, p, out, n, 0, r);
+    return check_ranges_in_set(r, kAdjustRanges, who);
 }
 
 // the adjustment's work buffer, allocated at the first call and sized to the creation-time count
@@ -1248,60 +1295,20 @@ int sfm_adjust_views(sfm_pair *const *pairs, int num_pairs, const sfm_adjust_in 
     if (rc != SFM_OK) return rc;
     if (num_pairs == 0) return SFM_OK;
     SFM_REQUIRE(pairs && ins && outs, SFM_E_INVALID, "null pair list, ins list or outs list");
+    rc = list_entries_present(pairs, num_pairs, "pairs[%d] is null");
+    if (rc != SFM_OK) return rc;
+    char who[32];
     for (int i = 0; i < num_pairs; ++i) {
-        SFM_REQUIRE(pairs[i], SFM_E_INVALID, "pairs[%d] is null", i);
-        char who[32];
         snprintf(who, sizeof(who), "pairs[%d]: ", i);
         rc = check_adjust_buffers(ins[i], *p, outs[i], 0, who);
         if (rc != SFM_OK) return rc;
     }
     sfm_ctx *ctx = pairs[0]->ctx;
-    for (int i = 1; i < num_pairs; ++i) SFM_REQUIRE(pairs[i]->ctx == ctx, SFM_E_INVALID, "pairs[%d] belongs to another context than pairs[0]", i);
-    {
-        std::vector<std::pair<const sfm_pair *, int>> sorted((size_t)num_pairs);
-        for (int i = 0; i < num_pairs; ++i) sorted[(size_t)i] = { pairs[i], i };
-        std::sort(sorted.begin(), sorted.end());
-        for (int k = 1; k < num_pairs; ++k)
-            SFM_REQUIRE(sorted[(size_t)k].first != sorted[(size_t)k - 1].first, SFM_E_INVALID,
-                        "pairs[%d]: the pair is listed twice (two blocks would write the same work buffer)", sorted[(size_t)k].second);
-    }
-    for (int i = 0; i < num_pairs; ++i) SFM_FLUSH(pairs[i]);
-    const uint32_t need = kPoints | kRefined | kView;
-    for (int i = 0; i < num_pairs; ++i)
-        SFM_REQUIRE(pairs[i]->state.has(need), SFM_E_STATE, "pairs[%d]: %s", i, pair_stage_hint(pairs[i]->state.missing(need)));
-    for (int i = 0; i < num_pairs; ++i) {
-        char who[32];
-        snprintf(who, sizeof(who), "pairs[%d]: ", i);
-        rc = check_adjust_buffers(ins[i], *p, outs[i], pairs[i]->n, who);                   // the same with the arrays' real lengths
-        if (rc != SFM_OK) return rc;
-    }
-    {
-        // across pairs: the blocks of different pairs run at the same time, so no output may lie on an output or an input of
-        // another pair either (inputs may be shared).  All ranges sorted by their start, one sweep.
-        struct Range { uintptr_t lo, hi; int pair; bool out; };
-        std::vector<Range> r;
-        r.reserve((size_t)num_pairs * 8);
-        auto add = [&r](const void *q, size_t bytes, int i, bool out) {
-            if (q && bytes) r.push_back({ reinterpret_cast<uintptr_t>(q), reinterpret_cast<uintptr_t>(q) + bytes, i, out });
-        };
-        for (int i = 0; i < num_pairs; ++i) {
-            const size_t np = (size_t)pairs[i]->n;
-            add(ins[i].d_sift, np * sizeof(sfm_sift_point), i, false); add(ins[i].d_points, 16 * np, i, false); add(ins[i].d_flags, np, i, false);
-            add(outs[i].d_poses, 24 * sizeof(float), i, true); add(outs[i].d_points, 16 * np, i, true); add(outs[i].d_views, np, i, true);
-            add(outs[i].d_err, 4 * np, i, true); add(outs[i].d_report, sizeof(sfm_adjust_report), i, true);
-        }
-        std::sort(r.begin(), r.end(), [](const Range &x, const Range &y) { return x.lo < y.lo; });
-        const Range *far_any = nullptr, *far_out = nullptr;     // the ranges seen so far that end last: any, and among the outputs
-        for (const Range &x : r) {
-            const Range *hit = x.out ? far_any : far_out;
-            if (hit && hit->hi > x.lo && hit->pair != x.pair) {
-                const int later = x.pair > hit->pair ? x.pair : hit->pair, other = x.pair > hit->pair ? hit->pair : x.pair;
-                SFM_REQUIRE(false, SFM_E_INVALID, "pairs[%d]: a buffer overlaps a buffer of pairs[%d], and one of the two is an output", later, other);
-            }
-            if (!far_any || x.hi > far_any->hi) far_any = &x;
-            if (x.out && (!far_out || x.hi > far_out->hi)) far_out = &x;
-        }
-    }
+    rc = list_one_context_each_once(pairs, num_pairs, ctx, "pairs[%d] belongs to another context than pairs[0]", "pairs", "", "two blocks would write the same work buffer");
+    if (rc == SFM_OK) rc = list_flush(pairs, num_pairs);
+    if (rc == SFM_OK) rc = list_stages(pairs, num_pairs, "pairs", "", [](int) { return (uint32_t)(kPoints | kRefined | kView); });
+    if (rc == SFM_OK) rc = check_ranges_of_entries(num_pairs, kAdjustRanges, "pairs", [&](int i, BufferRange *r) { adjust_ranges(ins[i], *p, outs[i], pairs[i]->n, i, r); });
+    if (rc != SFM_OK) return rc;
     SFM_HIP_TRY(hipSetDevice(ctx->device));
     for (int i = 0; i < num_pairs; ++i) { rc = adjust_buffers(pairs[i]); if (rc != SFM_OK) return rc; }
     std::vector<AdjustInputs> in((size_t)num_pairs);
@@ -1335,38 +1342,28 @@ static int check_align_params(const sfm_align_params &p)
     return SFM_OK;
 }
 
-struct AlignRange { const void *p; size_t bytes; const char *name; };
 // the caller's buffers of one link: inputs, then outputs.  na, nb: the pairs' record counts, or 0 where the pairs have not been
-// looked at yet -- then the arrays that grow with them count as one byte (check_adjust_buffers' rule).
-static void align_ranges(const int32_t *d_index, const sfm_align_params &p, const sfm_align_out &out, int na, int nb, AlignRange ins[5], AlignRange outs[5])
+// looked at yet (bytes_until_known)
+constexpr int kAlignRanges = 10;
+static void align_ranges(const int32_t *d_index, const sfm_align_params &p, const sfm_align_out &out, int na, int nb, int owner, BufferRange r[kAlignRanges])
 {
-    auto len = [](int n, size_t per) { return n ? (size_t)n * per : (size_t)1; };
-    ins[0] = { d_index, len(na, 4), "d_index" };
-    ins[1] = { p.d_points_a, len(na, 16), "params.d_points_a" }; ins[2] = { p.d_valid_a, len(na, 1), "params.d_valid_a" };
-    ins[3] = { p.d_points_b, len(nb, 16), "params.d_points_b" }; ins[4] = { p.d_valid_b, len(nb, 1), "params.d_valid_b" };
-    outs[0] = { out.d_sim, 26 * sizeof(float), "out.d_sim" }; outs[1] = { out.d_inlier, len(na, 1), "out.d_inlier" };
-    outs[2] = { out.d_err, len(na, 4), "out.d_err" }; outs[3] = { out.d_counts, (size_t)p.num_hypotheses * 4, "out.d_counts" };
-    outs[4] = { out.d_report, sizeof(sfm_align_report), "out.d_report" };
+    r[0] = { d_index, bytes_until_known(na, 4), false, owner, "d_index" };
+    r[1] = { p.d_points_a, bytes_until_known(na, 16), false, owner, "params.d_points_a" }; r[2] = { p.d_valid_a, bytes_until_known(na, 1), false, owner, "params.d_valid_a" };
+    r[3] = { p.d_points_b, bytes_until_known(nb, 16), false, owner, "params.d_points_b" }; r[4] = { p.d_valid_b, bytes_until_known(nb, 1), false, owner, "params.d_valid_b" };
+    r[5] = { out.d_sim, 26 * sizeof(float), true, owner, "out.d_sim" }; r[6] = { out.d_inlier, bytes_until_known(na, 1), true, owner, "out.d_inlier" };
+    r[7] = { out.d_err, bytes_until_known(na, 4), true, owner, "out.d_err" }; r[8] = { out.d_counts, (size_t)p.num_hypotheses * 4, true, owner, "out.d_counts" };
+    r[9] = { out.d_report, sizeof(sfm_align_report), true, owner, "out.d_report" };
 }
 
-// The checks of one link's buffers that need no device: required pointers, no output on top of an input or of another output.
-// who: "" or "links[i]: ".
+// The checks of one link's buffers that need no device: required pointers, no output on top of an input or of another output
+// (buffer_ranges.hpp).  who: "" or "links[i]: ".
 static int check_align_buffers(const int32_t *d_index, const sfm_align_params &p, const sfm_align_out &out, int na, int nb, const char *who)
 {
     SFM_REQUIRE(d_index, SFM_E_INVALID, "%sd_index is required", who);
     SFM_REQUIRE(out.d_sim && out.d_inlier && out.d_report, SFM_E_INVALID, "%ssfm_align_out.d_sim, d_inlier and d_report are required", who);
-    AlignRange ins[5], outs[5];
-    align_ranges(d_index, p, out, na, nb, ins, outs);
-    auto overlap = [](const AlignRange &x, const AlignRange &y) {
-        if (!x.p || !y.p) return false;
-        const uintptr_t a = reinterpret_cast<uintptr_t>(x.p), b = reinterpret_cast<uintptr_t>(y.p);
-        return a < b + y.bytes && b < a + x.bytes;
-    };
-    for (int o = 0; o < 5; ++o) {
-        for (int i = 0; i < 5; ++i) SFM_REQUIRE(!overlap(outs[o], ins[i]), SFM_E_INVALID, "%s%s overlaps %s", who, outs[o].name, ins[i].name);
-        for (int q = o + 1; q < 5; ++q) SFM_REQUIRE(!overlap(outs[o], outs[q]), SFM_E_INVALID, "%s%s overlaps %s", who, outs[o].name, outs[q].name);
-    }
-    return SFM_OK;
+    BufferRange r[kAlignRanges];
+    align_ranges(d_index, p, out, na, nb, 0, r);
+    return check_ranges_in_set(r, kAlignRanges, who);
 }
 
 // the work buffers of pair `a`: the per-record one allocated at the first call, the per-hypothesis one grown on demand
@@ -1441,62 +1438,28 @@ int sfm_align_pairs(sfm_pair *const *as, sfm_pair *const *bs, int num_links, con
     if (rc != SFM_OK) return rc;
     if (num_links == 0) return SFM_OK;
     SFM_REQUIRE(as && bs && d_indices && outs, SFM_E_INVALID, "null pair list, d_indices list or outs list");
+    rc = list_entries_present(as, num_links, "links[%d]: null pair");
+    if (rc == SFM_OK) rc = list_entries_present(bs, num_links, "links[%d]: null pair");
+    if (rc != SFM_OK) return rc;
     char who[32];
     for (int i = 0; i < num_links; ++i) {
-        SFM_REQUIRE(as[i] && bs[i], SFM_E_INVALID, "links[%d]: null pair", i);
         SFM_REQUIRE(as[i] != bs[i], SFM_E_INVALID, "links[%d]: a and b are the same pair", i);
         snprintf(who, sizeof(who), "links[%d]: ", i);
         rc = check_align_buffers(d_indices[i], *p, outs[i], 0, 0, who);
         if (rc != SFM_OK) return rc;
     }
     sfm_ctx *ctx = as[0]->ctx;
-    for (int i = 0; i < num_links; ++i)
-        SFM_REQUIRE(as[i]->ctx == ctx && bs[i]->ctx == ctx, SFM_E_INVALID, "links[%d]: a pair belongs to another context than links[0]'s a", i);
-    {
-        std::vector<std::pair<const sfm_pair *, int>> sorted((size_t)num_links);
-        for (int i = 0; i < num_links; ++i) sorted[(size_t)i] = { as[i], i };
-        std::sort(sorted.begin(), sorted.end());
-        for (int k = 1; k < num_links; ++k)
-            SFM_REQUIRE(sorted[(size_t)k].first != sorted[(size_t)k - 1].first, SFM_E_INVALID,
-                        "links[%d]: the pair is listed twice as a (two blocks would write the same work buffer)", sorted[(size_t)k].second);
-    }
-    for (int i = 0; i < num_links; ++i) { SFM_FLUSH(as[i]); SFM_FLUSH(bs[i]); }
-    const uint32_t need = kPoints | kRefined;
-    for (int i = 0; i < num_links; ++i) {
-        SFM_REQUIRE(as[i]->state.has(need), SFM_E_STATE, "links[%d]: a: %s", i, pair_stage_hint(as[i]->state.missing(need)));
-        SFM_REQUIRE(bs[i]->state.has(need), SFM_E_STATE, "links[%d]: b: %s", i, pair_stage_hint(bs[i]->state.missing(need)));
-    }
-    for (int i = 0; i < num_links; ++i) {
-        snprintf(who, sizeof(who), "links[%d]: ", i);
-        rc = check_align_buffers(d_indices[i], *p, outs[i], as[i]->n, bs[i]->n, who);      // the same with the arrays' real lengths
-        if (rc != SFM_OK) return rc;
-    }
-    {
-        // across links: the blocks of different links run at the same time, so no output may lie on an output or an input of
-        // another link either (inputs may be shared).  All ranges sorted by their start, one sweep (sfm_adjust_views').
-        struct Range { uintptr_t lo, hi; int link; bool out; };
-        std::vector<Range> r;
-        r.reserve((size_t)num_links * 6);
-        for (int i = 0; i < num_links; ++i) {
-            AlignRange ins[5], os[5];
-            align_ranges(d_indices[i], *p, outs[i], as[i]->n, bs[i]->n, ins, os);
-            for (int k = 0; k < 5; ++k) {
-                if (ins[k].p && ins[k].bytes) r.push_back({ reinterpret_cast<uintptr_t>(ins[k].p), reinterpret_cast<uintptr_t>(ins[k].p) + ins[k].bytes, i, false });
-                if (os[k].p && os[k].bytes) r.push_back({ reinterpret_cast<uintptr_t>(os[k].p), reinterpret_cast<uintptr_t>(os[k].p) + os[k].bytes, i, true });
-            }
-        }
-        std::sort(r.begin(), r.end(), [](const Range &x, const Range &y) { return x.lo < y.lo; });
-        const Range *far_any = nullptr, *far_out = nullptr;     // the ranges seen so far that end last: any, and among the outputs
-        for (const Range &x : r) {
-            const Range *hit = x.out ? far_any : far_out;
-            if (hit && hit->hi > x.lo && hit->link != x.link) {
-                const int later = x.link > hit->link ? x.link : hit->link, other = x.link > hit->link ? hit->link : x.link;
-                SFM_REQUIRE(false, SFM_E_INVALID, "links[%d]: a buffer overlaps a buffer of links[%d], and one of the two is an output", later, other);
-            }
-            if (!far_any || x.hi > far_any->hi) far_any = &x;
-            if (x.out && (!far_out || x.hi > far_out->hi)) far_out = &x;
-        }
-    }
+    const char *other_ctx = "links[%d]: a pair belongs to another context than links[0]'s a";
+    const auto need = [](int) { return (uint32_t)(kPoints | kRefined); };
+    rc = list_one_context_each_once(as, num_links, ctx, other_ctx, "links", " as a", "two blocks would write the same work buffer");
+    if (rc == SFM_OK) rc = list_one_context_each_once(bs, num_links, ctx, other_ctx, "links", "", nullptr);       // b is only read: as often as the caller likes
+    if (rc == SFM_OK) rc = list_flush(as, num_links);
+    if (rc == SFM_OK) rc = list_flush(bs, num_links);
+    if (rc == SFM_OK) rc = list_stages(as, num_links, "links", "a: ", need);
+    if (rc == SFM_OK) rc = list_stages(bs, num_links, "links", "b: ", need);
+    if (rc == SFM_OK) rc = check_ranges_of_entries(num_links, kAlignRanges, "links",
+                                                   [&](int i, BufferRange *r) { align_ranges(d_indices[i], *p, outs[i], as[i]->n, bs[i]->n, i, r); });
+    if (rc != SFM_OK) return rc;
     SFM_HIP_TRY(hipSetDevice(ctx->device));
     for (int i = 0; i < num_links; ++i) { rc = align_buffers(as[i], p->num_hypotheses); if (rc != SFM_OK) return rc; }
     std::vector<AlignInputs> in((size_t)num_links);
@@ -1522,19 +1485,22 @@ int sfm_fuse_chain(sfm_ctx *ctx, const sfm_fuse_pair_in *pairs, int num_pairs, c
     // the checks that need no device first, all of them before anything is enqueued
     SFM_REQUIRE(p, SFM_E_INVALID, "null params");
     SFM_REQUIRE(num_pairs >= 0 && num_pairs <= 4096, SFM_E_INVALID, "num_pairs %d outside 0..4096", num_pairs);
-    int rc = check_lm_params(*p, "sfm_fuse_params");
+    int rc = check_lm_params(*p, "sfm_fuse_params", 50);
     if (rc != SFM_OK) return rc;
-    SFM_REQUIRE(p->max_iterations <= 50, SFM_E_INVALID, "max_iterations %d outside 0..50", p->max_iterations);
     SFM_REQUIRE(isfinite(p->threshold_px) && p->threshold_px > 0.0f, SFM_E_INVALID, "threshold_px must be finite and > 0");
     if (num_pairs == 0) return SFM_OK;
     SFM_REQUIRE(ctx && pairs && out, SFM_E_INVALID, "null context, pair list or out");
     SFM_REQUIRE(links || num_pairs == 1, SFM_E_INVALID, "null link list");
     SFM_REQUIRE(out->d_frames && out->d_root && out->d_cams && out->d_track && out->d_track_offset && out->d_obs_cam && out->d_obs_record &&
                 out->d_points && out->d_flags && out->d_counts, SFM_E_INVALID, "every buffer of sfm_fuse_out but d_err is required");
+    std::vector<sfm_pair *> handles((size_t)num_pairs);
+    for (int i = 0; i < num_pairs; ++i) handles[(size_t)i] = pairs[i].pair;
+    rc = list_entries_present(handles.data(), num_pairs, "pairs[%d]: null pair");
+    if (rc == SFM_OK) rc = list_one_context_each_once(handles.data(), num_pairs, ctx, "pairs[%d]: the pair belongs to another context", "pairs", "",
+                                                      "a chain visits a pair once");
+    if (rc != SFM_OK) return rc;
     long long total = 0;
     for (int i = 0; i < num_pairs; ++i) {
-        SFM_REQUIRE(pairs[i].pair, SFM_E_INVALID, "pairs[%d]: null pair", i);
-        SFM_REQUIRE(pairs[i].pair->ctx == ctx, SFM_E_INVALID, "pairs[%d]: the pair belongs to another context", i);
         SFM_REQUIRE(pairs[i].d_points || !pairs[i].d_valid, SFM_E_INVALID, "pairs[%d]: d_valid needs d_points", i);
         total += pairs[i].pair->n;
     }
@@ -1543,19 +1509,15 @@ int sfm_fuse_chain(sfm_ctx *ctx, const sfm_fuse_pair_in *pairs, int num_pairs, c
         SFM_REQUIRE(links[i].d_index && links[i].d_sim && links[i].d_inlier && links[i].d_err && links[i].d_report, SFM_E_INVALID,
                     "links[%d]: d_index, d_sim, d_inlier, d_err and d_report are required", i);
     {
-        std::vector<std::pair<const sfm_pair *, int>> sorted((size_t)num_pairs);
-        for (int i = 0; i < num_pairs; ++i) sorted[(size_t)i] = { pairs[i].pair, i };
-        std::sort(sorted.begin(), sorted.end());
-        for (int k = 1; k < num_pairs; ++k)
-            SFM_REQUIRE(sorted[(size_t)k].first != sorted[(size_t)k - 1].first, SFM_E_INVALID, "pairs[%d]: the pair is listed twice", sorted[(size_t)k].second);
-    }
-    {
-        // no output on an input or on another output: all ranges sorted by their start, one sweep (sfm_adjust_views')
-        struct Range { uintptr_t lo, hi; bool out; int who; const char *name; };
-        std::vector<Range> r;
+        // no output on an input or on another output.  Every range is its own owner (its place in `entry`, which keeps the index its
+        // name takes): nothing is exempt, so the sweep is the whole check.
+        std::vector<BufferRange> r;
+        std::vector<int> entry;
         r.reserve((size_t)num_pairs * 8 + 11);
+        entry.reserve((size_t)num_pairs * 8 + 11);
         auto add = [&](const void *ptr, size_t bytes, bool is_out, int who, const char *name) {
-            if (ptr && bytes) r.push_back({ reinterpret_cast<uintptr_t>(ptr), reinterpret_cast<uintptr_t>(ptr) + bytes, is_out, who, name });
+            r.push_back({ ptr, bytes, is_out, (int)entry.size(), name });
+            entry.push_back(who);
         };
         const size_t N = (size_t)total, k = (size_t)num_pairs;
         for (int i = 0; i < num_pairs; ++i) {
@@ -1574,24 +1536,16 @@ int sfm_fuse_chain(sfm_ctx *ctx, const sfm_fuse_pair_in *pairs, int num_pairs, c
         add(out->d_obs_record, N * 8, true, -1, "out.d_obs_record"); add(out->d_points, N * 16, true, -1, "out.d_points");
         add(out->d_flags, N, true, -1, "out.d_flags"); add(out->d_err, N * 4, true, -1, "out.d_err");
         add(out->d_counts, 32, true, -1, "out.d_counts");
-        std::sort(r.begin(), r.end(), [](const Range &x, const Range &y) { return x.lo < y.lo; });
-        const Range *far_any = nullptr, *far_out = nullptr;     // the ranges seen so far that end last: any, and among the outputs
-        for (const Range &x : r) {
-            const Range *hit = x.out ? far_any : far_out;
-            if (hit && hit->hi > x.lo) {
-                char a[48], b[48];
-                snprintf(a, sizeof(a), x.name, x.who); snprintf(b, sizeof(b), hit->name, hit->who);
-                SFM_REQUIRE(false, SFM_E_INVALID, "%s overlaps %s", x.out ? a : b, x.out ? b : a);
-            }
-            if (!far_any || x.hi > far_any->hi) far_any = &x;
-            if (x.out && (!far_out || x.hi > far_out->hi)) far_out = &x;
+        if (const RangeConflict c = first_conflict_across_owners(r)) {
+            char a[48], b[48];
+            snprintf(a, sizeof(a), c.a->name, entry[(size_t)c.a->owner]); snprintf(b, sizeof(b), c.b->name, entry[(size_t)c.b->owner]);
+            SFM_REQUIRE(false, SFM_E_INVALID, "%s overlaps %s", c.a->out ? a : b, c.a->out ? b : a);       // the output first
         }
     }
-    for (int i = 0; i < num_pairs; ++i) SFM_FLUSH(pairs[i].pair);
-    for (int i = 0; i < num_pairs; ++i) {
-        const uint32_t need = (pairs[i].d_points && pairs[i].d_pose) ? kPoints : kPoints | kRefined;
-        SFM_REQUIRE(pairs[i].pair->state.has(need), SFM_E_STATE, "pairs[%d]: %s", i, pair_stage_hint(pairs[i].pair->state.missing(need)));
-    }
+    rc = list_flush(handles.data(), num_pairs);
+    if (rc == SFM_OK) rc = list_stages(handles.data(), num_pairs, "pairs", "",
+                                       [&](int i) { return (uint32_t)((pairs[i].d_points && pairs[i].d_pose) ? kPoints : kPoints | kRefined); });
+    if (rc != SFM_OK) return rc;
     SFM_HIP_TRY(hipSetDevice(ctx->device));
     std::vector<FusePair> fp((size_t)num_pairs);
     for (int i = 0; i < num_pairs; ++i) {

@@ -23,8 +23,6 @@
 #include "device_math.hpp"
 #include "block_ops.hpp"
 #include "adjust_math.hpp"
-#include <algorithm>
-#include <vector>
 
 namespace sfm {
 
@@ -447,23 +445,12 @@ int launch_adjust(sfm_pair *pair, const AdjustInputs &in, const sfm_adjust_param
 int launch_adjust_views(sfm_ctx *ctx, sfm_pair *const *pairs, int num_pairs, const AdjustInputs *in, const sfm_adjust_params &p, const sfm_adjust_out *outs)
 {
     hipStream_t st = ctx->stream;
-    JobArray &ja = ctx->adjust_jobs;
-    int rc = job_array_reserve(ja, (size_t)num_pairs, sizeof(AdjustArgs), st);
+    const AdjustArgs *d_jobs = nullptr;
+    int nmax = 0;                                         // long chains first: the solve blocks are dispatched in job order
+    const int rc = job_array_stage(ctx->adjust_jobs, num_pairs, st, [&](int i) { return pairs[i]->n; },
+                                   [&](AdjustArgs &job, int i) { adjust_args(pairs[i], in[i], p, outs[i], job); }, &d_jobs, &nmax);
     if (rc != SFM_OK) return rc;
-    // long chains first: the solve blocks are dispatched in job order.  Stable, so equal sizes keep the caller's order; a pair's
-    // result does not depend on its place (every block works on its own pair's buffers).
-    std::vector<int> order((size_t)num_pairs);
-    for (int i = 0; i < num_pairs; ++i) order[(size_t)i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return pairs[x]->n > pairs[y]->n; });
-    AdjustArgs *h_jobs = static_cast<AdjustArgs *>(ja.pinned);
-    for (int k = 0; k < num_pairs; ++k) {
-        const int i = order[(size_t)k];
-        adjust_args(pairs[i], in[i], p, outs[i], h_jobs[k]);
-    }
-    const AdjustArgs *d_jobs = static_cast<const AdjustArgs *>(ja.dev);
-    rc = job_array_upload(ja, (size_t)num_pairs, sizeof(AdjustArgs), st);
-    if (rc != SFM_OK) return rc;
-    const int nb = (h_jobs[0].n + kAdjGrid - 1) / kAdjGrid;
+    const int nb = (nmax + kAdjGrid - 1) / kAdjGrid;
     if (nb > 0) {
         hipLaunchKernelGGL(adjust_gather_views_kernel, dim3(nb, num_pairs), dim3(kAdjGrid), 0, st, d_jobs);
         SFM_HIP_TRY(hipGetLastError());

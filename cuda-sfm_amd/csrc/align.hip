@@ -28,8 +28,6 @@
 #include "device_math.hpp"
 #include "block_ops.hpp"
 #include "align_math.hpp"
-#include <algorithm>
-#include <vector>
 
 namespace sfm {
 
@@ -463,24 +461,13 @@ int launch_align_pairs(sfm_ctx *ctx, sfm_pair *const *as, sfm_pair *const *bs, i
                        const sfm_align_out *outs)
 {
     hipStream_t st = ctx->stream;
-    JobArray &ja = ctx->align_jobs;
-    int rc = job_array_reserve(ja, (size_t)num_links, sizeof(AlignArgs), st);
-    if (rc != SFM_OK) return rc;
-    // links with the most records first: the one-block gates and LM chains are dispatched in job order.  Stable, so equal sizes keep
-    // the caller's order; a link's result does not depend on its place (every block works on its own link's buffers).
-    std::vector<int> order((size_t)num_links);
-    for (int i = 0; i < num_links; ++i) order[(size_t)i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return as[x]->n > as[y]->n; });
-    AlignArgs *h_jobs = static_cast<AlignArgs *>(ja.pinned);
-    for (int k = 0; k < num_links; ++k) {
-        const int i = order[(size_t)k];
-        align_args(as[i], bs[i], in[i], p, outs[i], h_jobs[k]);
-    }
-    const AlignArgs *d_jobs = static_cast<const AlignArgs *>(ja.dev);
-    rc = job_array_upload(ja, (size_t)num_links, sizeof(AlignArgs), st);
+    const AlignArgs *d_jobs = nullptr;
+    int nmax = 0;                                         // links with the most records first: the one-block gates and LM chains are dispatched in job order
+    const int rc = job_array_stage(ctx->align_jobs, num_links, st, [&](int i) { return as[i]->n; },
+                                   [&](AlignArgs &job, int i) { align_args(as[i], bs[i], in[i], p, outs[i], job); }, &d_jobs, &nmax);
     if (rc != SFM_OK) return rc;
     const int hblocks = (int)((p.num_hypotheses + kAlnHypBlock - 1) / kAlnHypBlock);
-    const int splits = align_splits(ctx->num_cus, hblocks, num_links, h_jobs[0].na);         // ONE for the launch: counts do not depend on it
+    const int splits = align_splits(ctx->num_cus, hblocks, num_links, nmax);                 // ONE for the launch: counts do not depend on it
     hipLaunchKernelGGL(align_gate_pairs_kernel, dim3(num_links), dim3(kAlnGateThreads), 0, st, d_jobs);
     SFM_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(align_solve_pairs_kernel, dim3(hblocks, num_links), dim3(kAlnHypBlock), 0, st, d_jobs);

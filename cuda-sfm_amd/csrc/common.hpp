@@ -8,6 +8,7 @@
 #include <type_traits>
 #include "../../include/sfm_amd.h"
 #include "pair_state.hpp"
+#include "job_order.hpp"
 #if SFM_AB
 #include "../../include/sfm_amd_ab.h"
 #endif
@@ -85,9 +86,9 @@ struct Carver {
     }
 };
 
-// The job array of a many-pairs call (sfm_refine_pairs: RefineArgs, sfm_register_views: RegisterArgs): a context-owned device
-// array + pinned staging, grown on demand, and the event that sits behind the upload.  One mechanism, parameterised by the
-// element size.
+// The job array of a batched call (one per call in sfm_ctx: sfm_refine_pairs, sfm_register_views, sfm_triangulate_views,
+// sfm_adjust_views, sfm_align_pairs, sfm_fuse_chain): a context-owned device array + pinned staging, grown on demand, and the
+// event that sits behind the upload.  One mechanism, parameterised by the element size.
 struct JobArray {
     void *dev = nullptr, *pinned = nullptr;
     size_t cap = 0;                    // jobs
@@ -119,6 +120,21 @@ inline int job_array_upload(JobArray &j, size_t count, size_t elem, hipStream_t 
     SFM_HIP_TRY(hipMemcpyAsync(j.dev, j.pinned, count * elem, hipMemcpyHostToDevice, st));
     SFM_HIP_TRY(hipEventRecord(j.ev, st));
     return SFM_OK;
+}
+
+// The prologue of a batched launch (count >= 1): room for the jobs, the caller's entries by decreasing key (job_order.hpp),
+// fill(h_jobs[k], i) for job k from caller index i, the upload.  *d_jobs: the device array; *largest: the key of job 0.
+template <typename Job, typename Key, typename Fill>
+inline int job_array_stage(JobArray &j, int count, hipStream_t st, Key key, Fill fill, const Job **d_jobs, int *largest)
+{
+    int rc = job_array_reserve(j, (size_t)count, sizeof(Job), st);
+    if (rc != SFM_OK) return rc;
+    const std::vector<int> order = order_by_decreasing_key(count, key);
+    Job *h_jobs = static_cast<Job *>(j.pinned);
+    for (int k = 0; k < count; ++k) fill(h_jobs[k], order[(size_t)k]);
+    *d_jobs = static_cast<const Job *>(j.dev);
+    *largest = key(order[0]);
+    return job_array_upload(j, (size_t)count, sizeof(Job), st);
 }
 
 inline void job_array_free(JobArray &j)

@@ -24,8 +24,6 @@
 #include "device_math.hpp"
 #include "block_ops.hpp"
 #include "refine_math.hpp"
-#include <algorithm>
-#include <vector>
 
 namespace sfm {
 
@@ -437,23 +435,11 @@ int launch_refine(sfm_pair *pair, const sfm_refine_params &p)
 int launch_refine_pairs(sfm_ctx *ctx, sfm_pair *const *pairs, int num_pairs, const sfm_refine_params &p, const uint8_t *const *d_masks)
 {
     hipStream_t st = ctx->stream;
-    JobArray &ja = ctx->refine_jobs;
-    int rc = job_array_reserve(ja, (size_t)num_pairs, sizeof(RefineArgs), st);
+    const RefineArgs *d_jobs = nullptr;
+    int nmax = 0;                                         // long chains first: the solve blocks are dispatched in job order
+    const int rc = job_array_stage(ctx->refine_jobs, num_pairs, st, [&](int i) { return pairs[i]->n; },
+                                   [&](RefineArgs &job, int i) { refine_args(pairs[i], p, d_masks ? d_masks[i] : nullptr, job); }, &d_jobs, &nmax);
     if (rc != SFM_OK) return rc;
-    // long chains first: the solve blocks are dispatched in job order.  Stable, so equal sizes keep the caller's order; a pair's
-    // result does not depend on its place (every block works on its own pair's buffers).
-    std::vector<int> order((size_t)num_pairs);
-    for (int i = 0; i < num_pairs; ++i) order[(size_t)i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return pairs[x]->n > pairs[y]->n; });
-    RefineArgs *h_jobs = static_cast<RefineArgs *>(ja.pinned);
-    for (int k = 0; k < num_pairs; ++k) {
-        const int i = order[(size_t)k];
-        refine_args(pairs[i], p, d_masks ? d_masks[i] : nullptr, h_jobs[k]);
-    }
-    const RefineArgs *d_jobs = static_cast<const RefineArgs *>(ja.dev);
-    rc = job_array_upload(ja, (size_t)num_pairs, sizeof(RefineArgs), st);
-    if (rc != SFM_OK) return rc;
-    const int nmax = h_jobs[0].n;
     hipLaunchKernelGGL(refine_start_pairs_kernel, dim3((nmax + kStartPoints - 1) / kStartPoints, num_pairs), dim3(256), 0, st, d_jobs);
     SFM_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(refine_solve_pairs_kernel, dim3(num_pairs), dim3(kRefineThreads), 0, st, d_jobs);

@@ -29,8 +29,6 @@
 #include "device_math.hpp"
 #include "block_ops.hpp"
 #include "register_math.hpp"
-#include <algorithm>
-#include <vector>
 
 namespace sfm {
 
@@ -443,24 +441,13 @@ int launch_register_views(sfm_ctx *ctx, sfm_pair *const *pairs, int num_pairs, c
                           const float *const *d_points, const uint8_t *const *d_valid)
 {
     hipStream_t st = ctx->stream;
-    JobArray &ja = ctx->register_jobs;
-    int rc = job_array_reserve(ja, (size_t)num_pairs, sizeof(RegisterArgs), st);
-    if (rc != SFM_OK) return rc;
-    // large views first: the one-block gates and LM chains are dispatched in job order.  Stable, so equal sizes keep the caller's
-    // order; a pair's result does not depend on its place (every block works on its own pair's buffers).
-    std::vector<int> order((size_t)num_pairs);
-    for (int i = 0; i < num_pairs; ++i) order[(size_t)i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return pairs[x]->n > pairs[y]->n; });
-    RegisterArgs *h_jobs = static_cast<RegisterArgs *>(ja.pinned);
-    for (int k = 0; k < num_pairs; ++k) {
-        const int i = order[(size_t)k];
-        register_args(pairs[i], d_sifts[i], p, d_points[i], d_valid[i], h_jobs[k]);
-    }
-    const RegisterArgs *d_jobs = static_cast<const RegisterArgs *>(ja.dev);
-    rc = job_array_upload(ja, (size_t)num_pairs, sizeof(RegisterArgs), st);
+    const RegisterArgs *d_jobs = nullptr;
+    int nmax = 0;                                         // large views first: the one-block gates and LM chains are dispatched in job order
+    const int rc = job_array_stage(ctx->register_jobs, num_pairs, st, [&](int i) { return pairs[i]->n; },
+                                   [&](RegisterArgs &job, int i) { register_args(pairs[i], d_sifts[i], p, d_points[i], d_valid[i], job); }, &d_jobs, &nmax);
     if (rc != SFM_OK) return rc;
     const int hblocks = (int)((p.num_hypotheses + kRegHypBlock - 1) / kRegHypBlock);
-    const int splits = register_splits(ctx->num_cus, hblocks, num_pairs, h_jobs[0].n);       // ONE for the launch: counts do not depend on it
+    const int splits = register_splits(ctx->num_cus, hblocks, num_pairs, nmax);              // ONE for the launch: counts do not depend on it
     hipLaunchKernelGGL(register_gate_views_kernel, dim3(num_pairs), dim3(kRegGateThreads), 0, st, d_jobs);
     SFM_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(register_solve_views_kernel, dim3(hblocks, num_pairs), dim3(kRegHypBlock), 0, st, d_jobs);

@@ -22,8 +22,6 @@
 #include "block_ops.hpp"
 #include "view_points_math.hpp"
 #include <math.h>
-#include <algorithm>
-#include <vector>
 
 namespace sfm {
 
@@ -164,21 +162,10 @@ int launch_view_points_views(sfm_ctx *ctx, sfm_pair *const *pairs, int num_pairs
                              const sfm_view_points_out *outs)
 {
     hipStream_t st = ctx->stream;
-    JobArray &ja = ctx->view_points_jobs;
-    int rc = job_array_reserve(ja, (size_t)num_pairs, sizeof(ViewPointsArgs), st);
-    if (rc != SFM_OK) return rc;
-    // large pairs first (the blocks of a job are dispatched in job order).  Stable, so equal sizes keep the caller's order; a
-    // pair's result does not depend on its place (every block writes its own pair's outputs).
-    std::vector<int> order((size_t)num_pairs);
-    for (int i = 0; i < num_pairs; ++i) order[(size_t)i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return pairs[x]->n > pairs[y]->n; });
-    ViewPointsArgs *h_jobs = static_cast<ViewPointsArgs *>(ja.pinned);
-    for (int k = 0; k < num_pairs; ++k) {
-        const int i = order[(size_t)k];
-        view_points_args(pairs[i], in[i], p, outs[i], h_jobs[k]);
-    }
-    const ViewPointsArgs *d_jobs = static_cast<const ViewPointsArgs *>(ja.dev);
-    rc = job_array_upload(ja, (size_t)num_pairs, sizeof(ViewPointsArgs), st);
+    const ViewPointsArgs *d_jobs = nullptr;
+    int nmax = 0;                                         // large pairs first (the blocks of a job are dispatched in job order)
+    const int rc = job_array_stage(ctx->view_points_jobs, num_pairs, st, [&](int i) { return pairs[i]->n; },
+                                   [&](ViewPointsArgs &job, int i) { view_points_args(pairs[i], in[i], p, outs[i], job); }, &d_jobs, &nmax);
     if (rc != SFM_OK) return rc;
     // the count buffers: one memset per run of buffers that follow each other in memory (ONE when the caller keeps them in one array)
     for (int i = 0; i < num_pairs;) {
@@ -188,7 +175,6 @@ int launch_view_points_views(sfm_ctx *ctx, sfm_pair *const *pairs, int num_pairs
         if (first) SFM_HIP_TRY(hipMemsetAsync(first, 0, (size_t)run * 8 * sizeof(int32_t), st));
         i += run;
     }
-    const int nmax = h_jobs[0].n;
     if (nmax == 0) return SFM_OK;
     hipLaunchKernelGGL(view_points_views_kernel, dim3((nmax + kVpThreads - 1) / kVpThreads, num_pairs), dim3(kVpThreads), 0, st, d_jobs);
     SFM_HIP_TRY(hipGetLastError());
