@@ -83,6 +83,7 @@ EXPORTS = [
     "sfm_adjust_default_params", "sfm_adjust_view", "sfm_adjust_views",
     "sfm_align_default_params", "sfm_align_index_from_matches", "sfm_align_pair", "sfm_align_pairs",
     "sfm_fuse_default_params", "sfm_fuse_chain",
+    "sfm_adjust_chain_default_params", "sfm_adjust_chain",
 ]
 AB_EXPORTS = ["sfm_ransac_last_phases", "sfm_ransac_last_trace", "sfm_prefilter_probe", "sfm_prefilter_band_probe"]      # include/sfm_amd_ab.h
 if AB:
@@ -204,6 +205,34 @@ class FuseOut(C.Structure):
                 ("d_flags", C.c_void_p), ("d_err", C.c_void_p), ("d_counts", C.c_void_p)]
 
 
+class AdjustChainParams(C.Structure):
+    """sfm_adjust_chain_params (include/sfm_amd.h)."""
+    _fields_ = [("max_iterations", C.c_int32), ("huber_px", C.c_float), ("min_rel_decrease", C.c_float), ("initial_lambda", C.c_float),
+                ("max_track_views", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class AdjustChainIn(C.Structure):
+    """sfm_adjust_chain_in (include/sfm_amd.h): the host array of pair handles and what sfm_fuse_chain wrote."""
+    _fields_ = [("pairs", C.POINTER(C.c_void_p)), ("d_root", C.c_void_p), ("d_cams", C.c_void_p), ("d_track_offset", C.c_void_p),
+                ("d_obs_cam", C.c_void_p), ("d_obs_record", C.c_void_p), ("d_points", C.c_void_p), ("d_flags", C.c_void_p), ("d_counts", C.c_void_p)]
+
+
+class AdjustChainReport(C.Structure):
+    """sfm_adjust_chain_report (include/sfm_amd.h): one per pair, filled at a segment's root."""
+    _fields_ = [("root", C.c_int32), ("status", C.c_int32), ("iterations", C.c_int32), ("accepted", C.c_int32), ("num_cameras", C.c_int32),
+                ("num_tracks", C.c_int32), ("num_observations", C.c_int32), ("num_over_long", C.c_int32), ("initial_rms_px", C.c_float),
+                ("final_rms_px", C.c_float), ("final_cost", C.c_float), ("lambda_", C.c_float)]
+
+
+ADJUST_CHAIN_REPORT_DTYPE = np.dtype([(f if f != "lambda_" else "lambda", "<i4" if t is C.c_int32 else "<f4") for f, t in AdjustChainReport._fields_])
+assert ADJUST_CHAIN_REPORT_DTYPE.itemsize == C.sizeof(AdjustChainReport)
+
+
+class AdjustChainOut(C.Structure):
+    """sfm_adjust_chain_out (include/sfm_amd.h): the caller's device buffers."""
+    _fields_ = [("d_cams", C.c_void_p), ("d_points", C.c_void_p), ("d_used", C.c_void_p), ("d_err", C.c_void_p), ("d_reports", C.c_void_p)]
+
+
 FUSE_COUNTS = ("tracks", "observations", "refined", "kept", "segments", "longest_track")      # sfm_fuse_out.d_counts[0..5]
 
 _vp = C.c_void_p
@@ -302,6 +331,9 @@ _lib.sfm_align_pair.argtypes = [_vp, _vp, _vp, C.POINTER(AlignParams), C.POINTER
 _lib.sfm_align_pairs.argtypes = [C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.POINTER(AlignParams), C.POINTER(AlignOut)]
 _lib.sfm_fuse_default_params.argtypes = [C.POINTER(FuseParams)]
 _lib.sfm_fuse_default_params.restype = None
+_lib.sfm_adjust_chain_default_params.argtypes = [C.POINTER(AdjustChainParams)]
+_lib.sfm_adjust_chain_default_params.restype = None
+_lib.sfm_adjust_chain.argtypes = [_vp, C.POINTER(AdjustChainIn), C.c_int, C.POINTER(AdjustChainParams), C.POINTER(AdjustChainOut)]
 _lib.sfm_fuse_chain.argtypes = [_vp, C.POINTER(FusePairIn), C.c_int, C.POINTER(FuseLinkIn), C.POINTER(FuseParams), C.POINTER(FuseOut)]
 if AB:
     _lib.sfm_ransac_last_phases.argtypes = [_vp, C.POINTER(C.c_uint64)]
@@ -711,6 +743,70 @@ def _fuse_results(outs, k, N):
     return dict(frames=frames.reshape(k, 13), root=root, cams=cams.reshape(k, 2, 12), track=track, track_offset=off[:T + 1].copy(),
                 obs_cam=ocam[:M].copy(), obs_record=orec[:M].copy(), points=pts.reshape(4, N)[:, :T].copy(), flags=flags[:T].copy(),
                 err=err[:T].copy(), counts={name: int(counts[i]) for i, name in enumerate(FUSE_COUNTS)})
+
+
+_ADJUST_CHAIN_FIELDS = {f for f, _ in AdjustChainParams._fields_}
+
+
+def adjust_chain_params(**kw):
+    """sfm_adjust_chain_params with the library's defaults (10 iterations, Huber 1 px, 1e-6, lambda 1e-3, tracks of at most 8
+    views), fields overridden by kw."""
+    p = AdjustChainParams()
+    _lib.sfm_adjust_chain_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "reserved":
+            for i, x in enumerate(v):
+                p.reserved[i] = int(x)
+        elif k in _ADJUST_CHAIN_FIELDS:
+            setattr(p, k, v)
+        else:
+            raise TypeError(f"adjust_chain_params: no field {k!r} in sfm_adjust_chain_params")
+    return p
+
+
+def adjust_chain_enqueue(ctx, pairs, fused, params, outs):
+    """sfm_adjust_chain (enqueue only).  pairs: the ImagePairs of the chain; fused: device tensors / pointers (root, cams,
+    track_offset, obs_cam, obs_record, points, flags, counts) that fuse_chain_enqueue filled; outs: device tensors / pointers in the
+    order of sfm_adjust_chain_out (err may be None), the reports as bytes (ADJUST_CHAIN_REPORT_DTYPE.itemsize per pair)."""
+    k = len(pairs)
+    handles = (C.c_void_p * max(k, 1))(*[p._h.value if p is not None else None for p in pairs])
+    i = AdjustChainIn(C.cast(handles, C.POINTER(C.c_void_p)), *[_ptr(t) for t in fused]) if fused is not None else None
+    o = AdjustChainOut(*[_ptr(t) for t in outs]) if outs is not None else None
+    _check(_lib.sfm_adjust_chain(ctx._h if ctx is not None else None, C.byref(i) if i is not None else None, k,
+                                 C.byref(params) if params is not None else None, C.byref(o) if o is not None else None), "sfm_adjust_chain")
+
+
+def adjust_chain_buffers(device, k, N):
+    """Output tensors of one adjust_chain call in the order of sfm_adjust_chain_out, for k pairs with N records in all."""
+    e = lambda n, dt: torch.empty(int(n), dtype=dt, device=device)
+    return (e(24 * k, torch.float32), e(4 * N, torch.float32), e(N, torch.uint8), e(N, torch.float32),
+            e(k * ADJUST_CHAIN_REPORT_DTYPE.itemsize, torch.uint8))
+
+
+def adjust_chain_results(outs, k, N, T):
+    """The tensors of adjust_chain_buffers -> a dict of numpy arrays trimmed to the T tracks: cams (k, 2, 12), points (4, T), used (T),
+    err (T), reports (k records of ADJUST_CHAIN_REPORT_DTYPE)."""
+    cams, pts, used, err, rep = (t.cpu().numpy() for t in outs)
+    return dict(cams=cams.reshape(k, 2, 12), points=pts.reshape(4, N)[:, :T].copy(), used=used[:T].copy(), err=err[:T].copy(),
+                reports=rep.view(ADJUST_CHAIN_REPORT_DTYPE).copy())
+
+
+def adjust_chain(pairs, fused, **kw):
+    """One bundle adjustment over a fused chain: every camera and every used track together, per segment.  pairs: the ImagePairs of
+    the chain; fused: the device tensors of a fuse_chain_enqueue call in the order of sfm_fuse_out; kw are AdjustChainParams
+    fields.  Allocates the outputs, waits once and returns adjust_chain_results' dict."""
+    params = adjust_chain_params(**kw)
+    k = len(pairs)
+    if k == 0:
+        return dict(reports=np.zeros(0, ADJUST_CHAIN_REPORT_DTYPE))
+    ctx = pairs[0].ctx
+    dev = torch.device("cuda", ctx.device)
+    N = sum(p.num_points for p in pairs)
+    frames, root, cams, track, off, ocam, orec, pts, flags, err, counts = fused
+    outs = adjust_chain_buffers(dev, k, N)
+    adjust_chain_enqueue(ctx, pairs, (root, cams, off, ocam, orec, pts, flags, counts), params, outs)
+    ctx.synchronize()
+    return adjust_chain_results(outs, k, N, int(counts[0].item()))
 
 
 def sift_temp_layout(width, height, num_octaves=5, scale_up=False):

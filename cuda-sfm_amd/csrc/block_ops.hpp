@@ -56,6 +56,48 @@ __device__ __forceinline__ void block_sum(double (&v)[N], double *s_part, double
     __syncthreads();
 }
 
+// Sums of COUNT (<= 64) values over the wavefront, one per lane and value, in fp64, transposed: lane L returns the sum over all 64
+// lanes of v[L & (W - 1)] where W = 64 for COUNT > 32 and 32 otherwise (values past COUNT count as 0).  Log-step halving: at the
+// step with lane distance d a lane keeps the half of its partial sums that its bit d selects and receives the other lane's
+// partials for that half, so the steps exchange W / 2, W / 4, ..., 1 values (W - 1 shuffles) instead of six per value, and the
+// shuffles of one step are independent of each other.  The first step moves the fp32 terms and adds them as doubles.  The order
+// of every sum is fixed by the lane numbers alone.  (adjust.hip's system pass, chain_adjust.hip's.)
+template <int D>
+__device__ __forceinline__ void wave_halve(double (&a)[32], const int lane)
+{
+    const bool hi = (lane & D) != 0;
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        const double keep = hi ? a[D + i] : a[i], send = hi ? a[i] : a[D + i];
+        a[i] = keep + __shfl_xor(send, D);
+    }
+}
+
+template <int COUNT>
+__device__ __forceinline__ double wave_transpose_sum(const float *v, const int lane)
+{
+    static_assert(COUNT >= 1 && COUNT <= 64, "one value per lane at the most");
+    double a[32];
+    if (COUNT > 32) {
+        const bool hi = (lane & 32) != 0;
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            const float up = 32 + i < COUNT ? v[32 + i < COUNT ? 32 + i : 0] : 0.0f;
+            const float keep = hi ? up : v[i], send = hi ? v[i] : up;
+            a[i] = (double)keep + (double)__shfl_xor(send, 32);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 32; ++i) a[i] = i < COUNT ? (double)v[i < COUNT ? i : 0] + (double)__shfl_xor(v[i < COUNT ? i : 0], 32) : 0.0;
+    }
+    wave_halve<16>(a, lane);
+    wave_halve<8>(a, lane);
+    wave_halve<4>(a, lane);
+    wave_halve<2>(a, lane);
+    wave_halve<1>(a, lane);
+    return a[0];
+}
+
 // Exclusive scan of one value per thread over a block of WAVES wavefronts: returns the sum of the lower threads' values and
 // leaves the total in wsum[WAVES] (wsum: LDS [WAVES + 1]).  Two barriers, none in front: a caller that scans again with the
 // same wsum puts a __syncthreads() between its last read of wsum and the next call.

@@ -3,10 +3,12 @@
 //   per pair: features -> MatchSiftData -> SfM::Image_pair -> fillXU -> estimateE; ONE refine_pairs over all of them; ONE
 //   fuse_chain over the chain (pair i -> pair i + 1).
 // The arguments are align_pairs_demo's:
-//     fuse_chain_demo <k> <a1.bin> .. <ak.bin> <b1.bin> .. <bk.bin> [cloud.ply]
+//     fuse_chain_demo <k> <a1.bin> .. <ak.bin> <b1.bin> .. <bk.bin> [cloud.ply [adjust_iterations]]
 // a_i / b_i: files of raw SiftPoint records of pair i's first / second view; a_{i+1} must hold the records of b_i's view.
 // One `fuse:` line, then the fused cloud of the first segment -- one point per track, where align_pairs_demo writes a feature
-// once per pair that sees it -- as a PLY (default fused_cloud.ply).  Plain C++: needs only the facade headers and libsfm_amd.so.
+// once per pair that sees it -- as a PLY (default fused_cloud.ply).  With adjust_iterations > 0 (default 0: nothing changes) one
+// SfM::adjust_chain over the fused model follows, one `chain adjust:` line per segment is printed and the PLY holds the adjusted
+// points.  Plain C++: needs only the facade headers and libsfm_amd.so.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -41,11 +43,12 @@ static void upload(SiftData &data, const std::vector<SiftPoint> &f, const char *
 int main(int argc, char **argv)
 {
     const int count = argc > 1 ? std::atoi(argv[1]) : 0;
-    if (count < 1 || (argc != 2 + 2 * count && argc != 3 + 2 * count)) {
-        std::fprintf(stderr, "usage: %s k a1.bin .. ak.bin b1.bin .. bk.bin [cloud.ply]   (k >= 1)\n", argv[0]);
+    if (count < 1 || argc < 2 + 2 * count || argc > 4 + 2 * count) {
+        std::fprintf(stderr, "usage: %s k a1.bin .. ak.bin b1.bin .. bk.bin [cloud.ply [adjust_iterations]]   (k >= 1)\n", argv[0]);
         return 2;
     }
-    const char *ply = argc == 3 + 2 * count ? argv[2 + 2 * count] : "fused_cloud.ply";
+    const char *ply = argc >= 3 + 2 * count ? argv[2 + 2 * count] : "fused_cloud.ply";
+    const int adjust_iterations = argc == 4 + 2 * count ? std::atoi(argv[3 + 2 * count]) : 0;
     const unsigned w = 720, h = 576;                        // the dino frames
     float K[9] = { 2360.0f, 0, (float)(w / 2.0), 0, 2360, (float)(h / 2.0), 0, 0, 1 };
     float inv_K[9] = { (float)(1.0 / 2360), 0, (float)(-(w / 2.0) / 2360), 0, (float)(1.0 / 2360), (float)(-(h / 2.0) / 2360), 0, 0, 1 };
@@ -83,13 +86,25 @@ int main(int argc, char **argv)
     std::printf("fuse: %d tracks, %d observations, %d refined, %d kept, %d segments, longest track %d views\n", model.tracks, model.observations,
                 model.refined, model.kept, model.segments, model.longest_track);
 
-    // the first segment's tracks: one point each
     const int T = model.tracks;
+    std::vector<float> points = model.points;
+    if (adjust_iterations > 0) {
+        const SfM::AdjustedChain adj = SfM::adjust_chain(pairs.data(), count, model, adjust_iterations);
+        for (int i = 0; i < count; ++i) {
+            const sfm_adjust_chain_report &rep = adj.reports[(size_t)i];
+            if (rep.root != i) continue;
+            std::printf("chain adjust: segment %d: %d cameras, %d tracks, rms %.6g -> %.6g px, %d iterations\n", rep.root, rep.num_cameras,
+                        rep.num_tracks, (double)rep.initial_rms_px, (double)rep.final_rms_px, rep.iterations);
+        }
+        points = adj.points;
+    }
+
+    // the first segment's tracks: one point each
     std::vector<float> cloud;                               // x, y, z per point
     for (int t = 0; t < T; ++t) {
         const int pair = model.obs_cam[(size_t)model.track_offset[(size_t)t]] >> 1;
         if (model.root[(size_t)pair] != 0) continue;
-        for (int c = 0; c < 3; ++c) cloud.push_back(model.points[(size_t)c * T + t]);
+        for (int c = 0; c < 3; ++c) cloud.push_back(points[(size_t)c * T + t]);
     }
     const int total = (int)(cloud.size() / 3);
     std::vector<float> cols((size_t)4 * total, 1.0f);       // WritePLY's 4 x N layout

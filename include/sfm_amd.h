@@ -621,6 +621,63 @@ void sfm_fuse_default_params(sfm_fuse_params *p);
 int  sfm_fuse_chain(sfm_ctx *ctx, const sfm_fuse_pair_in *pairs, int num_pairs, const sfm_fuse_link_in *links,
                     const sfm_fuse_params *p, const sfm_fuse_out *out);          /* enqueue only */
 
+/* ---- one bundle adjustment over a fused chain: every camera and every track together --------------
+ * Reads the pairs and what sfm_fuse_chain wrote for them.  One unknown camera per pair p: its camera 2 (view p + 1), started at
+ * slot 2p + 1 of d_cams.  Camera 1 of pair p is the segment's fixed [I|0] where d_root[p] == p and the camera 2 of pair p - 1
+ * otherwise (slot 2p of d_cams is not read for such a pair): one camera per view.  Per segment the root pair's camera moves with
+ * sfm_refine_two_view's 5 degrees of freedom (t on the unit sphere, the start t normalised), every other camera with
+ * sfm_register_view's 6.  Segments are independent Levenberg-Marquardt problems with a report each.
+ * A track is used when its flag is SFM_FUSE_REFINED, it has at most max_track_views views, its point is finite and lies in front
+ * of every one of its views under the start cameras; an unused track returns its input column.  A segment whose root camera
+ * has fewer than 16 used observations, or any other camera fewer than 6, is SFM_REFINE_DEGENERATE (not an error): its cameras
+ * (both input slots) and its tracks' columns are returned as they came in.
+ * Residuals are pixels through the observing pair's K, Huber per view.  The reduced camera system is block-banded (a track's
+ * views are consecutive) and solved by a banded Cholesky in fp64.  No float atomics: two calls give the same bytes.
+ * The call READS the pairs and writes only the caller's buffers: no stage, buffer id or getter belongs to it. */
+typedef struct sfm_adjust_chain_params {
+    int32_t max_iterations;                               /* accepted + rejected, 0..50; default 10                    */
+    float   huber_px, min_rel_decrease, initial_lambda;   /* 1.0 / 1e-6 / 1e-3                                          */
+    int32_t max_track_views;                              /* W, 2..16; default 8: longer tracks are not used            */
+    int32_t reserved[4];                                  /* must be zero (else SFM_E_INVALID)                          */
+} sfm_adjust_chain_params;
+typedef struct sfm_adjust_chain_in {   /* pairs: HOST array; the rest DEVICE, what sfm_fuse_out holds; all required   */
+    sfm_pair *const *pairs;
+    const int32_t *d_root;             /* k                                                                           */
+    const float   *d_cams;             /* 24 x k                                                                      */
+    const int32_t *d_track_offset;     /* N + 1                                                                       */
+    const int32_t *d_obs_cam;          /* 2N                                                                          */
+    const int32_t *d_obs_record;       /* 2N                                                                          */
+    const float   *d_points;           /* 4 x N                                                                       */
+    const uint8_t *d_flags;            /* N                                                                           */
+    const int32_t *d_counts;           /* 8                                                                           */
+} sfm_adjust_chain_in;
+typedef struct sfm_adjust_chain_report {   /* entry p: all zero but `root` unless p is its segment's root             */
+    int32_t root;                      /* the first pair of pair p's segment                                          */
+    int32_t status;                    /* SFM_REFINE_*                                                                */
+    int32_t iterations, accepted;
+    int32_t num_cameras;               /* pairs of the segment                                                        */
+    int32_t num_tracks, num_observations;      /* used tracks and their observations                                  */
+    int32_t num_over_long;             /* tracks of the segment with more than max_track_views views                  */
+    float   initial_rms_px, final_rms_px;      /* sqrt(sum of squares / (2 num_observations))                         */
+    float   final_cost, lambda;
+} sfm_adjust_chain_report;
+typedef struct sfm_adjust_chain_out {  /* DEVICE buffers of the caller; all required unless marked                    */
+    float   *d_cams;       /* 24 x k, the layout of sfm_fuse_out.d_cams: inside a segment camera 1 of pair p + 1 is the
+                              bytes of camera 2 of pair p                                                             */
+    float   *d_points;     /* 4 x N, leading dimension N                                                              */
+    uint8_t *d_used;       /* N: 1 = the track was used                                                               */
+    float   *d_err;        /* N, optional: the largest pixel error over the track's views under the final cameras,
+                              +inf behind a camera; written for every track                                           */
+    sfm_adjust_chain_report *d_reports;    /* k                                                                       */
+} sfm_adjust_chain_out;
+void sfm_adjust_chain_default_params(sfm_adjust_chain_params *p);
+/* num_pairs 0..4096, N (the pairs' records in all) at most 2^26.  Zero pairs is SFM_OK and writes nothing.  Every pair belongs
+ * to ctx, is listed once and needs its normalised observations and K (the points stage).  No output may overlap an input or
+ * another output.  Every check precedes the first enqueue: on SFM_E_INVALID / SFM_E_STATE (the text names pairs[i]) nothing is
+ * written.  The work buffer belongs to the context. */
+int  sfm_adjust_chain(sfm_ctx *ctx, const sfm_adjust_chain_in *in, int num_pairs, const sfm_adjust_chain_params *p,
+                      const sfm_adjust_chain_out *out);                          /* enqueue only */
+
 /* ---- accessors (the reference keeps these private; needed for parity checks) ------------------ */
 #define SFM_BUF_X0      0   /* float 3 x ld   normalised coords image 1 (ld = sfm_pair_ld)   */
 #define SFM_BUF_X1      1
