@@ -54,6 +54,7 @@ REFINE_CONVERGED, REFINE_MAX_ITER, REFINE_DEGENERATE = 0, 1, 2         # sfm_ref
 VP_UNSEEN, VP_NEW, VP_REFINED, VP_NEW_REJECTED, VP_KEPT = range(5)     # sfm_view_points_out.d_flags
 ADJ_VIEW1, ADJ_VIEW2, ADJ_VIEW3 = 1, 2, 4                              # bits of sfm_adjust_out.d_views
 FUSE_REFINED, FUSE_KEPT = 1, 2                                         # sfm_fuse_out.d_flags
+RING_CLOSED, RING_OPEN, RING_REJECTED = 0, 1, 2                        # sfm_ring_report.status
 
 SIFT_DTYPE = np.dtype([
     ("xpos", "<f4"), ("ypos", "<f4"), ("scale", "<f4"), ("sharpness", "<f4"),
@@ -84,6 +85,7 @@ EXPORTS = [
     "sfm_align_default_params", "sfm_align_index_from_matches", "sfm_align_pair", "sfm_align_pairs",
     "sfm_fuse_default_params", "sfm_fuse_chain",
     "sfm_adjust_chain_default_params", "sfm_adjust_chain",
+    "sfm_ring_default_params", "sfm_close_ring",
 ]
 AB_EXPORTS = ["sfm_ransac_last_phases", "sfm_ransac_last_trace", "sfm_prefilter_probe", "sfm_prefilter_band_probe"]      # include/sfm_amd_ab.h
 if AB:
@@ -233,6 +235,30 @@ class AdjustChainOut(C.Structure):
     _fields_ = [("d_cams", C.c_void_p), ("d_points", C.c_void_p), ("d_used", C.c_void_p), ("d_err", C.c_void_p), ("d_reports", C.c_void_p)]
 
 
+class RingParams(C.Structure):
+    """sfm_ring_params (include/sfm_amd.h); weights is a HOST pointer."""
+    _fields_ = [("threshold_px", C.c_float), ("max_rotation_rad", C.c_float), ("max_log_scale", C.c_float), ("weights", C.c_void_p),
+                ("reserved", C.c_int32 * 4)]
+
+
+class RingLinkIn(C.Structure):
+    """sfm_ring_link_in (include/sfm_amd.h): what sfm_align_pairs gave for one link of the ring."""
+    _fields_ = [("d_sim", C.c_void_p), ("d_report", C.c_void_p)]
+
+
+class RingReport(C.Structure):
+    """sfm_ring_report (include/sfm_amd.h)."""
+    _fields_ = [("status", C.c_int32), ("num_links", C.c_int32), ("first_invalid", C.c_int32), ("drift_log_scale", C.c_float),
+                ("drift_rotation_rad", C.c_float), ("drift_t", C.c_float), ("seam_count", C.c_int32), ("seam_lost_open", C.c_int32),
+                ("seam_lost_closed", C.c_int32), ("seam_rms_link_px", C.c_float), ("seam_rms_open_px", C.c_float),
+                ("seam_rms_closed_px", C.c_float)]
+
+
+class RingOut(C.Structure):
+    """sfm_ring_out (include/sfm_amd.h): the caller's device buffers."""
+    _fields_ = [("d_links", C.c_void_p), ("d_frames", C.c_void_p), ("d_seam_err", C.c_void_p), ("d_report", C.c_void_p)]
+
+
 FUSE_COUNTS = ("tracks", "observations", "refined", "kept", "segments", "longest_track")      # sfm_fuse_out.d_counts[0..5]
 
 _vp = C.c_void_p
@@ -334,6 +360,9 @@ _lib.sfm_fuse_default_params.restype = None
 _lib.sfm_adjust_chain_default_params.argtypes = [C.POINTER(AdjustChainParams)]
 _lib.sfm_adjust_chain_default_params.restype = None
 _lib.sfm_adjust_chain.argtypes = [_vp, C.POINTER(AdjustChainIn), C.c_int, C.POINTER(AdjustChainParams), C.POINTER(AdjustChainOut)]
+_lib.sfm_ring_default_params.argtypes = [C.POINTER(RingParams)]
+_lib.sfm_ring_default_params.restype = None
+_lib.sfm_close_ring.argtypes = [_vp, C.POINTER(RingLinkIn), C.c_int, C.POINTER(FusePairIn), C.POINTER(RingParams), C.POINTER(RingOut)]
 _lib.sfm_fuse_chain.argtypes = [_vp, C.POINTER(FusePairIn), C.c_int, C.POINTER(FuseLinkIn), C.POINTER(FuseParams), C.POINTER(FuseOut)]
 if AB:
     _lib.sfm_ransac_last_phases.argtypes = [_vp, C.POINTER(C.c_uint64)]
@@ -743,6 +772,73 @@ def _fuse_results(outs, k, N):
     return dict(frames=frames.reshape(k, 13), root=root, cams=cams.reshape(k, 2, 12), track=track, track_offset=off[:T + 1].copy(),
                 obs_cam=ocam[:M].copy(), obs_record=orec[:M].copy(), points=pts.reshape(4, N)[:, :T].copy(), flags=flags[:T].copy(),
                 err=err[:T].copy(), counts={name: int(counts[i]) for i, name in enumerate(FUSE_COUNTS)})
+
+
+_RING_FIELDS = {f for f, _ in RingParams._fields_}
+
+
+def ring_params(**kw):
+    """sfm_ring_params with the library's defaults (4 px, 0.35 rad, ln 2, the weights from the links' reports), fields overridden
+    by kw.  weights: a sequence of k floats; the host array is kept alive by the returned struct."""
+    p = RingParams()
+    _lib.sfm_ring_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "reserved":
+            for i, x in enumerate(v):
+                p.reserved[i] = int(x)
+        elif k == "weights":
+            p._weights = None if v is None else np.ascontiguousarray(v, np.float32)
+            p.weights = None if v is None else p._weights.ctypes.data
+        elif k in _RING_FIELDS:
+            setattr(p, k, v)
+        else:
+            raise TypeError(f"ring_params: no field {k!r} in sfm_ring_params")
+    return p
+
+
+def _ring_buffers(device, k, n):
+    """Output tensors of one close_ring call in the order of sfm_ring_out, for k links and a last pair of n records."""
+    e = lambda m, dt: torch.empty(int(m), dtype=dt, device=device)
+    return (e(13 * k, torch.float32), e(13 * k, torch.float32), e(3 * n, torch.float32), e(C.sizeof(RingReport), torch.uint8))
+
+
+def close_ring_enqueue(ctx, links, last_pair, params, outs):
+    """sfm_close_ring (enqueue only).  links: one (sim, report) tuple of device tensors / pointers per link of the ring (k of them,
+    the closing link last); last_pair: pair k - 1 as an ImagePair or an (ImagePair, points, valid) tuple of device tensors /
+    pointers / None; outs: device tensors / pointers in the order of sfm_ring_out (seam_err may be None)."""
+    k = len(links)
+    lin = (RingLinkIn * max(k, 1))(*[RingLinkIn(*[_ptr(t) for t in x]) for x in links])
+    pin = None
+    if last_pair is not None:
+        x = last_pair if isinstance(last_pair, tuple) else (last_pair, None, None)
+        pin = FusePairIn(x[0]._h.value if x[0] is not None else None, _ptr(x[1]), _ptr(x[2]), None)
+    o = RingOut(*[_ptr(t) for t in outs]) if outs is not None else None
+    _check(_lib.sfm_close_ring(ctx._h if ctx is not None else None, lin, k, C.byref(pin) if pin is not None else None,
+                               C.byref(params) if params is not None else None, C.byref(o) if o is not None else None), "sfm_close_ring")
+
+
+def _ring_results(outs, k, n):
+    """The tensors of _ring_buffers -> (links (k, 13), frames (k, 13), seam errors (3, n), report dict)."""
+    links, frames, seam, rep = (t.cpu().numpy() for t in outs)
+    r = RingReport.from_buffer_copy(rep.tobytes())
+    return links.reshape(k, 13), frames.reshape(k, 13), seam.reshape(3, n), {f: getattr(r, f) for f, _ in RingReport._fields_}
+
+
+def close_ring(last_pair, align_outs, override=None, **kw):
+    """The ring of k pairs closed: the drift of its k links measured and spread over them.  last_pair: the ImagePair k - 1 (views
+    k - 1 and 0); align_outs: per link the device tensors (sim, inlier, err, counts, report) an align_pairs_enqueue call filled --
+    or (sim, report) -- the closing link (pair k - 1 onto pair 0) last; override: None or the pair's (points, valid) device tensors;
+    kw are RingParams fields.  Allocates the outputs, waits once and returns the corrected links (k, 13), the closed frames (k, 13),
+    the seam's pixel errors (3, n: link, open, closed) and the report as a dict.  The first k - 1 corrected links go into
+    fuse_chain_enqueue in place of the measured ones."""
+    params = ring_params(**kw)
+    k, n = len(align_outs), last_pair.num_points
+    ctx = last_pair.ctx
+    outs = _ring_buffers(torch.device("cuda", ctx.device), k, n)
+    links = [(a[0], a[-1]) for a in align_outs]
+    close_ring_enqueue(ctx, links, (last_pair,) + tuple(override) if override is not None else last_pair, params, outs)
+    ctx.synchronize()
+    return _ring_results(outs, k, n)
 
 
 _ADJUST_CHAIN_FIELDS = {f for f, _ in AdjustChainParams._fields_}

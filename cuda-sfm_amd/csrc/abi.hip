@@ -4,6 +4,7 @@
 #include "device_math.hpp"
 #include "fuse_math.hpp"
 #include "chain_adjust_math.hpp"
+#include "ring_math.hpp"
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -299,6 +300,8 @@ static int ctx_destroy_now(sfm_ctx *ctx)
     if (ctx->fuse_ws) (void)hipFree(ctx->fuse_ws);
     job_array_free(ctx->chain_jobs);
     if (ctx->chain_ws) (void)hipFree(ctx->chain_ws);
+    job_array_free(ctx->ring_jobs);
+    if (ctx->ring_ws) (void)hipFree(ctx->ring_ws);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     for (auto &t : ctx->tev) for (hipEvent_t e : t) if (e) (void)hipEventDestroy(e);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -1628,6 +1631,82 @@ int sfm_adjust_chain(sfm_ctx *ctx, const sfm_adjust_chain_in *in, int num_pairs,
         f.n = pr->n; f.ld = pr->ld;
     }
     return launch_adjust_chain(ctx, fp.data(), num_pairs, *in, *p, *out);       // reads the pairs: no stage changes
+}
+
+// ---- a ring of aligned pairs closed: the drift spread over the links (ring.hip) -------------------
+void sfm_ring_default_params(sfm_ring_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->threshold_px = 4.0f;
+    p->max_rotation_rad = 0.35f;
+    p->max_log_scale = 0.693147182f;                      // ln 2
+}
+
+int sfm_close_ring(sfm_ctx *ctx, const sfm_ring_link_in *links, int num_links, const sfm_fuse_pair_in *last_pair, const sfm_ring_params *p,
+                   const sfm_ring_out *out)
+{
+    // the checks that need no device first, all of them before anything is enqueued
+    SFM_REQUIRE(p, SFM_E_INVALID, "null params");
+    SFM_REQUIRE(num_links >= 3 && num_links <= 4096, SFM_E_INVALID, "num_links %d outside 3..4096", num_links);
+    SFM_REQUIRE(ctx && links && last_pair && out, SFM_E_INVALID, "null context, link list, last_pair or out");
+    for (int i = 0; i < num_links; ++i)
+        SFM_REQUIRE(links[i].d_sim && links[i].d_report, SFM_E_INVALID, "links[%d]: d_sim and d_report are required", i);
+    SFM_REQUIRE(last_pair->pair, SFM_E_INVALID, "last_pair: null pair");
+    SFM_REQUIRE(last_pair->d_points || !last_pair->d_valid, SFM_E_INVALID, "last_pair: d_valid needs d_points");
+    SFM_REQUIRE(out->d_links && out->d_frames && out->d_report, SFM_E_INVALID, "every buffer of sfm_ring_out but d_seam_err is required");
+    SFM_REQUIRE(p->reserved[0] == 0 && p->reserved[1] == 0 && p->reserved[2] == 0 && p->reserved[3] == 0, SFM_E_INVALID,
+                "sfm_ring_params.reserved[] must be zero");
+    SFM_REQUIRE(p->max_rotation_rad > 0.0f && p->max_rotation_rad <= 1.57079637f, SFM_E_INVALID, "max_rotation_rad must lie in (0, pi/2]");
+    SFM_REQUIRE(isfinite(p->max_log_scale) && p->max_log_scale > 0.0f, SFM_E_INVALID, "max_log_scale must be finite and > 0");
+    SFM_REQUIRE(isfinite(p->threshold_px) && p->threshold_px > 0.0f, SFM_E_INVALID, "threshold_px must be finite and > 0");
+    if (p->weights) {
+        double sum = 0.0;
+        for (int i = 0; i < num_links; ++i) {
+            SFM_REQUIRE(isfinite(p->weights[i]) && p->weights[i] >= 0.0f, SFM_E_INVALID, "links[%d]: its weight must be finite and >= 0", i);
+            sum += (double)p->weights[i];
+        }
+        SFM_REQUIRE(sum > 0.0, SFM_E_INVALID, "the weights must have a positive sum");
+    }
+    sfm_pair *pr = last_pair->pair;
+    SFM_REQUIRE(pr->ctx == ctx, SFM_E_INVALID, "last_pair: the pair belongs to another context");
+    {
+        // no output on an input or on another output: every range its own owner, so the sweep is the whole check
+        std::vector<BufferRange> r;
+        std::vector<int> entry;
+        r.reserve((size_t)num_links * 2 + 6);
+        entry.reserve((size_t)num_links * 2 + 6);
+        auto add = [&](const void *ptr, size_t bytes, bool is_out, int who, const char *name) {
+            r.push_back({ ptr, bytes, is_out, (int)entry.size(), name });
+            entry.push_back(who);
+        };
+        const size_t n = (size_t)pr->n, k = (size_t)num_links;
+        for (int i = 0; i < num_links; ++i) {
+            add(links[i].d_sim, 52, false, i, "links[%d].d_sim");
+            add(links[i].d_report, sizeof(sfm_align_report), false, i, "links[%d].d_report");
+        }
+        add(last_pair->d_points, n * 16, false, -1, "last_pair.d_points"); add(last_pair->d_valid, n, false, -1, "last_pair.d_valid");
+        add(out->d_links, k * 52, true, -1, "out.d_links"); add(out->d_frames, k * 52, true, -1, "out.d_frames");
+        add(out->d_seam_err, n * 12, true, -1, "out.d_seam_err"); add(out->d_report, sizeof(sfm_ring_report), true, -1, "out.d_report");
+        if (const RangeConflict c = first_conflict_across_owners(r)) {
+            char a[48], b[48];
+            snprintf(a, sizeof(a), c.a->name, entry[(size_t)c.a->owner]); snprintf(b, sizeof(b), c.b->name, entry[(size_t)c.b->owner]);
+            SFM_REQUIRE(false, SFM_E_INVALID, "%s overlaps %s", c.a->out ? a : b, c.a->out ? b : a);       // the output first
+        }
+    }
+    SFM_FLUSH(pr);
+    const uint32_t stages = last_pair->d_points ? kPoints : kPoints | kRefined;
+    SFM_REQUIRE(pr->state.has(stages), SFM_E_STATE, "last_pair: %s", pair_stage_hint(pr->state.missing(stages)));
+    SFM_HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<RingLink> rl((size_t)num_links);
+    for (int i = 0; i < num_links; ++i) rl[(size_t)i] = { links[i].d_sim, links[i].d_report, p->weights ? (double)p->weights[i] : 0.0 };
+    FusePair f;
+    memset(&f, 0, sizeof(f));
+    f.points = last_pair->d_points ? last_pair->d_points : pr->d_rpoints;
+    f.valid = last_pair->d_points ? last_pair->d_valid : reproj_flags(pr, pr->d_rreproj);
+    f.X0 = pr->d_X[0]; f.X1 = pr->d_X[1]; f.K = pr->d_K;
+    f.n = pr->n; f.ld = pr->ld;
+    return launch_close_ring(ctx, rl.data(), num_links, f, *p, *out);                        // reads the pair: no stage changes
 }
 
 // ---- accessors ------------------------------------------------------------------------------------

@@ -206,11 +206,14 @@ struct sfm_ctx {
     // sfm_refine_pairs / sfm_register_views / sfm_triangulate_views: the RefineArgs (refine.hip) / RegisterArgs (register.hip) /
     // ViewPointsArgs (view_points.hip) of a call; sfm_adjust_views: the AdjustArgs (adjust.hip); sfm_align_pairs: the AlignArgs
     // (align.hip); sfm_fuse_chain and sfm_adjust_chain: the FusePair (fuse_math.hpp) of every pair
-    sfm::JobArray refine_jobs, register_jobs, view_points_jobs, adjust_jobs, align_jobs, fuse_jobs, chain_jobs;
+    // sfm_close_ring: the RingLink (ring_math.hpp) of every link
+    sfm::JobArray refine_jobs, register_jobs, view_points_jobs, adjust_jobs, align_jobs, fuse_jobs, chain_jobs, ring_jobs;
     void *fuse_ws = nullptr;           // sfm_fuse_chain: per-node keys, successors, path lengths and classes, the block counts (fuse.hip)
     size_t fuse_ws_bytes = 0;
     void *chain_ws = nullptr;          // sfm_adjust_chain: states, points, partial bands, the band and the segments (chain_adjust.hip)
     size_t chain_ws_bytes = 0;
+    void *ring_ws = nullptr;           // sfm_close_ring: the fp64 frames, weights and running sums, the seam's block partials (ring.hip)
+    size_t ring_ws_bytes = 0;
     void *sift_job = nullptr;          // the extraction in flight (sift.hip: SiftJob), sfm_extract_sift_begin .. _end
     // kernels that already opted in to > 64 KiB of dynamic LDS on THIS context's device (function attributes are
     // per device; a context is used by one host thread at a time, so no process-wide flag)
@@ -422,6 +425,11 @@ int launch_fuse_chain(sfm_ctx *ctx, const FusePair *pairs, int num_pairs, const 
 // chain_adjust.hip: one bundle adjustment over a fused chain; pairs: HOST array (X0, X1, K, n, ld resolved by the caller)
 int launch_adjust_chain(sfm_ctx *ctx, const FusePair *pairs, int num_pairs, const sfm_adjust_chain_in &in, const sfm_adjust_chain_params &p,
                         const sfm_adjust_chain_out &out);
+
+// ring.hip: the drift of a ring measured and spread over its links; links: HOST array, last: pair k - 1 (points, valid, X1, K, n, ld
+// resolved by the caller)
+struct RingLink;
+int launch_close_ring(sfm_ctx *ctx, const RingLink *links, int num_links, const FusePair &last, const sfm_ring_params &p, const sfm_ring_out &out);
 
 // sift.hip
 void sift_layout(int width, int height, int num_octaves, int scale_up, sfm_sift_layout *L);

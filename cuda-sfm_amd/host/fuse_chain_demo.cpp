@@ -3,16 +3,21 @@
 //   per pair: features -> MatchSiftData -> SfM::Image_pair -> fillXU -> estimateE; ONE refine_pairs over all of them; ONE
 //   fuse_chain over the chain (pair i -> pair i + 1).
 // The arguments are align_pairs_demo's:
-//     fuse_chain_demo <k> <a1.bin> .. <ak.bin> <b1.bin> .. <bk.bin> [cloud.ply [adjust_iterations]]
+//     fuse_chain_demo <k> <a1.bin> .. <ak.bin> <b1.bin> .. <bk.bin> [cloud.ply [adjust_iterations [ring]]]
 // a_i / b_i: files of raw SiftPoint records of pair i's first / second view; a_{i+1} must hold the records of b_i's view.
+// With the word `ring` behind adjust_iterations the pairs are a ring (k >= 3, b_k holds the records of a_1's view): pair k is also
+// aligned onto pair 1, SfM::close_ring spreads the drift over the k links, one `ring:` line is printed first and the chain is
+// fused over the corrected links.  Without it nothing changes.
 // One `fuse:` line, then the fused cloud of the first segment -- one point per track, where align_pairs_demo writes a feature
 // once per pair that sees it -- as a PLY (default fused_cloud.ply).  With adjust_iterations > 0 (default 0: nothing changes) one
 // SfM::adjust_chain over the fused model follows, one `chain adjust:` line per segment is printed and the PLY holds the adjusted
 // points.  Plain C++: needs only the facade headers and libsfm_amd.so.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "sfm.h"
@@ -43,24 +48,25 @@ static void upload(SiftData &data, const std::vector<SiftPoint> &f, const char *
 int main(int argc, char **argv)
 {
     const int count = argc > 1 ? std::atoi(argv[1]) : 0;
-    if (count < 1 || argc < 2 + 2 * count || argc > 4 + 2 * count) {
-        std::fprintf(stderr, "usage: %s k a1.bin .. ak.bin b1.bin .. bk.bin [cloud.ply [adjust_iterations]]   (k >= 1)\n", argv[0]);
+    const bool ring = count >= 1 && argc == 5 + 2 * count && std::string(argv[4 + 2 * count]) == "ring";
+    if (count < 1 || argc < 2 + 2 * count || (argc > 4 + 2 * count && !ring) || (ring && count < 3)) {
+        std::fprintf(stderr, "usage: %s k a1.bin .. ak.bin b1.bin .. bk.bin [cloud.ply [adjust_iterations [ring]]]   (k >= 1; ring: k >= 3)\n", argv[0]);
         return 2;
     }
     const char *ply = argc >= 3 + 2 * count ? argv[2 + 2 * count] : "fused_cloud.ply";
-    const int adjust_iterations = argc == 4 + 2 * count ? std::atoi(argv[3 + 2 * count]) : 0;
+    const int adjust_iterations = argc >= 4 + 2 * count ? std::atoi(argv[3 + 2 * count]) : 0;
     const unsigned w = 720, h = 576;                        // the dino frames
     float K[9] = { 2360.0f, 0, (float)(w / 2.0), 0, 2360, (float)(h / 2.0), 0, 0, 1 };
     float inv_K[9] = { (float)(1.0 / 2360), 0, (float)(-(w / 2.0) / 2360), 0, (float)(1.0 / 2360), (float)(-(h / 2.0) / 2360), 0, 0, 1 };
 
     std::vector<std::vector<SiftPoint>> fa, fb;
     for (int k = 0; k < count; ++k) { fa.push_back(read_sift(argv[2 + k])); fb.push_back(read_sift(argv[2 + count + k])); }
-    for (int k = 0; k + 1 < count; ++k) {                   // a link follows match indices: b_k and a_{k+1} are one view's records
-        const std::vector<SiftPoint> &x = fb[(size_t)k], &y = fa[(size_t)k + 1];
+    for (int k = 0; k + (ring ? 0 : 1) < count; ++k) {      // a link follows match indices: b_k and a_{k+1} are one view's records
+        const std::vector<SiftPoint> &x = fb[(size_t)k], &y = fa[(size_t)(k + 1) % (size_t)count];
         bool same = x.size() == y.size();
         for (size_t j = 0; same && j < x.size(); ++j) same = x[j].xpos == y[j].xpos && x[j].ypos == y[j].ypos;
         if (!same) {
-            std::fprintf(stderr, "%s and %s are not the records of one view (count or positions differ)\n", argv[2 + count + k], argv[3 + k]);
+            std::fprintf(stderr, "%s and %s are not the records of one view (count or positions differ)\n", argv[2 + count + k], argv[2 + (k + 1) % count]);
             return 2;
         }
     }
@@ -82,7 +88,16 @@ int main(int argc, char **argv)
         records.push_back(s1.d_data);
     }
     SfM::refine_pairs(pairs.data(), count);
-    const SfM::FusedModel model = SfM::fuse_chain(pairs.data(), records.data(), count);
+    SfM::ClosedRing closed;
+    if (ring) {
+        static const char *const status[3] = { "closed", "open", "rejected" };
+        closed = SfM::close_ring(pairs.data(), records.data(), count);
+        const sfm_ring_report &rr = closed.report;
+        std::printf("ring: %s, drift s %.6g rot %.6g rad, seam rms %.6g -> %.6g px (link %.6g), %d records\n", status[rr.status],
+                    std::exp((double)rr.drift_log_scale), (double)rr.drift_rotation_rad, (double)rr.seam_rms_open_px, (double)rr.seam_rms_closed_px,
+                    (double)rr.seam_rms_link_px, rr.seam_count);
+    }
+    const SfM::FusedModel model = SfM::fuse_chain(pairs.data(), records.data(), count, 5, 4.0f, ring ? closed.corrected.data() : nullptr);
     std::printf("fuse: %d tracks, %d observations, %d refined, %d kept, %d segments, longest track %d views\n", model.tracks, model.observations,
                 model.refined, model.kept, model.segments, model.longest_track);
 

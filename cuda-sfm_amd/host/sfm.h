@@ -531,8 +531,11 @@ struct FusedModel {
 
 // A chain of `count` refined pairs, pair i + 1's first view being pair i's second, fused into tracks and one point per track
 // (sfm_align_pairs over the count - 1 links, then sfm_fuse_chain): data[i] = the records pairs[i]'s fillXU took.  One wait at
-// the end.
-inline FusedModel fuse_chain(Image_pair *const *pairs, SiftPoint *const *data, int count, int max_iterations = 5, float threshold_px = 4.0f)
+// the end.  corrected_links: null, or 13 x (count - 1) floats the fusion reads in place of the measured links (the first
+// count - 1 of ClosedRing::corrected: the chain of a closed ring); the links are aligned all the same, for their masks and
+// errors, and FusedModel::links stays what the alignment measured.
+inline FusedModel fuse_chain(Image_pair *const *pairs, SiftPoint *const *data, int count, int max_iterations = 5, float threshold_px = 4.0f,
+                             const float *corrected_links = nullptr)
 {
     FusedModel r;
     if (count <= 0) return r;
@@ -564,11 +567,17 @@ inline FusedModel fuse_chain(Image_pair *const *pairs, SiftPoint *const *data, i
         aouts.push_back(o);
     }
     if (nl > 0) SFM_FACADE_CALL(sfm_align_pairs(ha.data(), hb.data(), nl, indices.data(), &ap, aouts.data()));
+    std::unique_ptr<detail::DeviceBlock> given;            // the corrected links: ONE upload, read in place of the aligned ones
+    if (corrected_links && nl > 0) {
+        given.reset(new detail::DeviceBlock(52 * (size_t)nl));
+        SFM_FACADE_CALL(sfm_copy_to_device(ctx, given->p, corrected_links, 52 * (size_t)nl));
+    }
     std::vector<sfm_fuse_pair_in> pin((size_t)count);
     std::vector<sfm_fuse_link_in> lin((size_t)(nl > 0 ? nl : 1));
     for (int i = 0; i < count; ++i) { pin[(size_t)i].pair = pairs[i] ? pairs[i]->handle() : nullptr; pin[(size_t)i].d_points = nullptr; pin[(size_t)i].d_valid = nullptr; pin[(size_t)i].d_pose = nullptr; }
     for (int i = 0; i < nl; ++i) {
-        lin[(size_t)i].d_index = indices[(size_t)i]; lin[(size_t)i].d_sim = aouts[(size_t)i].d_sim; lin[(size_t)i].d_inlier = aouts[(size_t)i].d_inlier;
+        lin[(size_t)i].d_index = indices[(size_t)i]; lin[(size_t)i].d_inlier = aouts[(size_t)i].d_inlier;
+        lin[(size_t)i].d_sim = given ? reinterpret_cast<const float *>(given->p + 52 * (size_t)i) : aouts[(size_t)i].d_sim;
         lin[(size_t)i].d_err = aouts[(size_t)i].d_err; lin[(size_t)i].d_report = aouts[(size_t)i].d_report;
     }
     // the outputs in ONE block, every array at a multiple of 16 bytes
@@ -610,6 +619,65 @@ inline FusedModel fuse_chain(Image_pair *const *pairs, SiftPoint *const *data, i
         SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.flags.data(), o.d_flags, T));
         SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.err.data(), o.d_err, 4 * T));
     }
+    for (size_t i = 0; i < k; ++i) r.frames.push_back(Sim3::from(frames.data() + 13 * i));
+    return r;
+}
+
+// what close_ring returns, in host memory
+struct ClosedRing {
+    std::vector<PairLink> links;        // count: the measured links as align_pairs gives them; link count - 1 closes the ring
+    std::vector<float> corrected;       // 13 x count: the corrected links (s, R, t) as sfm_close_ring rounds them
+    std::vector<Sim3> frames;           // count: the closed frames (the open ones unless report.status is SFM_RING_CLOSED)
+    sfm_ring_report report;
+};
+
+// A ring of `count` (>= 3) refined pairs, pair i + 1 mod count's first view being pair i's second, closed (sfm_align_pairs over
+// all count links, the last one carrying pair count - 1 onto pair 0, then sfm_close_ring): data[i] = the records pairs[i]'s fillXU
+// took.  The first count - 1 corrected links go into fuse_chain.  One wait at the end.
+inline ClosedRing close_ring(Image_pair *const *pairs, SiftPoint *const *data, int count, float threshold_px = 4.0f)
+{
+    ClosedRing r;
+    sfm_ctx *ctx = sfm_facade::context();
+    sfm_align_params ap;
+    sfm_align_default_params(&ap);
+    sfm_ring_params rp;
+    sfm_ring_default_params(&rp);
+    rp.threshold_px = threshold_px;
+    std::vector<sfm_pair *> ha, hb;
+    std::vector<std::unique_ptr<detail::AlignScratch>> scratch;
+    std::vector<const int32_t *> indices;
+    std::vector<sfm_align_out> aouts;
+    std::vector<sfm_ring_link_in> lin;
+    for (int i = 0; i < count; ++i) {
+        Image_pair *b = pairs[(i + 1) % count];
+        ha.push_back(pairs[i] ? pairs[i]->handle() : nullptr);
+        hb.push_back(b ? b->handle() : nullptr);
+        const int n = pairs[i] ? pairs[i]->numPoints() : 0;
+        scratch.emplace_back(new detail::AlignScratch(n));
+        SFM_FACADE_CALL(sfm_align_index_from_matches(ctx, reinterpret_cast<const sfm_sift_point *>(data[i]), n, 0.85f, 0.95f, scratch.back()->index()));
+        indices.push_back(scratch.back()->index());
+        aouts.push_back(scratch.back()->out());
+        sfm_ring_link_in l;
+        l.d_sim = aouts.back().d_sim; l.d_report = aouts.back().d_report;
+        lin.push_back(l);
+    }
+    if (count > 0) SFM_FACADE_CALL(sfm_align_pairs(ha.data(), hb.data(), count, indices.data(), &ap, aouts.data()));
+    const size_t k = (size_t)(count > 0 ? count : 0);
+    detail::DeviceBlock mem(2 * (52 * k + 16) + sizeof(sfm_ring_report) + 16);
+    sfm_ring_out o;
+    o.d_links = reinterpret_cast<float *>(mem.p); o.d_frames = reinterpret_cast<float *>(mem.p + 52 * k + 16);
+    o.d_seam_err = nullptr;
+    o.d_report = reinterpret_cast<sfm_ring_report *>(mem.p + 2 * (52 * k + 16));
+    sfm_fuse_pair_in last;
+    last.pair = count > 0 && pairs[count - 1] ? pairs[count - 1]->handle() : nullptr;
+    last.d_points = nullptr; last.d_valid = nullptr; last.d_pose = nullptr;
+    SFM_FACADE_CALL(sfm_close_ring(ctx, lin.data(), count, &last, &rp, &o));
+    for (int i = 0; i < count; ++i) r.links.push_back(scratch[(size_t)i]->download());      // (the first download waits for everything)
+    std::vector<float> frames(13 * k);
+    r.corrected.resize(13 * k);
+    SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.corrected.data(), o.d_links, 52 * k));
+    SFM_FACADE_CALL(sfm_copy_to_host(ctx, frames.data(), o.d_frames, 52 * k));
+    SFM_FACADE_CALL(sfm_copy_to_host(ctx, &r.report, o.d_report, sizeof(r.report)));
     for (size_t i = 0; i < k; ++i) r.frames.push_back(Sim3::from(frames.data() + 13 * i));
     return r;
 }

@@ -678,6 +678,63 @@ void sfm_adjust_chain_default_params(sfm_adjust_chain_params *p);
 int  sfm_adjust_chain(sfm_ctx *ctx, const sfm_adjust_chain_in *in, int num_pairs, const sfm_adjust_chain_params *p,
                       const sfm_adjust_chain_out *out);                          /* enqueue only */
 
+/* ---- closing a ring of aligned pairs: the drift measured and spread over the links -----------------
+ * Pairs 0 .. k-1 of a ring, pair i = (view i, view i + 1 mod k), and ALL k links: link i carries pair i's frame into pair
+ * (i + 1 mod k)'s, so link k - 1 is the closing one (what sfm_align_pairs gives for a = pair k - 1, b = pair 0).  The open frames
+ * are sfm_fuse_chain's: F_0 = I, F_{i+1} = F_i o L_i^-1 in fp64; the drift D = F_k is the identity for a perfect ring.
+ * status: SFM_RING_OPEN when some link is invalid (sfm_fuse_chain's rule), SFM_RING_REJECTED when all are valid but D's rotation
+ * angle exceeds max_rotation_rad or |ln s_D| exceeds max_log_scale (gates against a wrong closing link; none on t, whose length
+ * follows the gauge), else SFM_RING_CLOSED.
+ * CLOSED: with (sigma, w, t_c) = (ln s, axis-angle, t) of D^-1 and alpha_0 = 0 <= alpha_1 <= ... <= alpha_k = 1 the running sums of
+ * the normalised weights (1 / max(num_inliers_i, 1) from the links' reports, or `weights`), B_i = (exp(alpha_i sigma),
+ * exp(alpha_i [w]x), alpha_i t_c), B_k = D^-1 itself; d_frames holds the closed frames F'_i = B_i o F_i and d_links the corrected
+ * links L'_i = F'_{i+1}^-1 o F'_i, all in fp64 and rounded once.  F'_k = I: the corrected links compose to the identity, and their
+ * first k - 1 go unchanged into sfm_fuse_chain.  OPEN / REJECTED: d_links is the input bit for bit, d_frames is byte for byte what
+ * sfm_fuse_chain writes for the first k - 1 links (an invalid link restarts at the identity); drift_* are 0 when OPEN.
+ * The seam: view 0 is the second view of pair k - 1.  Every usable record of pair k - 1 (the registration's point test) is carried
+ * into pair 0's frame by the measured closing link, by the open frame F_{k-1} and by the closed frame F'_{k-1} (= the open one
+ * unless CLOSED) and held against its own X1 observation through the pair's K under [I|0] (sfm_register_view's inlier test and
+ * error at threshold_px).  seam_count: the records that pass under the measured link; seam_rms_*_px: the rms pixel error over
+ * them under each frame, without the members whose error there is not finite -- seam_lost_* count those.
+ * The call READS the pair and writes only the caller's buffers: no stage, buffer id or getter belongs to it.  No float atomics:
+ * two calls give the same bytes. */
+#define SFM_RING_CLOSED   0
+#define SFM_RING_OPEN     1
+#define SFM_RING_REJECTED 2
+typedef struct sfm_ring_params {
+    float   threshold_px;              /* the seam's inlier test; default 4.0                                         */
+    float   max_rotation_rad;          /* in (0, pi/2]; default 0.35                                                  */
+    float   max_log_scale;             /* > 0; default ln 2                                                           */
+    const float *weights;              /* optional HOST float[k]: finite, >= 0, positive sum; NULL = from the reports */
+    int32_t reserved[4];               /* must be zero (else SFM_E_INVALID)                                           */
+} sfm_ring_params;
+typedef struct sfm_ring_link_in {      /* HOST array, one per link i: pair i -> pair i + 1 mod k; DEVICE, required    */
+    const float *d_sim;                /* first 13 floats of sfm_align_out.d_sim                                      */
+    const sfm_align_report *d_report;
+} sfm_ring_link_in;
+typedef struct sfm_ring_report {
+    int32_t status;                    /* SFM_RING_*                                                                  */
+    int32_t num_links;
+    int32_t first_invalid;             /* the first invalid link, -1 = none                                           */
+    float   drift_log_scale, drift_rotation_rad, drift_t;   /* ln s, rotation angle and |t| of D                      */
+    int32_t seam_count, seam_lost_open, seam_lost_closed;
+    float   seam_rms_link_px, seam_rms_open_px, seam_rms_closed_px;
+} sfm_ring_report;
+typedef struct sfm_ring_out {          /* DEVICE buffers of the caller; all required unless marked                    */
+    float   *d_links;      /* 13 x k: the corrected links                                                             */
+    float   *d_frames;     /* 13 x k: the closed frames (the layout of sfm_fuse_out.d_frames)                         */
+    float   *d_seam_err;   /* 3 x n of pair k - 1, optional: pixel error per record under the link, the open and the
+                              closed frame; +inf where the record is not usable or the point lies behind the camera   */
+    sfm_ring_report *d_report;
+} sfm_ring_out;
+void sfm_ring_default_params(sfm_ring_params *p);
+/* links: HOST array of num_links (3..4096) entries.  last_pair: pair k - 1 with sfm_fuse_chain's overrides (d_pose is not read);
+ * it belongs to ctx and needs points, and the refinement unless d_points is given (SFM_E_STATE).  No output may overlap an input
+ * or another output.  Every check precedes the first enqueue: on SFM_E_INVALID / SFM_E_STATE (the text names links[i] or
+ * last_pair) nothing is written.  The work buffer belongs to the context. */
+int  sfm_close_ring(sfm_ctx *ctx, const sfm_ring_link_in *links, int num_links, const sfm_fuse_pair_in *last_pair,
+                    const sfm_ring_params *p, const sfm_ring_out *out);          /* enqueue only */
+
 /* ---- accessors (the reference keeps these private; needed for parity checks) ------------------ */
 #define SFM_BUF_X0      0   /* float 3 x ld   normalised coords image 1 (ld = sfm_pair_ld)   */
 #define SFM_BUF_X1      1
