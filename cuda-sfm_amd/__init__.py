@@ -54,6 +54,7 @@ REFINE_CONVERGED, REFINE_MAX_ITER, REFINE_DEGENERATE = 0, 1, 2         # sfm_ref
 VP_UNSEEN, VP_NEW, VP_REFINED, VP_NEW_REJECTED, VP_KEPT = range(5)     # sfm_view_points_out.d_flags
 ADJ_VIEW1, ADJ_VIEW2, ADJ_VIEW3 = 1, 2, 4                              # bits of sfm_adjust_out.d_views
 FUSE_REFINED, FUSE_KEPT = 1, 2                                         # sfm_fuse_out.d_flags
+FUSE_SEAM_REFINED, FUSE_SEAM_KEPT = 3, 4                               # the same of a track that crosses a ring's seam (sfm_fuse_ring)
 RING_CLOSED, RING_OPEN, RING_REJECTED = 0, 1, 2                        # sfm_ring_report.status
 
 SIFT_DTYPE = np.dtype([
@@ -85,7 +86,7 @@ EXPORTS = [
     "sfm_align_default_params", "sfm_align_index_from_matches", "sfm_align_pair", "sfm_align_pairs",
     "sfm_fuse_default_params", "sfm_fuse_chain",
     "sfm_adjust_chain_default_params", "sfm_adjust_chain",
-    "sfm_ring_default_params", "sfm_close_ring",
+    "sfm_ring_default_params", "sfm_close_ring", "sfm_fuse_ring_default_params", "sfm_fuse_ring",
 ]
 AB_EXPORTS = ["sfm_ransac_last_phases", "sfm_ransac_last_trace", "sfm_prefilter_probe", "sfm_prefilter_band_probe"]      # include/sfm_amd_ab.h
 if AB:
@@ -259,6 +260,18 @@ class RingOut(C.Structure):
     _fields_ = [("d_links", C.c_void_p), ("d_frames", C.c_void_p), ("d_seam_err", C.c_void_p), ("d_report", C.c_void_p)]
 
 
+class FuseRingParams(C.Structure):
+    """sfm_fuse_ring_params (include/sfm_amd.h)."""
+    _fields_ = [("fuse", FuseParams), ("max_closure_rotation_rad", C.c_float), ("max_closure_log_scale", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+class FuseRingReport(C.Structure):
+    """sfm_fuse_ring_report (include/sfm_amd.h)."""
+    _fields_ = [("status", C.c_int32), ("first_invalid", C.c_int32), ("closure_log_scale", C.c_float), ("closure_rotation_rad", C.c_float),
+                ("closure_t", C.c_float), ("seam_proposals", C.c_int32), ("seam_ineligible", C.c_int32), ("seam_tracks", C.c_int32),
+                ("seam_refined", C.c_int32), ("seam_kept", C.c_int32)]
+
+
 FUSE_COUNTS = ("tracks", "observations", "refined", "kept", "segments", "longest_track")      # sfm_fuse_out.d_counts[0..5]
 
 _vp = C.c_void_p
@@ -363,6 +376,9 @@ _lib.sfm_adjust_chain.argtypes = [_vp, C.POINTER(AdjustChainIn), C.c_int, C.POIN
 _lib.sfm_ring_default_params.argtypes = [C.POINTER(RingParams)]
 _lib.sfm_ring_default_params.restype = None
 _lib.sfm_close_ring.argtypes = [_vp, C.POINTER(RingLinkIn), C.c_int, C.POINTER(FusePairIn), C.POINTER(RingParams), C.POINTER(RingOut)]
+_lib.sfm_fuse_ring_default_params.argtypes = [C.POINTER(FuseRingParams)]
+_lib.sfm_fuse_ring_default_params.restype = None
+_lib.sfm_fuse_ring.argtypes = [_vp, C.POINTER(FusePairIn), C.c_int, C.POINTER(FuseLinkIn), C.POINTER(FuseRingParams), C.POINTER(FuseOut), _vp]
 _lib.sfm_fuse_chain.argtypes = [_vp, C.POINTER(FusePairIn), C.c_int, C.POINTER(FuseLinkIn), C.POINTER(FuseParams), C.POINTER(FuseOut)]
 if AB:
     _lib.sfm_ransac_last_phases.argtypes = [_vp, C.POINTER(C.c_uint64)]
@@ -772,6 +788,69 @@ def _fuse_results(outs, k, N):
     return dict(frames=frames.reshape(k, 13), root=root, cams=cams.reshape(k, 2, 12), track=track, track_offset=off[:T + 1].copy(),
                 obs_cam=ocam[:M].copy(), obs_record=orec[:M].copy(), points=pts.reshape(4, N)[:, :T].copy(), flags=flags[:T].copy(),
                 err=err[:T].copy(), counts={name: int(counts[i]) for i, name in enumerate(FUSE_COUNTS)})
+
+
+_FUSE_RING_FIELDS = {f for f, _ in FuseRingParams._fields_} - {"fuse", "reserved"}
+
+
+def fuse_ring_params(**kw):
+    """sfm_fuse_ring_params with the library's defaults (sfm_fuse_params' own, closure gates 1e-3 rad and 1e-3), fields overridden
+    by kw: the two gates and `reserved` are the ring's, every other name is a FuseParams field (`fuse_reserved`: its reserved)."""
+    p = FuseRingParams()
+    _lib.sfm_fuse_ring_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "reserved":
+            for i, x in enumerate(v):
+                p.reserved[i] = int(x)
+        elif k == "fuse_reserved":
+            for i, x in enumerate(v):
+                p.fuse.reserved[i] = int(x)
+        elif k in _FUSE_RING_FIELDS:
+            setattr(p, k, v)
+        elif k in _FUSE_FIELDS and k != "reserved":
+            setattr(p.fuse, k, v)
+        else:
+            raise TypeError(f"fuse_ring_params: no field {k!r} in sfm_fuse_ring_params")
+    return p
+
+
+def fuse_ring_enqueue(ctx, pairs, links, params, outs, report):
+    """sfm_fuse_ring (enqueue only).  pairs: as fuse_chain_enqueue takes them; links: one (index, sim, inlier, err, report) tuple of
+    device tensors / pointers per link of the ring (len(pairs) of them, the last one from pair k - 1 onto pair 0); outs: device
+    tensors / pointers in the order of sfm_fuse_out (err may be None); report: a device tensor / pointer of
+    sizeof(FuseRingReport) bytes."""
+    k = len(pairs)
+    pin = (FusePairIn * max(k, 1))()
+    for i, x in enumerate(pairs):
+        x = x if isinstance(x, tuple) else (x, None, None, None)
+        pin[i] = FusePairIn(x[0]._h.value if x[0] is not None else None, *[_ptr(t) for t in x[1:]])
+    lin = (FuseLinkIn * max(len(links), 1))(*[FuseLinkIn(*[_ptr(t) for t in x]) for x in links]) if links is not None else None
+    o = FuseOut(*[_ptr(t) for t in outs]) if outs is not None else None
+    _check(_lib.sfm_fuse_ring(ctx._h if ctx is not None else None, pin, k, lin, C.byref(params) if params is not None else None,
+                              C.byref(o) if o is not None else None, _ptr(report)), "sfm_fuse_ring")
+
+
+def fuse_ring(pairs, indices, align_outs, overrides=None, **kw):
+    """A closed ring of aligned pairs fused: fuse_chain over the k pairs with the tracks that cross the seam joined.  pairs: the k
+    ImagePairs (pair i = views i, i + 1 mod k); indices: the device index tensor of every one of the k links; align_outs: per link
+    the device tensors (sim, inlier, err, counts, report), sim normally a row of close_ring's corrected links; overrides as in
+    fuse_chain; kw are fuse_ring_params' names.  Allocates the outputs, waits once and returns fuse_chain's dict + report (a dict
+    of FuseRingReport's fields)."""
+    params = fuse_ring_params(**kw)
+    k = len(pairs)
+    ctx = pairs[0].ctx
+    dev = torch.device("cuda", ctx.device)
+    N = sum(p.num_points for p in pairs)
+    outs = _fuse_buffers(torch, dev, k, N)
+    rep = torch.empty(C.sizeof(FuseRingReport), dtype=torch.uint8, device=dev)
+    pin = [(p,) + tuple(overrides[i]) if overrides is not None and overrides[i] is not None else p for i, p in enumerate(pairs)]
+    links = [(indices[i], a[0], a[1], a[2], a[4]) for i, a in enumerate(align_outs)]
+    fuse_ring_enqueue(ctx, pin, links, params, outs, rep)
+    ctx.synchronize()
+    out = _fuse_results(outs, k, N)
+    r = FuseRingReport.from_buffer_copy(rep.cpu().numpy().tobytes())
+    out["report"] = {f: getattr(r, f) for f, _ in FuseRingReport._fields_}
+    return out
 
 
 _RING_FIELDS = {f for f, _ in RingParams._fields_}

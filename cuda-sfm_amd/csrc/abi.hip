@@ -1485,6 +1485,106 @@ void sfm_fuse_default_params(sfm_fuse_params *p)
     p->initial_lambda = 1e-3f;
 }
 
+// What sfm_fuse_chain and sfm_fuse_ring share behind their argument checks, in two steps that each call keeps in its own order
+// around its link checks.  fuse_check_pairs: every pair present, of this context and listed once (`visits`: the text for a pair
+// listed twice), d_valid only with d_points, at most 2^26 records; handles and total are filled.
+static int fuse_check_pairs(sfm_ctx *ctx, const sfm_fuse_pair_in *pairs, int num_pairs, const char *visits, std::vector<sfm_pair *> &handles,
+                            long long &total)
+{
+    handles.resize((size_t)num_pairs);
+    for (int i = 0; i < num_pairs; ++i) handles[(size_t)i] = pairs[i].pair;
+    int rc = list_entries_present(handles.data(), num_pairs, "pairs[%d]: null pair");
+    if (rc == SFM_OK) rc = list_one_context_each_once(handles.data(), num_pairs, ctx, "pairs[%d]: the pair belongs to another context", "pairs", "",
+                                                      visits);
+    if (rc != SFM_OK) return rc;
+    total = 0;
+    for (int i = 0; i < num_pairs; ++i) {
+        SFM_REQUIRE(pairs[i].d_points || !pairs[i].d_valid, SFM_E_INVALID, "pairs[%d]: d_valid needs d_points", i);
+        total += pairs[i].pair->n;
+    }
+    SFM_REQUIRE(total <= (1ll << 26), SFM_E_INVALID, "%lld records in all: more than 2^26", total);
+    return SFM_OK;
+}
+
+// fuse_ready: no output on an input or on another output (num_links links: the chain's k - 1 or the ring's k; d_report: the ring's
+// further output, or null), the pairs flushed and their stages there, the device set, and the FusePair of every pair with link i in
+// pair i.  Every range is its own owner (its place in `entry`, which keeps the index its name takes): nothing is exempt, so the
+// sweep is the whole check.
+static int fuse_ready(sfm_ctx *ctx, const sfm_fuse_pair_in *pairs, int num_pairs, const sfm_fuse_link_in *links, int num_links,
+                      const sfm_fuse_out *out, const sfm_fuse_ring_report *d_report, std::vector<sfm_pair *> &handles, long long total,
+                      std::vector<FusePair> &fp)
+{
+    {
+        std::vector<BufferRange> r;
+        std::vector<int> entry;
+        r.reserve((size_t)num_pairs * 8 + 12);
+        entry.reserve((size_t)num_pairs * 8 + 12);
+        auto add = [&](const void *ptr, size_t bytes, bool is_out, int who, const char *name) {
+            r.push_back({ ptr, bytes, is_out, (int)entry.size(), name });
+            entry.push_back(who);
+        };
+        const size_t N = (size_t)total, k = (size_t)num_pairs;
+        for (int i = 0; i < num_pairs; ++i) {
+            const size_t n = (size_t)pairs[i].pair->n;
+            add(pairs[i].d_points, n * 16, false, i, "pairs[%d].d_points"); add(pairs[i].d_valid, n, false, i, "pairs[%d].d_valid");
+            add(pairs[i].d_pose, 48, false, i, "pairs[%d].d_pose");
+            if (i < num_links) {
+                add(links[i].d_index, n * 4, false, i, "links[%d].d_index"); add(links[i].d_sim, 52, false, i, "links[%d].d_sim");
+                add(links[i].d_inlier, n, false, i, "links[%d].d_inlier"); add(links[i].d_err, n * 4, false, i, "links[%d].d_err");
+                add(links[i].d_report, sizeof(sfm_align_report), false, i, "links[%d].d_report");
+            }
+        }
+        add(out->d_frames, k * 52, true, -1, "out.d_frames"); add(out->d_root, k * 4, true, -1, "out.d_root");
+        add(out->d_cams, k * 96, true, -1, "out.d_cams"); add(out->d_track, N * 4, true, -1, "out.d_track");
+        add(out->d_track_offset, (N + 1) * 4, true, -1, "out.d_track_offset"); add(out->d_obs_cam, N * 8, true, -1, "out.d_obs_cam");
+        add(out->d_obs_record, N * 8, true, -1, "out.d_obs_record"); add(out->d_points, N * 16, true, -1, "out.d_points");
+        add(out->d_flags, N, true, -1, "out.d_flags"); add(out->d_err, N * 4, true, -1, "out.d_err");
+        add(out->d_counts, 32, true, -1, "out.d_counts"); add(d_report, sizeof(sfm_fuse_ring_report), true, -1, "d_report");
+        if (const RangeConflict c = first_conflict_across_owners(r)) {
+            char a[48], b[48];
+            snprintf(a, sizeof(a), c.a->name, entry[(size_t)c.a->owner]); snprintf(b, sizeof(b), c.b->name, entry[(size_t)c.b->owner]);
+            SFM_REQUIRE(false, SFM_E_INVALID, "%s overlaps %s", c.a->out ? a : b, c.a->out ? b : a);       // the output first
+        }
+    }
+    int rc = list_flush(handles.data(), num_pairs);
+    if (rc == SFM_OK) rc = list_stages(handles.data(), num_pairs, "pairs", "",
+                                       [&](int i) { return (uint32_t)((pairs[i].d_points && pairs[i].d_pose) ? kPoints : kPoints | kRefined); });
+    if (rc != SFM_OK) return rc;
+    SFM_HIP_TRY(hipSetDevice(ctx->device));
+    fp.resize((size_t)num_pairs);
+    for (int i = 0; i < num_pairs; ++i) {
+        const sfm_pair *pr = pairs[i].pair;
+        FusePair &f = fp[(size_t)i];
+        memset(&f, 0, sizeof(f));
+        f.points = pairs[i].d_points ? pairs[i].d_points : pr->d_rpoints;
+        f.valid = pairs[i].d_points ? pairs[i].d_valid : reproj_flags(pr, pr->d_rreproj);
+        f.X0 = pr->d_X[0]; f.X1 = pr->d_X[1]; f.K = pr->d_K;
+        f.pose = pairs[i].d_pose ? pairs[i].d_pose : pr->d_rstate + refine_pose_offset();
+        f.pose_rows = pairs[i].d_pose ? 3 : 4;
+        f.n = pr->n; f.ld = pr->ld;
+        if (i < num_links) {
+            f.index = links[i].d_index; f.sim = links[i].d_sim; f.inlier = links[i].d_inlier; f.err = links[i].d_err; f.report = links[i].d_report;
+        }
+    }
+    return SFM_OK;
+}
+
+// every field of links 0 .. num_links - 1 is there
+static int fuse_links_complete(const sfm_fuse_link_in *links, int num_links)
+{
+    for (int i = 0; i < num_links; ++i)
+        SFM_REQUIRE(links[i].d_index && links[i].d_sim && links[i].d_inlier && links[i].d_err && links[i].d_report, SFM_E_INVALID,
+                    "links[%d]: d_index, d_sim, d_inlier, d_err and d_report are required", i);
+    return SFM_OK;
+}
+
+static int fuse_out_required(const sfm_fuse_out *out)
+{
+    SFM_REQUIRE(out->d_frames && out->d_root && out->d_cams && out->d_track && out->d_track_offset && out->d_obs_cam && out->d_obs_record &&
+                out->d_points && out->d_flags && out->d_counts, SFM_E_INVALID, "every buffer of sfm_fuse_out but d_err is required");
+    return SFM_OK;
+}
+
 int sfm_fuse_chain(sfm_ctx *ctx, const sfm_fuse_pair_in *pairs, int num_pairs, const sfm_fuse_link_in *links, const sfm_fuse_params *p,
                    const sfm_fuse_out *out)
 {
@@ -1497,78 +1597,55 @@ int sfm_fuse_chain(sfm_ctx *ctx, const sfm_fuse_pair_in *pairs, int num_pairs, c
     if (num_pairs == 0) return SFM_OK;
     SFM_REQUIRE(ctx && pairs && out, SFM_E_INVALID, "null context, pair list or out");
     SFM_REQUIRE(links || num_pairs == 1, SFM_E_INVALID, "null link list");
-    SFM_REQUIRE(out->d_frames && out->d_root && out->d_cams && out->d_track && out->d_track_offset && out->d_obs_cam && out->d_obs_record &&
-                out->d_points && out->d_flags && out->d_counts, SFM_E_INVALID, "every buffer of sfm_fuse_out but d_err is required");
-    std::vector<sfm_pair *> handles((size_t)num_pairs);
-    for (int i = 0; i < num_pairs; ++i) handles[(size_t)i] = pairs[i].pair;
-    rc = list_entries_present(handles.data(), num_pairs, "pairs[%d]: null pair");
-    if (rc == SFM_OK) rc = list_one_context_each_once(handles.data(), num_pairs, ctx, "pairs[%d]: the pair belongs to another context", "pairs", "",
-                                                      "a chain visits a pair once");
+    rc = fuse_out_required(out);
     if (rc != SFM_OK) return rc;
+    std::vector<sfm_pair *> handles;
+    std::vector<FusePair> fp;
     long long total = 0;
-    for (int i = 0; i < num_pairs; ++i) {
-        SFM_REQUIRE(pairs[i].d_points || !pairs[i].d_valid, SFM_E_INVALID, "pairs[%d]: d_valid needs d_points", i);
-        total += pairs[i].pair->n;
-    }
-    SFM_REQUIRE(total <= (1ll << 26), SFM_E_INVALID, "%lld records in all: more than 2^26", total);
-    for (int i = 0; i + 1 < num_pairs; ++i)
-        SFM_REQUIRE(links[i].d_index && links[i].d_sim && links[i].d_inlier && links[i].d_err && links[i].d_report, SFM_E_INVALID,
-                    "links[%d]: d_index, d_sim, d_inlier, d_err and d_report are required", i);
-    {
-        // no output on an input or on another output.  Every range is its own owner (its place in `entry`, which keeps the index its
-        // name takes): nothing is exempt, so the sweep is the whole check.
-        std::vector<BufferRange> r;
-        std::vector<int> entry;
-        r.reserve((size_t)num_pairs * 8 + 11);
-        entry.reserve((size_t)num_pairs * 8 + 11);
-        auto add = [&](const void *ptr, size_t bytes, bool is_out, int who, const char *name) {
-            r.push_back({ ptr, bytes, is_out, (int)entry.size(), name });
-            entry.push_back(who);
-        };
-        const size_t N = (size_t)total, k = (size_t)num_pairs;
-        for (int i = 0; i < num_pairs; ++i) {
-            const size_t n = (size_t)pairs[i].pair->n;
-            add(pairs[i].d_points, n * 16, false, i, "pairs[%d].d_points"); add(pairs[i].d_valid, n, false, i, "pairs[%d].d_valid");
-            add(pairs[i].d_pose, 48, false, i, "pairs[%d].d_pose");
-            if (i + 1 < num_pairs) {
-                add(links[i].d_index, n * 4, false, i, "links[%d].d_index"); add(links[i].d_sim, 52, false, i, "links[%d].d_sim");
-                add(links[i].d_inlier, n, false, i, "links[%d].d_inlier"); add(links[i].d_err, n * 4, false, i, "links[%d].d_err");
-                add(links[i].d_report, sizeof(sfm_align_report), false, i, "links[%d].d_report");
-            }
-        }
-        add(out->d_frames, k * 52, true, -1, "out.d_frames"); add(out->d_root, k * 4, true, -1, "out.d_root");
-        add(out->d_cams, k * 96, true, -1, "out.d_cams"); add(out->d_track, N * 4, true, -1, "out.d_track");
-        add(out->d_track_offset, (N + 1) * 4, true, -1, "out.d_track_offset"); add(out->d_obs_cam, N * 8, true, -1, "out.d_obs_cam");
-        add(out->d_obs_record, N * 8, true, -1, "out.d_obs_record"); add(out->d_points, N * 16, true, -1, "out.d_points");
-        add(out->d_flags, N, true, -1, "out.d_flags"); add(out->d_err, N * 4, true, -1, "out.d_err");
-        add(out->d_counts, 32, true, -1, "out.d_counts");
-        if (const RangeConflict c = first_conflict_across_owners(r)) {
-            char a[48], b[48];
-            snprintf(a, sizeof(a), c.a->name, entry[(size_t)c.a->owner]); snprintf(b, sizeof(b), c.b->name, entry[(size_t)c.b->owner]);
-            SFM_REQUIRE(false, SFM_E_INVALID, "%s overlaps %s", c.a->out ? a : b, c.a->out ? b : a);       // the output first
-        }
-    }
-    rc = list_flush(handles.data(), num_pairs);
-    if (rc == SFM_OK) rc = list_stages(handles.data(), num_pairs, "pairs", "",
-                                       [&](int i) { return (uint32_t)((pairs[i].d_points && pairs[i].d_pose) ? kPoints : kPoints | kRefined); });
+    rc = fuse_check_pairs(ctx, pairs, num_pairs, "a chain visits a pair once", handles, total);
+    if (rc == SFM_OK) rc = fuse_links_complete(links, num_pairs - 1);
+    if (rc == SFM_OK) rc = fuse_ready(ctx, pairs, num_pairs, links, num_pairs - 1, out, nullptr, handles, total, fp);
     if (rc != SFM_OK) return rc;
-    SFM_HIP_TRY(hipSetDevice(ctx->device));
-    std::vector<FusePair> fp((size_t)num_pairs);
-    for (int i = 0; i < num_pairs; ++i) {
-        const sfm_pair *pr = pairs[i].pair;
-        FusePair &f = fp[(size_t)i];
-        memset(&f, 0, sizeof(f));
-        f.points = pairs[i].d_points ? pairs[i].d_points : pr->d_rpoints;
-        f.valid = pairs[i].d_points ? pairs[i].d_valid : reproj_flags(pr, pr->d_rreproj);
-        f.X0 = pr->d_X[0]; f.X1 = pr->d_X[1]; f.K = pr->d_K;
-        f.pose = pairs[i].d_pose ? pairs[i].d_pose : pr->d_rstate + refine_pose_offset();
-        f.pose_rows = pairs[i].d_pose ? 3 : 4;
-        f.n = pr->n; f.ld = pr->ld;
-        if (i + 1 < num_pairs) {
-            f.index = links[i].d_index; f.sim = links[i].d_sim; f.inlier = links[i].d_inlier; f.err = links[i].d_err; f.report = links[i].d_report;
-        }
-    }
     return launch_fuse_chain(ctx, fp.data(), num_pairs, *p, *out);                           // reads the pairs: no stage changes
+}
+
+// ---- the same fusion over a closed ring, the seam joined (fuse_ring.hip) ---------------------------
+void sfm_fuse_ring_default_params(sfm_fuse_ring_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    sfm_fuse_default_params(&p->fuse);
+    p->max_closure_rotation_rad = 1e-3f;
+    p->max_closure_log_scale = 1e-3f;
+}
+
+int sfm_fuse_ring(sfm_ctx *ctx, const sfm_fuse_pair_in *pairs, int num_pairs, const sfm_fuse_link_in *links, const sfm_fuse_ring_params *p,
+                  const sfm_fuse_out *out, sfm_fuse_ring_report *d_report)
+{
+    // sfm_fuse_chain's contract: the checks that need no device first (here all k links before the pairs), all of them before
+    // anything is enqueued
+    SFM_REQUIRE(p, SFM_E_INVALID, "null params");
+    SFM_REQUIRE(num_pairs >= 3 && num_pairs <= 4096, SFM_E_INVALID, "num_pairs %d outside 3..4096", num_pairs);
+    SFM_REQUIRE(ctx && pairs && links && out && d_report, SFM_E_INVALID, "null context, pair list, link list, out or d_report");
+    int rc = fuse_out_required(out);
+    if (rc == SFM_OK) rc = fuse_links_complete(links, num_pairs);
+    if (rc != SFM_OK) return rc;
+    SFM_REQUIRE(p->reserved[0] == 0 && p->reserved[1] == 0 && p->reserved[2] == 0 && p->reserved[3] == 0, SFM_E_INVALID,
+                "sfm_fuse_ring_params.reserved[] must be zero");
+    SFM_REQUIRE(p->max_closure_rotation_rad > 0.0f && p->max_closure_rotation_rad <= 1.57079637f, SFM_E_INVALID,
+                "max_closure_rotation_rad must lie in (0, pi/2]");
+    SFM_REQUIRE(isfinite(p->max_closure_log_scale) && p->max_closure_log_scale > 0.0f, SFM_E_INVALID,
+                "max_closure_log_scale must be finite and > 0");
+    rc = check_lm_params(p->fuse, "sfm_fuse_params", 50);
+    if (rc != SFM_OK) return rc;
+    SFM_REQUIRE(isfinite(p->fuse.threshold_px) && p->fuse.threshold_px > 0.0f, SFM_E_INVALID, "threshold_px must be finite and > 0");
+    std::vector<sfm_pair *> handles;
+    std::vector<FusePair> fp;
+    long long total = 0;
+    rc = fuse_check_pairs(ctx, pairs, num_pairs, "a ring visits a pair once", handles, total);
+    if (rc == SFM_OK) rc = fuse_ready(ctx, pairs, num_pairs, links, num_pairs, out, d_report, handles, total, fp);
+    if (rc != SFM_OK) return rc;
+    return launch_fuse_ring(ctx, fp.data(), num_pairs, *p, *out, d_report);                  // reads the pairs: no stage changes
 }
 
 // ---- one bundle adjustment over a fused chain (chain_adjust.hip) -----------------------------------

@@ -421,6 +421,9 @@ size_t align_hyp_bytes(size_t num_hypotheses);                    // bytes of pa
 // caller (offset and block0 are filled in here)
 struct FusePair;
 int launch_fuse_chain(sfm_ctx *ctx, const FusePair *pairs, int num_pairs, const sfm_fuse_params &p, const sfm_fuse_out &out);
+// fuse_ring.hip: the same over a closed ring of num_pairs pairs and as many links (pair k - 1 holds the closing one)
+int launch_fuse_ring(sfm_ctx *ctx, const FusePair *pairs, int num_pairs, const sfm_fuse_ring_params &p, const sfm_fuse_out &out,
+                     sfm_fuse_ring_report *d_report);
 
 // chain_adjust.hip: one bundle adjustment over a fused chain; pairs: HOST array (X0, X1, K, n, ld resolved by the caller)
 int launch_adjust_chain(sfm_ctx *ctx, const FusePair *pairs, int num_pairs, const sfm_adjust_chain_in &in, const sfm_adjust_chain_params &p,

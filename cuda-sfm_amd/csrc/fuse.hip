@@ -25,54 +25,9 @@
 //   fuse_points_kernel   one lane per track: the mean start, the LM over the track's list (walked again for every trial cost:
 //                        no per-lane array sized by the number of views), the acceptance test; a wavefront that keeps start
 //                        points moves their number from REFINED to KEPT by two integer atomics.
-#include "common.hpp"
-#include "device_math.hpp"
-#include "block_ops.hpp"
-#include "fuse_math.hpp"
+#include "fuse_device.hpp"
 
 namespace sfm {
-
-constexpr int kFuseWaves = kFuseBlock / 64;
-constexpr int kFuseScanThreads = 256;     // block counts per round of the scan kernel
-constexpr int kFuseFrameThreads = 256;    // links per round of the frames kernel (40 KiB of LDS)
-
-struct FuseArgs {
-    const FusePair *pairs;
-    int k, N, blocks;                     // pairs, nodes, node blocks
-    sfm_fuse_params p;
-    unsigned long long *keys;             // N: the winning key of every node's incoming edges
-    int *succ;                            // N: the node behind this one on its path, or -1
-    int *len;                             // N: pairs on the path that starts here (heads only)
-    uint8_t *kind;                        // N: 0 dead, 1 live, 2 head
-    unsigned long long *blk;              // blocks: (observations << 32) | heads per block, then its exclusive scan
-    int *blkmax;                          // blocks: the longest track (views) that starts in the block
-    sfm_fuse_out out;
-};
-
-constexpr uint8_t kFuseDead = 0, kFuseLive = 1, kFuseHead = 2;
-
-// the pair of node block b: the last pair whose block0 is <= b (pairs without records own no block)
-__device__ __forceinline__ int fuse_locate(const FusePair *__restrict__ pairs, int k, int b)
-{
-    int lo = 0, hi = k - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (pairs[mid].block0 <= b) lo = mid; else hi = mid - 1;
-    }
-    return __builtin_amdgcn_readfirstlane(lo);
-}
-
-// pair i of the chain where i is the same in every lane of the wavefront: its pointers are global ones in scalar registers.  Where
-// every lane has a pair of its own (the frames kernel's lanes, a track's views) the struct is read as it is.
-__device__ __forceinline__ FusePair load_pair(const FusePair *__restrict__ pairs, int i)
-{
-    FusePair p = pairs[i];
-    p.points = global_ptr(p.points); p.valid = global_ptr(p.valid); p.X0 = global_ptr(p.X0); p.X1 = global_ptr(p.X1);
-    p.K = global_ptr(p.K); p.pose = global_ptr(p.pose);
-    p.index = global_ptr(p.index); p.sim = global_ptr(p.sim); p.inlier = global_ptr(p.inlier); p.err = global_ptr(p.err);
-    p.report = global_ptr(p.report);
-    return p;
-}
 
 __global__ __launch_bounds__(kFuseFrameThreads)
 void fuse_frames_kernel(FuseArgs a)
@@ -315,20 +270,8 @@ void fuse_points_kernel(FuseArgs a)
     }
 }
 
-// the context's work buffer for N nodes in `blocks` node blocks: the arrays of `a` inside it; returns its size in bytes
-static size_t fuse_work_layout(void *buffer, size_t N, size_t blocks, FuseArgs &a)
-{
-    Carver w(buffer);
-    a.keys = w.take<unsigned long long>(N, 16);
-    a.blk = w.take<unsigned long long>(blocks, 8);
-    a.succ = w.take<int>(N, 4);
-    a.len = w.take<int>(N, 4);
-    a.blkmax = w.take<int>(blocks, 4);
-    a.kind = w.take<uint8_t>(N);
-    return w.used;
-}
-
-int launch_fuse_chain(sfm_ctx *ctx, const FusePair *h_pairs, int num_pairs, const sfm_fuse_params &p, const sfm_fuse_out &out)
+int fuse_prepare(sfm_ctx *ctx, const FusePair *h_pairs, int num_pairs, const sfm_fuse_params &p, const sfm_fuse_out &out, FuseArgs &a,
+                 size_t seam, int **seam_head)
 {
     hipStream_t st = ctx->stream;
     JobArray &ja = ctx->fuse_jobs;
@@ -341,37 +284,57 @@ int launch_fuse_chain(sfm_ctx *ctx, const FusePair *h_pairs, int num_pairs, cons
         jobs[i].offset = N; jobs[i].block0 = blocks;
         N += h_pairs[i].n; blocks += fuse_blocks(h_pairs[i].n);
     }
-    FuseArgs a;
     a.pairs = static_cast<const FusePair *>(ja.dev);
     a.k = num_pairs; a.N = N; a.blocks = blocks;
     a.p = p;
     a.out = out;
-    const size_t need = fuse_work_layout(nullptr, (size_t)N, (size_t)blocks, a);
+    const size_t need = fuse_work_layout(nullptr, (size_t)N, (size_t)blocks, a, seam, seam_head);
     rc = grow(&ctx->fuse_ws, &ctx->fuse_ws_bytes, need, st);
     if (rc != SFM_OK) return rc;
-    fuse_work_layout(ctx->fuse_ws, (size_t)N, (size_t)blocks, a);
-    rc = job_array_upload(ja, (size_t)num_pairs, sizeof(FusePair), st);
-    if (rc != SFM_OK) return rc;
+    fuse_work_layout(ctx->fuse_ws, (size_t)N, (size_t)blocks, a, seam, seam_head);
+    return job_array_upload(ja, (size_t)num_pairs, sizeof(FusePair), st);
+}
+
+int fuse_enqueue_front(hipStream_t st, const FuseArgs &a)
+{
     hipLaunchKernelGGL(fuse_frames_kernel, dim3(1), dim3(kFuseFrameThreads), 0, st, a);
     SFM_HIP_TRY(hipGetLastError());
-    if (blocks == 0) {                                    // no records anywhere: no tracks
+    if (a.blocks == 0) return SFM_OK;                     // no records anywhere
+    SFM_HIP_TRY(hipMemsetAsync(a.keys, 0xFF, (size_t)a.N * sizeof(unsigned long long), st));
+    if (a.k > 1) {
+        hipLaunchKernelGGL(fuse_edges_kernel, dim3(a.blocks), dim3(kFuseBlock), 0, st, a);
+        SFM_HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(fuse_links_kernel, dim3(a.blocks), dim3(kFuseBlock), 0, st, a);
+    SFM_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(fuse_count_kernel, dim3(a.blocks), dim3(kFuseBlock), 0, st, a);
+    SFM_HIP_TRY(hipGetLastError());
+    return SFM_OK;
+}
+
+int fuse_enqueue_scan(hipStream_t st, const FuseArgs &a)
+{
+    hipLaunchKernelGGL(fuse_scan_kernel, dim3(1), dim3(kFuseScanThreads), 0, st, a);
+    SFM_HIP_TRY(hipGetLastError());
+    return SFM_OK;
+}
+
+int launch_fuse_chain(sfm_ctx *ctx, const FusePair *h_pairs, int num_pairs, const sfm_fuse_params &p, const sfm_fuse_out &out)
+{
+    hipStream_t st = ctx->stream;
+    FuseArgs a;
+    int rc = fuse_prepare(ctx, h_pairs, num_pairs, p, out, a);
+    if (rc == SFM_OK) rc = fuse_enqueue_front(st, a);
+    if (rc != SFM_OK) return rc;
+    if (a.blocks == 0) {                                  // no records anywhere: no tracks
         SFM_HIP_TRY(hipMemsetAsync(out.d_track_offset, 0, sizeof(int32_t), st));
         return SFM_OK;
     }
-    SFM_HIP_TRY(hipMemsetAsync(a.keys, 0xFF, (size_t)N * sizeof(unsigned long long), st));
-    if (num_pairs > 1) {
-        hipLaunchKernelGGL(fuse_edges_kernel, dim3(blocks), dim3(kFuseBlock), 0, st, a);
-        SFM_HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(fuse_links_kernel, dim3(blocks), dim3(kFuseBlock), 0, st, a);
+    rc = fuse_enqueue_scan(st, a);
+    if (rc != SFM_OK) return rc;
+    hipLaunchKernelGGL(fuse_fill_kernel, dim3(a.blocks), dim3(kFuseBlock), 0, st, a);
     SFM_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(fuse_count_kernel, dim3(blocks), dim3(kFuseBlock), 0, st, a);
-    SFM_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(fuse_scan_kernel, dim3(1), dim3(kFuseScanThreads), 0, st, a);
-    SFM_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(fuse_fill_kernel, dim3(blocks), dim3(kFuseBlock), 0, st, a);
-    SFM_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(fuse_points_kernel, dim3((N + kFuseBlock - 1) / kFuseBlock), dim3(kFuseBlock), 0, st, a);
+    hipLaunchKernelGGL(fuse_points_kernel, dim3((a.N + kFuseBlock - 1) / kFuseBlock), dim3(kFuseBlock), 0, st, a);
     SFM_HIP_TRY(hipGetLastError());
     return SFM_OK;
 }

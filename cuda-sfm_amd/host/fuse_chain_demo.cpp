@@ -3,11 +3,13 @@
 //   per pair: features -> MatchSiftData -> SfM::Image_pair -> fillXU -> estimateE; ONE refine_pairs over all of them; ONE
 //   fuse_chain over the chain (pair i -> pair i + 1).
 // The arguments are align_pairs_demo's:
-//     fuse_chain_demo <k> <a1.bin> .. <ak.bin> <b1.bin> .. <bk.bin> [cloud.ply [adjust_iterations [ring]]]
+//     fuse_chain_demo <k> <a1.bin> .. <ak.bin> <b1.bin> .. <bk.bin> [cloud.ply [adjust_iterations [ring | loop]]]
 // a_i / b_i: files of raw SiftPoint records of pair i's first / second view; a_{i+1} must hold the records of b_i's view.
 // With the word `ring` behind adjust_iterations the pairs are a ring (k >= 3, b_k holds the records of a_1's view): pair k is also
 // aligned onto pair 1, SfM::close_ring spreads the drift over the k links, one `ring:` line is printed first and the chain is
-// fused over the corrected links.  Without it nothing changes.
+// fused over the corrected links.  Without it nothing changes.  With the word `loop` in its place the ring is closed in the same
+// way and then fused as a RING by SfM::fuse_ring over all k corrected links: the tracks that cross the seam are joined, and one
+// `seam:` line follows the `fuse:` line (status, closure, proposals, seam tracks refined / kept).
 // One `fuse:` line, then the fused cloud of the first segment -- one point per track, where align_pairs_demo writes a feature
 // once per pair that sees it -- as a PLY (default fused_cloud.ply).  With adjust_iterations > 0 (default 0: nothing changes) one
 // SfM::adjust_chain over the fused model follows, one `chain adjust:` line per segment is printed and the PLY holds the adjusted
@@ -48,9 +50,10 @@ static void upload(SiftData &data, const std::vector<SiftPoint> &f, const char *
 int main(int argc, char **argv)
 {
     const int count = argc > 1 ? std::atoi(argv[1]) : 0;
-    const bool ring = count >= 1 && argc == 5 + 2 * count && std::string(argv[4 + 2 * count]) == "ring";
+    const bool loop = count >= 1 && argc == 5 + 2 * count && std::string(argv[4 + 2 * count]) == "loop";
+    const bool ring = loop || (count >= 1 && argc == 5 + 2 * count && std::string(argv[4 + 2 * count]) == "ring");
     if (count < 1 || argc < 2 + 2 * count || (argc > 4 + 2 * count && !ring) || (ring && count < 3)) {
-        std::fprintf(stderr, "usage: %s k a1.bin .. ak.bin b1.bin .. bk.bin [cloud.ply [adjust_iterations [ring]]]   (k >= 1; ring: k >= 3)\n", argv[0]);
+        std::fprintf(stderr, "usage: %s k a1.bin .. ak.bin b1.bin .. bk.bin [cloud.ply [adjust_iterations [ring | loop]]]   (k >= 1; ring, loop: k >= 3)\n", argv[0]);
         return 2;
     }
     const char *ply = argc >= 3 + 2 * count ? argv[2 + 2 * count] : "fused_cloud.ply";
@@ -97,9 +100,18 @@ int main(int argc, char **argv)
                     std::exp((double)rr.drift_log_scale), (double)rr.drift_rotation_rad, (double)rr.seam_rms_open_px, (double)rr.seam_rms_closed_px,
                     (double)rr.seam_rms_link_px, rr.seam_count);
     }
-    const SfM::FusedModel model = SfM::fuse_chain(pairs.data(), records.data(), count, 5, 4.0f, ring ? closed.corrected.data() : nullptr);
+    SfM::FusedRing fused;
+    if (loop) fused = SfM::fuse_ring(pairs.data(), records.data(), count, closed.corrected.data());
+    const SfM::FusedModel model = loop ? fused.model : SfM::fuse_chain(pairs.data(), records.data(), count, 5, 4.0f, ring ? closed.corrected.data() : nullptr);
     std::printf("fuse: %d tracks, %d observations, %d refined, %d kept, %d segments, longest track %d views\n", model.tracks, model.observations,
                 model.refined, model.kept, model.segments, model.longest_track);
+    if (loop) {
+        static const char *const status[3] = { "closed", "open", "rejected" };
+        const sfm_fuse_ring_report &fr = fused.report;
+        std::printf("seam: %s, closure s %.6g rot %.6g rad t %.6g, %d proposals, %d ineligible, %d seam tracks, %d refined, %d kept\n", status[fr.status],
+                    std::exp((double)fr.closure_log_scale), (double)fr.closure_rotation_rad, (double)fr.closure_t, fr.seam_proposals, fr.seam_ineligible,
+                    fr.seam_tracks, fr.seam_refined, fr.seam_kept);
+    }
 
     const int T = model.tracks;
     std::vector<float> points = model.points;

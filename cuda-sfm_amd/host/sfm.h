@@ -16,6 +16,7 @@
 #define SFM_AMD_SFM_H
 
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <vector>
 
@@ -524,18 +525,16 @@ struct FusedModel {
     std::vector<int32_t> obs_cam;       // M: 2 * pair + (0 | 1)
     std::vector<int32_t> obs_record;    // M: the record of that pair
     std::vector<float> points;          // 4 x T (leading dimension T): one point per track in its segment's root frame
-    std::vector<uint8_t> flags;         // T: SFM_FUSE_REFINED / SFM_FUSE_KEPT
+    std::vector<uint8_t> flags;         // T: SFM_FUSE_REFINED / SFM_FUSE_KEPT (fuse_ring: also SFM_FUSE_SEAM_*)
     std::vector<float> err;             // T: largest pixel error over the track's views
     int tracks = 0, observations = 0, refined = 0, kept = 0, segments = 0, longest_track = 0;
 };
 
-// A chain of `count` refined pairs, pair i + 1's first view being pair i's second, fused into tracks and one point per track
-// (sfm_align_pairs over the count - 1 links, then sfm_fuse_chain): data[i] = the records pairs[i]'s fillXU took.  One wait at
-// the end.  corrected_links: null, or 13 x (count - 1) floats the fusion reads in place of the measured links (the first
-// count - 1 of ClosedRing::corrected: the chain of a closed ring); the links are aligned all the same, for their masks and
-// errors, and FusedModel::links stays what the alignment measured.
-inline FusedModel fuse_chain(Image_pair *const *pairs, SiftPoint *const *data, int count, int max_iterations = 5, float threshold_px = 4.0f,
-                             const float *corrected_links = nullptr)
+namespace detail {
+// fuse_chain (report == null: count - 1 links) and fuse_ring (report given: count links, link count - 1 onto pair 0) in one body;
+// corrected_links: null, or 13 floats per link
+inline FusedModel fuse_links(Image_pair *const *pairs, SiftPoint *const *data, int count, int max_iterations, float threshold_px,
+                             const float *corrected_links, sfm_fuse_ring_report *report)
 {
     FusedModel r;
     if (count <= 0) return r;
@@ -546,7 +545,7 @@ inline FusedModel fuse_chain(Image_pair *const *pairs, SiftPoint *const *data, i
     sfm_fuse_default_params(&fp);
     fp.max_iterations = max_iterations;
     fp.threshold_px = threshold_px;
-    const int nl = count - 1;
+    const int nl = report ? count : count - 1;
     size_t N = 0;
     for (int i = 0; i < count; ++i) N += pairs[i] ? (size_t)pairs[i]->numPoints() : 0;
     std::vector<sfm_pair *> ha, hb;
@@ -555,8 +554,9 @@ inline FusedModel fuse_chain(Image_pair *const *pairs, SiftPoint *const *data, i
     std::vector<const int32_t *> indices;
     std::vector<sfm_align_out> aouts;
     for (int i = 0; i < nl; ++i) {
+        Image_pair *b = pairs[(i + 1) % count];
         ha.push_back(pairs[i] ? pairs[i]->handle() : nullptr);
-        hb.push_back(pairs[i + 1] ? pairs[i + 1]->handle() : nullptr);
+        hb.push_back(b ? b->handle() : nullptr);
         const int n = pairs[i] ? pairs[i]->numPoints() : 0;
         scratch.emplace_back(new detail::AlignScratch(n));
         errs.emplace_back(new detail::DeviceBlock(4 * (size_t)n + 16));
@@ -595,7 +595,14 @@ inline FusedModel fuse_chain(Image_pair *const *pairs, SiftPoint *const *data, i
     o.d_obs_record = reinterpret_cast<int32_t *>(mem.p + at[6]); o.d_points = reinterpret_cast<float *>(mem.p + at[7]);
     o.d_flags = reinterpret_cast<uint8_t *>(mem.p + at[8]); o.d_err = reinterpret_cast<float *>(mem.p + at[9]);
     o.d_counts = reinterpret_cast<int32_t *>(mem.p + at[10]);
-    SFM_FACADE_CALL(sfm_fuse_chain(ctx, pin.data(), count, lin.data(), &fp, &o));
+    std::unique_ptr<detail::DeviceBlock> rep;              // the ring's report: allocated for fuse_ring alone
+    if (report) {
+        sfm_fuse_ring_params rp;
+        sfm_fuse_ring_default_params(&rp);
+        rp.fuse = fp;
+        rep.reset(new detail::DeviceBlock(sizeof(sfm_fuse_ring_report) + 16));
+        SFM_FACADE_CALL(sfm_fuse_ring(ctx, pin.data(), count, lin.data(), &rp, &o, reinterpret_cast<sfm_fuse_ring_report *>(rep->p)));
+    } else SFM_FACADE_CALL(sfm_fuse_chain(ctx, pin.data(), count, lin.data(), &fp, &o));
     for (int i = 0; i < nl; ++i) r.links.push_back(scratch[(size_t)i]->download());        // (the first download waits for everything)
     int32_t counts[8];
     SFM_FACADE_CALL(sfm_copy_to_host(ctx, counts, o.d_counts, sizeof(counts)));
@@ -620,6 +627,38 @@ inline FusedModel fuse_chain(Image_pair *const *pairs, SiftPoint *const *data, i
         SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.err.data(), o.d_err, 4 * T));
     }
     for (size_t i = 0; i < k; ++i) r.frames.push_back(Sim3::from(frames.data() + 13 * i));
+    if (report) SFM_FACADE_CALL(sfm_copy_to_host(ctx, report, rep->p, sizeof(*report)));
+    return r;
+}
+} // namespace detail
+
+// A chain of `count` refined pairs, pair i + 1's first view being pair i's second, fused into tracks and one point per track
+// (sfm_align_pairs over the count - 1 links, then sfm_fuse_chain): data[i] = the records pairs[i]'s fillXU took.  One wait at
+// the end.  corrected_links: null, or 13 x (count - 1) floats the fusion reads in place of the measured links (the first
+// count - 1 of ClosedRing::corrected: the chain of a closed ring); the links are aligned all the same, for their masks and
+// errors, and FusedModel::links stays what the alignment measured.
+inline FusedModel fuse_chain(Image_pair *const *pairs, SiftPoint *const *data, int count, int max_iterations = 5, float threshold_px = 4.0f,
+                             const float *corrected_links = nullptr)
+{
+    return detail::fuse_links(pairs, data, count, max_iterations, threshold_px, corrected_links, nullptr);
+}
+
+// what fuse_ring returns: the model (links: all count of them; flags: also SFM_FUSE_SEAM_REFINED / SFM_FUSE_SEAM_KEPT for the tracks
+// that cross the seam, which adjust_chain leaves alone) and the call's report
+struct FusedRing {
+    FusedModel model;
+    sfm_fuse_ring_report report;
+};
+
+// A RING of `count` (>= 3) refined pairs fused (sfm_align_pairs over all count links, then sfm_fuse_ring): fuse_chain with the
+// tracks that cross the seam joined.  corrected_links: 13 x count floats, ClosedRing::corrected -- the measured links of a real
+// ring do not pass the call's closure gates (report.status is then SFM_RING_REJECTED and the model is fuse_chain's).
+inline FusedRing fuse_ring(Image_pair *const *pairs, SiftPoint *const *data, int count, const float *corrected_links, int max_iterations = 5,
+                           float threshold_px = 4.0f)
+{
+    FusedRing r;
+    memset(&r.report, 0, sizeof(r.report));
+    r.model = detail::fuse_links(pairs, data, count, max_iterations, threshold_px, corrected_links, &r.report);
     return r;
 }
 

@@ -627,7 +627,8 @@ int  sfm_fuse_chain(sfm_ctx *ctx, const sfm_fuse_pair_in *pairs, int num_pairs, 
  * otherwise (slot 2p of d_cams is not read for such a pair): one camera per view.  Per segment the root pair's camera moves with
  * sfm_refine_two_view's 5 degrees of freedom (t on the unit sphere, the start t normalised), every other camera with
  * sfm_register_view's 6.  Segments are independent Levenberg-Marquardt problems with a report each.
- * A track is used when its flag is SFM_FUSE_REFINED, it has at most max_track_views views, its point is finite and lies in front
+ * A track is used when its flag EQUALS SFM_FUSE_REFINED (a ring's seam tracks, SFM_FUSE_SEAM_*, are therefore not: their views
+ * are not consecutive), it has at most max_track_views views, its point is finite and lies in front
  * of every one of its views under the start cameras; an unused track returns its input column.  A segment whose root camera
  * has fewer than 16 used observations, or any other camera fewer than 6, is SFM_REFINE_DEGENERATE (not an error): its cameras
  * (both input slots) and its tracks' columns are returned as they came in.
@@ -734,6 +735,56 @@ void sfm_ring_default_params(sfm_ring_params *p);
  * last_pair) nothing is written.  The work buffer belongs to the context. */
 int  sfm_close_ring(sfm_ctx *ctx, const sfm_ring_link_in *links, int num_links, const sfm_fuse_pair_in *last_pair,
                     const sfm_ring_params *p, const sfm_ring_out *out);          /* enqueue only */
+
+/* ---- fusing a closed ring: sfm_fuse_chain over k pairs and k links, the seam joined ---------------
+ * Pairs 0 .. k-1 of a ring, pair i = (view i, view i + 1 mod k), and ALL k links in sfm_fuse_link_in form: link k - 1 is what
+ * sfm_align_pairs took and gave for a = pair k - 1, b = pair 0; d_sim normally points into sfm_ring_out.d_links.
+ * The chain part is sfm_fuse_chain's over the k pairs and the first k - 1 links: d_frames, d_root and d_cams are byte for byte
+ * what it writes, and its paths are the CHAIN TRACKS.  status: SFM_RING_OPEN when one of the k links is invalid (first_invalid
+ * names it); else D = the stored fp32 frame of pair k - 1 composed with the inverse of link k - 1 in fp64, and SFM_RING_REJECTED
+ * when D's rotation angle exceeds max_closure_rotation_rad or |ln s_D| exceeds max_closure_log_scale (no gate on t, whose length
+ * follows the gauge), else SFM_RING_CLOSED.  closure_*: ln s, the angle and |t| of D, zeros when OPEN.  Not CLOSED: every buffer
+ * of sfm_fuse_out ends byte for byte as sfm_fuse_chain leaves it; only the report differs.
+ * CLOSED, the seam: record j of pair k - 1 proposes to join node (0, m), m = d_index[j] of link k - 1, under sfm_fuse_chain's
+ * edge test.  With A the chain track that ends in (k - 1, j), h_A its head's pair, and B the chain track headed by (0, m) over
+ * len(B) pairs, the proposal is ELIGIBLE when len(B) < h_A: the joined track then sees every view at most once (views h_A ..
+ * k - 1, view 0 through pair 0's X0, views 1 .. len(B)).  Eligibility comes before the contest: among the eligible proposers of
+ * one target the smallest d_err wins, then the lowest record; an ineligible one never blocks an eligible one.  The winner's
+ * track goes on into B: (0, m) is a head no more, B's nodes take A's track number, the joined track has len(A) + len(B) pairs and
+ * one observation more: the X0 column of each record in path order, then the X1 column of B's last record (A's own slot-1
+ * observation of view 0 gives way to pair 0's slot 0).  It follows that a feature followed through all k pairs back to its own
+ * record (A = B, h_A = 0) stays one chain track with view 0 at both ends; a track crosses the seam at most once; no track has
+ * more than k pairs; no walk can cycle; tracks stay numbered by their head (pair, then record).
+ * Points and flags are sfm_fuse_chain's, but a track that crosses the seam (its first observation's pair is larger than its
+ * last's) is flagged SFM_FUSE_SEAM_REFINED / SFM_FUSE_SEAM_KEPT; d_counts[2] / [3] count 1 + 3 and 2 + 4.  sfm_adjust_chain uses
+ * a track only when its flag EQUALS SFM_FUSE_REFINED, so seam tracks stay out of its banded system (whose views must be
+ * consecutive) and come back as they went in: the ring's table may be handed to it as it is.
+ * The call READS the pairs and writes only the caller's buffers: no stage, buffer id or getter belongs to it.  Integer atomics
+ * only: two calls give the same bytes. */
+#define SFM_FUSE_SEAM_REFINED 3   /* SFM_FUSE_REFINED of a track that crosses the seam of a ring                     */
+#define SFM_FUSE_SEAM_KEPT    4   /* SFM_FUSE_KEPT of such a track                                                   */
+typedef struct sfm_fuse_ring_params {
+    sfm_fuse_params fuse;
+    float   max_closure_rotation_rad;  /* in (0, pi/2]; default 1e-3                                                  */
+    float   max_closure_log_scale;     /* > 0; default 1e-3                                                           */
+    int32_t reserved[4];               /* must be zero (else SFM_E_INVALID)                                           */
+} sfm_fuse_ring_params;
+typedef struct sfm_fuse_ring_report {
+    int32_t status, first_invalid;     /* SFM_RING_*; the first invalid link, -1 = none                               */
+    float   closure_log_scale, closure_rotation_rad, closure_t;     /* ln s, rotation angle and |t| of D              */
+    int32_t seam_proposals;            /* records of pair k - 1 that pass the edge test                               */
+    int32_t seam_ineligible;           /* of them: len(B) >= h_A                                                      */
+    int32_t seam_tracks;               /* joins = tracks that cross the seam                                          */
+    int32_t seam_refined, seam_kept;   /* of them by flag                                                             */
+} sfm_fuse_ring_report;
+void sfm_fuse_ring_default_params(sfm_fuse_ring_params *p);
+/* pairs: HOST array of num_pairs (3..4096) entries, N at most 2^26; links: HOST array of num_pairs entries, every field
+ * required; d_report: DEVICE, required.  The contract is sfm_fuse_chain's: every pair belongs to ctx and is listed once; each
+ * needs points, and the refinement unless both d_points and d_pose are given (SFM_E_STATE).  No output (d_report included) may
+ * overlap an input or another output.  Every check precedes the first enqueue: on SFM_E_INVALID / SFM_E_STATE (the text names
+ * pairs[i] or links[i]) nothing is written.  The work buffers belong to the context. */
+int  sfm_fuse_ring(sfm_ctx *ctx, const sfm_fuse_pair_in *pairs, int num_pairs, const sfm_fuse_link_in *links,
+                   const sfm_fuse_ring_params *p, const sfm_fuse_out *out, sfm_fuse_ring_report *d_report);   /* enqueue only */
 
 /* ---- accessors (the reference keeps these private; needed for parity checks) ------------------ */
 #define SFM_BUF_X0      0   /* float 3 x ld   normalised coords image 1 (ld = sfm_pair_ld)   */
