@@ -345,6 +345,7 @@ int launch_permutation_indices(sfm_ctx *ctx, int n, uint32_t seed, int32_t *d_in
 bool prefilter_usable(const sfm_pair *pair, const sfm_ransac_params &p, uint32_t count);
 int prefilter_pick_rule(sfm_pair *pair, const sfm_ransac_params &p, uint32_t count);   // the rule of this launch (kPfRuleBandTile / kPfRuleBandPack; lab bench: any), kept in pair->pf_rule
 int launch_score_prefilter(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0, uint32_t count, unsigned long long *key2);
+bool prefilter_sums_counts(const sfm_pair *pair, const sfm_ransac_params &p, uint32_t count);          // after prefilter_pick_rule: the launch sums into zeroed counts[], keys from ransac_argmax_counts
 int launch_pf_prep(sfm_pair *pair, const sfm_ransac_params &p, uint32_t count);
 int prefilter_tile_points(const sfm_pair *pair, const sfm_ransac_params &p);      // points per scoring tile of a launch on this pair
 int launch_pf_cells(sfm_pair *pair, bool want_sorted = false, int tile = 0);                                            // the pair's cell table, (re)built when the points changed        // PfRecords from d_Ecand (paths whose solve kernel does not write them)

@@ -51,4 +51,14 @@ static inline int pf_tile_points(int ld, int tmax)
     return t < 32 ? 32 : t;
 }
 
+// Which epilogue a launch of `count` hypotheses over tiles of `tile` points runs (ransac_prefilter.hip: pf_tail_var): from this many
+// (hypothesis, tile) partial counts on, the counts are summed without an answer and ransac_argmax_counts makes the keys behind the
+// launch; below it the extra launch costs more than the passes save (profiles/NOTES_r09.md).  In this header so that the host-compiled
+// check (tests/hostcheck/pfdecodecheck.hip, tests/test_pf_decode.py) asks the very function the launcher asks.
+constexpr unsigned long long kPfSumCountsMin = 1ull << 21;
+static inline bool pf_sums_counts_at(unsigned count, int ld, int tile)
+{
+    return (unsigned long long)count * (unsigned long long)((ld + tile - 1) / tile) >= kPfSumCountsMin;
+}
+
 } // namespace sfm

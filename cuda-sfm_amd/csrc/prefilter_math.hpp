@@ -551,7 +551,7 @@ SFM_HD bool prefilter_band_pack_reject(float nt)
 // bits of the word (their reject bits sit at positions 4, 2 and 0 (mod 6): disjoint), registers 3..5 into the odd bits (shifted up by
 // one).  pf_pack_code(b) = what the survivor at bit (31 - b) is: ((j & 3) + 8 (j >> 2)) | s << 5 -- the accumulator's row offset among
 // the 32 hypotheses of a pass (device_math's MFMA row order) and the step.
-SFM_HD uint32_t pf_pack_code(int b)
+SFM_HD constexpr uint32_t pf_pack_code(int b)
 {
     const int bitpos = 31 - b, odd = bitpos & 1, p = bitpos - odd;
     const int reg = (p % 6 == 4) ? 0 : (p % 6 == 2) ? 1 : 2;
@@ -559,6 +559,25 @@ SFM_HD uint32_t pf_pack_code(int b)
     const int j = f >> 1, st = f & 1;
     return (uint32_t)((j & 3) + 8 * (j >> 2)) | ((uint32_t)st << 5);
 }
+
+// The same without a table (what the scoring kernel's flush runs: the table's LDS read sat between the ring read and the point and E
+// reads of every flush round).  A reject bit of field f (among the 16 of its register triple) sits at bit 6 f + 4 of 96, i.e. at the
+// even position p = 2 q of the merged word with 6 f + 4 = 2 q (mod 32), 3 f + 2 = q (mod 16); 3 x 11 = 33 = 1 (mod 16), so
+// f = 11 (q - 2) = 10 - 5 q (mod 16).  With q = 15 - (b >> 1): f = 5 (b >> 1) + 15 (mod 16).  Bit 31 - b is odd for even b: the second
+// triple, + 16.  The code is f's bits moved: j = f >> 1, row offset (j & 3) + 8 (j >> 2) = bits 2..1 of f -> 1..0, bits 4..3 stay, the
+// step f & 1 -> bit 5.
+SFM_HD constexpr uint32_t pf_pack_code_closed(int b)
+{
+    const uint32_t f = ((5u * ((uint32_t)b >> 1) + 15u) & 15u) | ((~(uint32_t)b & 1u) << 4);
+    return ((f >> 1) & 3u) | (f & 24u) | ((f & 1u) << 5);
+}
+constexpr bool pf_pack_code_closed_ok()
+{
+    for (int b = 0; b < 32; ++b)
+        if (pf_pack_code_closed(b) != pf_pack_code(b)) return false;
+    return true;
+}
+static_assert(pf_pack_code_closed_ok(), "pf_pack_code_closed: the closed form is not the table's permutation");
 
 // The same as a shift out of a 64-bit constant (what the kernel runs): field f = 2 j + s of the survivor at bit (31 - b).  Bits 31 - b
 // and 30 - b (b even) share the even position p = 30 - b of the merged registers, whose field among the 16 of its half is 4 bits of

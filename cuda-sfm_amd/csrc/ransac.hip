@@ -444,18 +444,7 @@ int launch_ransac_score(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0,
     hipEvent_t *tev = timed ? ctx->tev[ctx->tcount] : nullptr;
     if (timed) SFM_HIP_TRY(hipEventRecord(tev[0], ctx->stream));
     const bool pf_tickets = prefilter && (SFM_SW(p, 3) == 2 || SFM_SW(p, 3) == 17);      // (AB build: kernels that sum into counts[] and draw tickets)
-    int *zero_counts = (grid2d || pf_tickets) ? pair->d_counts : nullptr;
-    const float4 *pts4 = (pair->state.have_pts4 && SFM_SW(p, 0) != 4) ? pair->d_pts4 : nullptr;      // (AB build, reserved[0] == 4: scattered gathers)
-    // pre-filter kernel: one 64-bit accumulator per hypothesis (count | tiles arrived; round 3: a ticket per 32 hypotheses next to
-    // zeroed counts), cleared by the solve kernel (or by a memset when there is none); its per-hypothesis records come from the
-    // lane-solve kernel itself on the default path, from pf_prep_kernel otherwise
     const bool pf_r2 = prefilter && SFM_SW(p, 3) == 2;                   // (AB build) the round-2 kernel: builds its operands itself
-    const uint32_t nzero = !prefilter ? 0u : (pf_tickets ? (count + (uint32_t)kPfGroup - 1u) / (uint32_t)kPfGroup : 2u * count);
-    uint32_t *zero_ticks = prefilter ? pair->d_tick : nullptr;
-    if (prefilter && d_E_given) {
-        SFM_HIP_TRY(hipMemsetAsync(pair->d_tick, 0, (size_t)nzero * sizeof(uint32_t), ctx->stream));
-        zero_ticks = nullptr;
-    }
     PfScales pf_sc = {};
     if (prefilter) (void)prefilter_scales(p.threshold, pf_sc);            // (checked by prefilter_usable)
     if (prefilter && !pf_r2) {                                            // the table of occupied cells the records are checked against
@@ -464,6 +453,20 @@ int launch_ransac_score(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0,
         const int pf_rule = prefilter_pick_rule(pair, p, count);
         const int rcc = launch_pf_cells(pair, pf_rule == kPfRuleBandTile, prefilter_tile_points(pair, p));
         if (rcc != SFM_OK) return rcc;
+    }
+    // pre-filter kernel, large launches (prefilter_sums_counts): every (hypothesis, tile) adds its count to counts[] and
+    // ransac_argmax_counts makes the keys behind it, so counts[] is cleared by the solve kernel (or by a memset when there is none).
+    // Smaller ones: one 64-bit accumulator per hypothesis (count | tiles arrived; lab bench, round 3: a ticket per 32 hypotheses next
+    // to zeroed counts), cleared the same way.  The per-hypothesis records come from the lane-solve kernel itself on the default path,
+    // from pf_prep_kernel otherwise.
+    const bool pf_sums = prefilter && !pf_r2 && !pf_tickets && prefilter_sums_counts(pair, p, count);
+    int *zero_counts = (grid2d || pf_tickets || pf_sums) ? pair->d_counts : nullptr;
+    const float4 *pts4 = (pair->state.have_pts4 && SFM_SW(p, 0) != 4) ? pair->d_pts4 : nullptr;      // (AB build, reserved[0] == 4: scattered gathers)
+    const uint32_t nzero = (!prefilter || pf_sums) ? 0u : (pf_tickets ? (count + (uint32_t)kPfGroup - 1u) / (uint32_t)kPfGroup : 2u * count);
+    uint32_t *zero_ticks = (prefilter && !pf_sums) ? pair->d_tick : nullptr;
+    if (zero_ticks && d_E_given) {
+        SFM_HIP_TRY(hipMemsetAsync(pair->d_tick, 0, (size_t)nzero * sizeof(uint32_t), ctx->stream));
+        zero_ticks = nullptr;
     }
     bool need_prep = prefilter && !pf_r2;
     if (d_E_given) {                 // caller-supplied candidates (sfm_ransac_score_candidates): no solve, clear what it would have cleared
@@ -533,7 +536,13 @@ int launch_ransac_score(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0,
         if (pf_r2) rc = launch_score_prefilter_r2(pair, p, h0, count, key2);
         else
 #endif
-        rc = launch_score_prefilter(pair, p, h0, count, key2);      // arg-max included (per-group tickets)
+        rc = launch_score_prefilter(pair, p, h0, count, key2);      // (lab bench: the earlier epilogues make the keys themselves)
+        if (rc == SFM_OK && pf_sums) {                              // the keys of the complete counts, in front of whatever the caller enqueues next
+            const int ablocks = (int)((count + 4095u) / 4096u);
+            hipLaunchKernelGGL(ransac_argmax_counts, dim3(ablocks < 1024 ? ablocks : 1024), dim3(256), 0, ctx->stream,
+                               pair->d_counts, h0, count, pair->d_key, key2);
+            SFM_HIP_TRY(hipGetLastError());
+        }
     }
 #if SFM_AB
     else if (kernel == SFM_KERNEL_MFMA) {

@@ -19,8 +19,9 @@
 //     k + 1 and the fragments of step k + 2 are on their way from LDS (two accumulator sets, sched_group_barrier);
 //   * lanes with a surviving pair append one word per two steps to the wavefront's ring in LDS; 64 entries at a time go
 //     through the exact filter, one entry per lane, and inliers bump the hypothesis' counter in LDS;
-//   * partial counts reach counts[] through integer atomics (order-independent, so the result is deterministic); the
-//     wavefront that adds the last tile of a 32-hypothesis group folds its keys into the shard's arg-max key.
+//   * partial counts reach counts[] through integer atomics (order-independent, so the result is deterministic): large launches
+//     add them without waiting for an answer and ransac_argmax_counts (ransac.hip) makes the keys behind the launch; in smaller
+//     ones the lane that adds a hypothesis' last tile stores its count and the wavefront folds its keys into the shard's arg-max key.
 #include "ransac_device.hpp"
 #include "block_ops.hpp"
 #include "prefilter_math.hpp"
@@ -173,6 +174,14 @@ __device__ __forceinline__ void mfma_step(const PfFrags &a, const PfFrags &b, f1
 // VAR (AB build only; the product instantiates VAR = 0): bit 0 = round 3's epilogue -- partial counts summed into counts[] with
 // atomics, a ticket per 32-hypothesis group, the last wavefront re-reads the counts (two dependent round trips per pass).
 constexpr int kPfVarTickets = 1;
+// Round 9 tried three ways to shorten the tail of a pass of the two product rules (profiles/NOTES_r09.md).  One paid, for large
+// launches: VAR = 0 sums the counts into counts[] without waiting for an answer.  The product also instantiates
+// kPfVarAnswerEpilogue -- round 4's epilogue -- for launches too small to pay for the arg-max launch behind them
+// (kPfSumCountsMin); the other two did not pay and exist in the lab bench only (reserved[3] = 8 + bits, include/sfm_amd_ab.h):
+constexpr int kPfVarDrainLocal = 2;         // in the drain a lane works through up to 3 further survivors of its entry before the rest is re-queued
+constexpr int kPfVarClosedDecode = 4;       // a survivor's bit position is decoded by arithmetic (pf_pack_code_closed) instead of the 32-byte table in LDS
+constexpr int kPfVarAnswerEpilogue = 8;     // one returning 64-bit atomic per (hypothesis, tile); the last tile's lane stores the count and owns the key
+constexpr int kPfVarDrainK1 = 16, kPfVarDrainK7 = 32;      // the drain's cap: 1 or 7 further survivors per lane
 
 // FL2 (experiment): a ring of 256 entries, flushed 128 at a time -- two entries per lane, their LDS reads issued together
 // WIDE (experiment): ring entries of 16 bytes that cover FOUR steps (two conversions): half as many appends
@@ -184,7 +193,7 @@ constexpr int kPfVarTickets = 1;
 // product runs are compiled for five wavefronts per SIMD, which caps them at 96; the lab bench's variants keep the default.
 constexpr int pf_score_waves_per_simd(int var, int rule, int fl2, int pipe, int wide, int prio)
 {
-    return (var == 0 && (rule == kPfRuleBandTile || rule == kPfRuleBandPack) && !fl2 && !pipe && !wide && !prio) ? 5 : 4;
+    return ((var & kPfVarTickets) == 0 && (rule == kPfRuleBandTile || rule == kPfRuleBandPack) && !fl2 && !pipe && !wide && !prio) ? 5 : 4;
 }
 
 template <int W, int VAR = 0, int RULE = kPfRuleBandTile, int FL2 = 0, int PIPE = 0, int WIDE = 0, int PRIO = 0>
@@ -223,7 +232,13 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
     const uint32_t nstatic = gridDim.x * (uint32_t)W;             // passes handed out by position
     using LT = PfLds<RULE>;
     constexpr bool kBand = RULE != kPfRuleG, kTile = RULE == kPfRuleBandTile, kPack = RULE == kPfRuleBandPack || kTile;
-    static_assert(!(FL2 && kPack) && !(VAR && kPack), "the recorded variants were built on the v_alignbit scan");
+    static_assert(!(FL2 && kPack) && !((VAR & kPfVarTickets) && kPack), "the recorded variants were built on the v_alignbit scan");
+    // the pass tail of round 9: the product's two rules (and their lab-bench twins with the parts that did not pay switched on)
+    constexpr bool kTail9 = kPack && W == 16 && !FL2 && !PIPE && !WIDE && !PRIO && !(VAR & kPfVarTickets);
+    static_assert(kTail9 || (VAR & ~kPfVarTickets) == 0, "the pass-tail switches belong to the product's two rules");
+    constexpr int kDrainMore = !kTail9 ? 0 : (VAR & kPfVarDrainK1) ? 1 : (VAR & kPfVarDrainK7) ? 7 : (VAR & kPfVarDrainLocal) ? 3 : 0;
+    constexpr bool kDecodeTable = !(kTail9 && (VAR & kPfVarClosedDecode));
+    constexpr bool kSumCounts = kTail9 && !(VAR & kPfVarAnswerEpilogue);
     constexpr int kRing = FL2 ? 256 : kPfRing;
     constexpr int kEnt = WIDE ? 16 : 8;                       // bytes per ring entry
     static_assert(!WIDE || (kPack && !PIPE && !FL2), "wide entries: the packed scan's plain loop only");
@@ -279,7 +294,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
     // memory would balance the blocks too, but 131072 device-scope atomics on one address take 1.5 ms.)
     uint32_t *next_idx = reinterpret_cast<uint32_t *>(smem + L.next);
     if (threadIdx.x == 0) *next_idx = (uint32_t)W;
-    if (kPack && threadIdx.x < 32) smem[L.lut + threadIdx.x] = (unsigned char)pf_pack_code((int)threadIdx.x);
+    if (kPack && kDecodeTable && threadIdx.x < 32) smem[L.lut + threadIdx.x] = (unsigned char)pf_pack_code((int)threadIdx.x);
     // tile rule: the pair's bound and this tile's boxes (pf_bucket_scatter_kernel, once per fillXU) are requested now and used after the staging
     float pf_B = 0.0f;
     uint32_t bw[8] = {};
@@ -421,38 +436,50 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
         int head = 0, nq = 0;                       // ring state (wave-uniform)
         // a lane's point in 32-point block 0 (LDS byte address, a multiple of 16) | its accumulator-row offset 4 (lane >> 5)
         const uint32_t lane_tag = (uint32_t)(size_t)(lds_cf4 *)pts + (uint32_t)(row * 16) + (uint32_t)(half * 4);
-        auto flush = [&](int m) {
+        // the exact decision for the FIRST surviving pair of a ring entry's mask; the survivor leaves the mask
+        // entry = { 32-bit mask of surviving accumulators (bit 31 - r: accumulator r of the pair's first point block, bit 15 - r:
+        // of its second), LDS byte address of the lane's point in the pair's first block | 4 (lane >> 5) }.
+        auto decide_first = [&](uint32_t &rest, uint32_t tag) {
+            const int b = __builtin_clz(rest);                                  // the first surviving accumulator of the first step that has one
+            rest &= ~(0x80000000u >> b);
+            // G rule: bit 31 - r = accumulator r of the first step, 15 - r of the second; band rule: 31 - 2 r and 30 - 2 r; packed
+            // scan: pf_pack_code through the table (lab bench: as arithmetic on b, about seven vector instructions -- measured slower)
+            int hl, sub;
+            if (kPack) {
+                const uint32_t code = kDecodeTable ? (uint32_t)lut_l[b] : pf_pack_code_closed(b);
+                hl = (int)(code & 31u) + (int)(tag & 4u); sub = (int)(code >> 5);
+            } else {
+                const int r = kBand ? b >> 1 : b & 15;
+                sub = kBand ? b & 1 : b >> 4;
+                hl = r + (r & 12) + (int)(tag & 4u);                            // accumulator row = local hypothesis: (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+            }
+            if (hl < nvalid) {
+                const f4v q = *(lds_cf4 *)((__attribute__((address_space(3))) const unsigned char *)0 + ((tag & ~15u) + ((uint32_t)sub << 9)));
+                lds_cf *e = etab_l + hl;
+                const v2f p0 = { e[0], e[32] }, p1 = { e[64], e[96] }, p2 = { e[128], e[160] }, p3 = { e[192], e[224] };      // (e2 e6) (e1 e3) (e5 e7) (e0 e4): one ds_read2_b32 each
+                const float e8 = e[256];
+                if (pf_exact_inlier(p0, p1, p2, p3, e8, v2f{ q.x, q.y }, v2f{ q.z, q.w }, band))
+                    __hip_atomic_fetch_add(cnt_l + hl, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        };
+        auto flush = [&](int m, auto more_c) {
             // Exact decision for up to 64 ring entries starting at `head`, one entry per lane: the lane evaluates the FIRST
             // surviving pair of its entry; an entry that holds more goes back to the tail of the ring with the rest of its
             // mask, so that every pass of the exact filter runs on (nearly) 64 busy lanes.
-            // entry = { 32-bit mask of surviving accumulators (bit 31 - r: accumulator r of the pair's first point block, bit 15 - r:
-            // of its second), LDS byte address of the lane's point in the pair's first block | 4 (lane >> 5) }.
+            // Lab bench (kMore > 0, the drain only): a lane works through up to kMore further survivors of its entry itself before
+            // the rest is re-queued -- no ring traffic, where a re-queued entry waits for a whole round that runs on a handful of
+            // lanes.  Every survivor is still decided exactly once.  Measured: no gain (profiles/r09_pass_tail_ab.txt).
+            constexpr int kMore = decltype(more_c)::value;
             uint32_t rest = 0, tag = 0;
             if (PRIO == 2) __builtin_amdgcn_s_setprio(2);
             if (lane < m) {
                 const u2v ent = *ring_at(((uint32_t)head + (uint32_t)lane) * 8u);
                 tag = ent.y;
-                const uint32_t surv = ent.x;
-                const int b = __builtin_clz(surv);                                  // the first surviving accumulator of the first step that has one
-                rest = surv & ~(0x80000000u >> b);
-                // G rule: bit 31 - r = accumulator r of the first step, 15 - r of the second; band rule: 31 - 2 r and 30 - 2 r; packed
-                // scan: the table (pf_pack_code)
-                int hl, sub;
-                if (kPack) {
-                    const uint32_t code = lut_l[b];
-                    hl = (int)(code & 31u) + (int)(tag & 4u); sub = (int)(code >> 5);
-                } else {
-                    const int r = kBand ? b >> 1 : b & 15;
-                    sub = kBand ? b & 1 : b >> 4;
-                    hl = r + (r & 12) + (int)(tag & 4u);                            // accumulator row = local hypothesis: (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-                }
-                if (hl < nvalid) {
-                    const f4v q = *(lds_cf4 *)((__attribute__((address_space(3))) const unsigned char *)0 + ((tag & ~15u) + ((uint32_t)sub << 9)));
-                    lds_cf *e = etab_l + hl;
-                    const v2f p0 = { e[0], e[32] }, p1 = { e[64], e[96] }, p2 = { e[128], e[160] }, p3 = { e[192], e[224] };      // (e2 e6) (e1 e3) (e5 e7) (e0 e4): one ds_read2_b32 each
-                    const float e8 = e[256];
-                    if (pf_exact_inlier(p0, p1, p2, p3, e8, v2f{ q.x, q.y }, v2f{ q.z, q.w }, band))
-                        __hip_atomic_fetch_add(cnt_l + hl, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                rest = ent.x;
+                decide_first(rest, tag);
+                if constexpr (kMore > 0) {
+#pragma unroll 1
+                    for (int it = 0; it < kMore && rest != 0u; ++it) decide_first(rest, tag);
                 }
             }
             const unsigned long long more = __ballot(rest != 0u);
@@ -464,6 +491,8 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
             nq += __builtin_popcountll(more) - m;
             if (PRIO == 2) __builtin_amdgcn_s_setprio(0);
         };
+        constexpr std::integral_constant<int, 0> kInLoop{};            // the scan's flushes: one survivor per lane and round (round 6: more lost 2 %)
+        constexpr std::integral_constant<int, kDrainMore> kDrain{};
         // wide entries { survivors of phase 2 k, survivors of phase 2 k + 1, tag of phase 2 k, - }: the first survivor of the first word that has one
         auto flush_w = [&](int m) {
             uint32_t ra = 0, rb = 0, tag = 0;
@@ -566,7 +595,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
             __builtin_amdgcn_sched_barrier(0);
             SFM_PHASE("append_and_inloop_flush");
             if (any) {
-                while (nq >= 64) flush(64);
+                while (nq >= 64) flush(64, kInLoop);
                 const int slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(any >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)any, 0u));
                 if (mine) *ring_at(((uint32_t)(head + nq) + (uint32_t)slot) * 8u) = u2v{ ~rej32, lane_tag + ((uint32_t)pp << 10) };
                 nq += __builtin_popcountll(any);
@@ -589,7 +618,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
             const unsigned long long any = __ballot(mine);
             SFM_PHASE("append_and_inloop_flush");
             if (any) {
-                while (nq >= 64) flush(64);
+                while (nq >= 64) flush(64, kInLoop);
                 const int slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(any >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)any, 0u));
                 if (mine) *ring_at(((uint32_t)(head + nq) + (uint32_t)slot) * 8u) = u2v{ ~rej32, lane_tag + ((uint32_t)pp << 10) };
                 nq += __builtin_popcountll(any);
@@ -666,7 +695,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
             if (any) {
                 if (FL2) { while (nq >= 128) flush2(); }
                 else
-                while (nq >= 64) flush(64);             // make room first (a flush of 64 entries re-queues up to 64: it may take more than one)
+                while (nq >= 64) flush(64, kInLoop);             // make room first (a flush of 64 entries re-queues up to 64: it may take more than one)
                 const int slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(any >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)any, 0u));
                 if (mine) *ring_at(((uint32_t)(head + nq) + (uint32_t)slot) * 8u) = u2v{ ~rej32, lane_tag + ((uint32_t)pp << 10) };
                 nq += __builtin_popcountll(any);
@@ -684,7 +713,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
         SFM_PHASE("drain_flush");
         if (FL2) { while (nq >= 128) flush2(); }
         if (WIDE) { while (nq > 0) flush_w(min(nq, 64)); }
-        while (nq > 0) flush(min(nq, 64));
+        while (nq > 0) flush(min(nq, 64), kDrain);
         SFM_PHASE("epilogue");
         PF_PHASE(7);
         if (VAR & kPfVarTickets) {
@@ -713,6 +742,20 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
                 atomicMax(best_key, k);
                 if (best_key2) atomicMax(best_key2, k);
             }
+        }
+        } else if (kSumCounts) {
+        // LDS counters -> counts[] (zeroed by the solve kernel, or by a memset in front of caller-supplied candidates): one 32-bit
+        // atomic per (hypothesis, tile) that has inliers, whose answer nobody waits for -- a sum needs none.  The keys come from
+        // ransac_argmax_counts behind this launch (ransac.hip), as on the tile-parallel path of the plain kernel.  A wavefront's LDS
+        // operations complete in order: the counters are read before install_rows clears them.
+        if (lane < nvalid) {
+            const int c = cnt[lane];
+            if (c) __hip_atomic_fetch_add(&counts[h_first + lane], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (have_next) {
+            if (kTile) build_operands(e_next, key0n, dn_next, lin_next);
+            else { afrag = afrag_next; key0 = key0n; }
+            install_rows(e_next);
         }
         } else {
         // LDS counters -> the hypothesis' accumulator in global memory: ONE 64-bit atomic per hypothesis adds this tile's count
@@ -1238,6 +1281,35 @@ static int pf_tile_of(const sfm_pair *pair, const sfm_ransac_params &p)
 
 int prefilter_tile_points(const sfm_pair *pair, const sfm_ransac_params &p) { return pf_tile_of(pair, p); }
 
+// Which epilogue a launch of the product's two rules runs (VAR bits of the instance).  Summing the counts without an answer saves every
+// wavefront a device-scope round trip per pass and costs one short launch (ransac_argmax_counts) per call: it pays for large launches
+// and costs small ones (profiles/NOTES_r09.md has the crossover, profiles/r09_pass_tail_ab.txt every run) -- so it runs from
+// kPfSumCountsMin (hypothesis, tile) partial counts per launch on (prefilter_lds.hpp: pf_sums_counts_at), round 4's epilogue below that.
+// Lab bench: reserved[3] = 8 + (1: the drain works through further survivors locally, 2: table-free decode, 4: round 4's epilogue at every
+// size); reserved[1] = 18: counts are summed at every size; 16 / 17: the same with the drain's cap at 1 / 7 further survivors (per-tile form).
+static int pf_tail_var(const sfm_pair *pair, const sfm_ransac_params &p, uint32_t count)
+{
+    const bool large = pf_sums_counts_at(count, pair->ld, pf_tile_of(pair, p));
+    if (pair->pf_rule == kPfRuleBandTile && SFM_SW(p, 1) == 16) return kPfVarDrainK1;
+    if (pair->pf_rule == kPfRuleBandTile && SFM_SW(p, 1) == 17) return kPfVarDrainK7;
+    int var = 0;
+    const bool lab = SFM_SW(p, 3) >= 8 && SFM_SW(p, 3) < 16;
+    if (lab && (SFM_SW(p, 3) & 1)) var |= kPfVarDrainLocal;
+    if (lab && (SFM_SW(p, 3) & 2)) var |= kPfVarClosedDecode;
+    const bool sum = (lab && (SFM_SW(p, 3) & 4)) ? false : (large || (SFM_SW(p, 1) >= 16 && SFM_SW(p, 1) <= 18));
+    if (!sum) var |= kPfVarAnswerEpilogue;
+    return var;
+}
+
+// Does the scoring launch of this call (rule picked: prefilter_pick_rule) only SUM into counts[] -- zeroed before it, keys from
+// ransac_argmax_counts behind it?  The lab bench's recorded variants keep their own epilogues.
+bool prefilter_sums_counts(const sfm_pair *pair, const sfm_ransac_params &p, uint32_t count)
+{
+    const bool product_rule = pair->pf_rule == kPfRuleBandTile || pair->pf_rule == kPfRuleBandPack;
+    const bool variant = SFM_SW(p, 1) == 5 || (SFM_SW(p, 1) >= 11 && SFM_SW(p, 1) <= 15);      // 12 wavefronts, pipelined scan, wide entries, s_setprio
+    return product_rule && !variant && !(pf_tail_var(pair, p, count) & kPfVarAnswerEpilogue);
+}
+
 int launch_score_prefilter(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0, uint32_t count, unsigned long long *key2)
 {
     sfm_ctx *ctx = pair->ctx;
@@ -1262,6 +1334,7 @@ int launch_score_prefilter(sfm_pair *pair, const sfm_ransac_params &p, uint32_t 
     const int dynamic = SFM_SW(p, 1) == 2 ? 0 : 1;                               // (AB build, reserved[1] == 2: static striding)
     const int var = SFM_SW(p, 3) >= 16 ? SFM_SW(p, 3) - 16 : 0;                 // (AB build, reserved[3] = 16 + VAR bits)
     const int rule = pair->pf_rule;
+    const int tail_var = pf_tail_var(pair, p, count);
     const bool fl2 = rule == kPfRuleBand && waves == kPfWaves && SFM_SW(p, 1) == 9;      // (AB build: 256-entry ring, two entries per lane per flush)
     const bool wide = rule == kPfRuleBandTile && SFM_SW(p, 1) == 13;                     // (AB build: 16-byte ring entries covering four steps)
     const int lds_bytes = wide ? PfLds<kPfRuleBand>(tile, kPfRing, 16).bytes : fl2 ? PfLds<kPfRuleBand>(tile, 256).bytes : rule != kPfRuleG ? PfLds<kPfRuleBand>(tile).bytes : PfLds<kPfRuleG>(tile).bytes;
@@ -1288,11 +1361,24 @@ int launch_score_prefilter(sfm_pair *pair, const sfm_ransac_params &p, uint32_t 
     else if (wide) rcl = launch(&ransac_score_prefilter<16, 0, kPfRuleBandTile, 0, 0, 1>);
     else if (rule == kPfRuleBandTile && SFM_SW(p, 1) == 14) rcl = launch(&ransac_score_prefilter<16, 0, kPfRuleBandTile, 0, 0, 0, 1>);     // (s_setprio experiments)
     else if (rule == kPfRuleBandTile && SFM_SW(p, 1) == 15) rcl = launch(&ransac_score_prefilter<16, 0, kPfRuleBandTile, 0, 0, 0, 2>);
+    else if (tail_var != 0 && tail_var != kPfVarAnswerEpilogue) {                                                                          // (round 9's pass tail: the parts that did not pay)
+        rcl = SFM_E_INVALID;
+#define PF_TAIL_CASE(V) case V: rcl = rule == kPfRuleBandPack ? launch(&ransac_score_prefilter<16, V, kPfRuleBandPack>) : launch(&ransac_score_prefilter<16, V, kPfRuleBandTile>); break
+        switch (tail_var) {
+        PF_TAIL_CASE(2); PF_TAIL_CASE(4); PF_TAIL_CASE(6); PF_TAIL_CASE(10); PF_TAIL_CASE(12); PF_TAIL_CASE(14);
+        case kPfVarDrainK1: rcl = launch(&ransac_score_prefilter<16, kPfVarDrainK1, kPfRuleBandTile>); break;
+        case kPfVarDrainK7: rcl = launch(&ransac_score_prefilter<16, kPfVarDrainK7, kPfRuleBandTile>); break;
+        default: set_error("pass-tail switches %d: no such instance", tail_var); break;
+        }
+#undef PF_TAIL_CASE
+    }
     else
 #endif
-    if (rule == kPfRuleBandPack) rcl = launch(&ransac_score_prefilter<16, 0, kPfRuleBandPack>);
+    if (tail_var & kPfVarAnswerEpilogue) rcl = rule == kPfRuleBandPack ? launch(&ransac_score_prefilter<16, kPfVarAnswerEpilogue, kPfRuleBandPack>)
+                                                                       : launch(&ransac_score_prefilter<16, kPfVarAnswerEpilogue, kPfRuleBandTile>);
+    else if (rule == kPfRuleBandPack) rcl = launch(&ransac_score_prefilter<16, 0, kPfRuleBandPack>);
     else rcl = launch(&ransac_score_prefilter<16, 0, kPfRuleBandTile>);
-    (void)var; (void)fl2; (void)wide;
+    (void)var; (void)fl2; (void)wide; (void)tail_var;
     if (rcl != SFM_OK) return rcl;
     SFM_HIP_TRY(hipGetLastError());
     pair->last_grid = (int)cols * ntiles; pair->last_block = waves * 64; pair->last_lds = lds_bytes;

@@ -35,7 +35,9 @@ extern "C" {
  *       sets with 16 / 12 wavefronts per block (30 spills / 140 registers: profiles/r06_ab_pack_scan.txt); 13 ring entries of 16
  *       bytes that cover four steps instead of 8 bytes per two steps (half as many appends: measured 3 % slower, r06_ab_wide_entries.txt);
  *       14 / 15 s_setprio 2 around the MFMA issue / around the exact filter of a flush (level: r06_ab_prio.txt); 13-15 run the per-tile form
- *       on every call;
+ *       on every call; 18 the pre-filter launch sums its counts into counts[] without waiting for an answer, keys from ransac_argmax_counts
+ *       behind it, at EVERY size (the product: from 2^21 (hypothesis, tile) partial counts per launch on); 16 / 17 the same, and in the drain
+ *       a lane works through up to 1 / 7 further survivors of its ring entry before the rest is re-queued (per-tile form);
  *   [2] k > 0: minimum hypothesis batches per scoring block (default 8); pre-filter kernel: grid columns;
  *   [3] 1 AUTO never picks SFM_KERNEL_PREFILTER; 2 the round-2 pre-filter kernel (csrc/ab/ransac_prefilter_r2.hip);
  *       3 per-hypothesis records from the stand-alone kernel instead of the lane-solve kernel; 4 the G rule of rounds 2-4
@@ -45,7 +47,11 @@ extern "C" {
  *       sigma and the coefficient slots derived per (hypothesis, tile) inside the scoring kernel from a 16-byte record:
  *       profiles/r06_ab_tile_rule_fast.txt, r06_fresh_pair_cost.txt); 5 the band rule scanned with one
  *       v_alignbit_b32 per pair (round 5) instead of the six-bit conversion of round 6 ([1] = 5, 7, 9 imply it: those variants were
- *       built on that scan); 16 + bits: recorded variants built on the G rule. */
+ *       built on that scan); 16 + bits: recorded variants built on the G rule; 8 + bits: the pass tail of the product's two rules
+ *       (profiles/NOTES_r09.md, r09_pass_tail_ab.txt) -- 1 in the drain a lane works through up to 3 further survivors of its ring entry
+ *       itself before the rest is re-queued (measured: no gain), 2 a survivor's bit position is decoded by arithmetic instead of the
+ *       32-byte table in LDS (measured 0.3-0.6 % slower), 4 round 4's epilogue at every size: one returning 64-bit atomic per (hypothesis,
+ *       tile), the keys made inside the scoring kernel (the product: below 2^21 partial counts per launch); each on its own or together. */
 
 /* Where block 0 of the last pre-filter scoring launch (SFM_KERNEL_PREFILTER) spent its time: ticks[0] shader-clock ticks and
  * ticks[1] 100 MHz ticks over its lifetime (as above); 100 MHz ticks since its start at: [2] tile staged, [3] first pass'

@@ -1,4 +1,7 @@
-"""Where block 0 of ransac_score_prefilter spends its time (sfm_ransac_last_phases), per shard size and grid width."""
+"""Where block 0 of ransac_score_prefilter spends its time (sfm_ransac_last_phases), per shard size and grid width.
+python profiles/phase_probe.py LABEL [reserved1 [reserved3 [samples]]]: 2^20 hypotheses only, with those lab-bench switches
+(include/sfm_amd_ab.h), `samples` launches stamped, each line tagged LABEL and carrying the drain (ring_drained - first_block_scanned)
+and the epilogue (first_pass_done - ring_drained) -- profiles/r09_phase_probe.txt."""
 import json
 import os
 import sys
@@ -16,15 +19,19 @@ scene = synth.two_view_scene(n)
 d_sift = torch.from_numpy(scene["sift"].view(np.uint8).reshape(n, 576)).to(dev)
 pair = S.ImagePair(ctx, scene["K"], scene["Kinv"], 2, n)
 pair.fillXU(d_sift)
-for H, cols in ((131072, 0), (131072, 64), (262144, 0), (1048576, 0), (1048576, 64)):
+label = sys.argv[1] if len(sys.argv) > 1 else None
+r1, r3, samples = (int(sys.argv[k]) if len(sys.argv) > k else d for k, d in ((2, 0), (3, 0), (4, 1)))
+cases = ((1048576, 0),) * samples if label else ((131072, 0), (131072, 64), (262144, 0), (1048576, 0), (1048576, 64))
+for H, cols in cases:
     p = S.default_params(n, num_hypotheses=H, seed=3, kernel=S.KERNEL_PREFILTER)
-    p.reserved[2] = cols
+    p.reserved[1], p.reserved[2], p.reserved[3] = r1, cols, r3
     for _ in range(10):
         pair.estimateE(p)
     ctx.kernel_timing(True) if hasattr(ctx, "kernel_timing") else None
     pair.estimateE(p)
     t = pair.last_phases()
     us = lambda k: round(t[k] / 100.0, 2)
-    print(json.dumps({"hypotheses": H, "grid": pair.last_launch()["grid"], "block0_lifetime_us": us(1), "tile_staged_us": us(2), "first_pass_prepared_us": us(3),
+    tag = {"build": label, "reserved": [0, r1, cols, r3], "drain_us": round((t[7] - t[4]) / 100.0, 2), "epilogue_us": round((t[5] - t[7]) / 100.0, 2)} if label else {}
+    print(json.dumps({**tag, "hypotheses": H, "grid": pair.last_launch()["grid"], "block0_lifetime_us": us(1), "tile_staged_us": us(2), "first_pass_prepared_us": us(3),
                       "first_block_scanned_us": us(4), "ring_drained_us": us(7), "first_pass_done_us": us(5), "passes_of_wave0": t[6],
                       "shader_mhz": round(100.0 * t[0] / max(t[1], 1))}), flush=True)
