@@ -266,19 +266,19 @@ void ransac_score_mfma(const float *__restrict__ X0, const float *__restrict__ X
 }
 
 template <int WPB>
-static int launch_mfma_t(sfm_pair *pair, uint32_t h0, uint32_t count, float thr, int tile, int ntiles, int grid, size_t lds)
+static int launch_mfma_t(sfm_pair *pair, ShardSlot &s, hipStream_t stream, uint32_t h0, uint32_t count, float thr, int tile, int ntiles, int grid, size_t lds)
 {
     const int rc_lds = allow_big_lds(pair->ctx, reinterpret_cast<const void *>(&ransac_score_mfma<WPB>));
     if (rc_lds != SFM_OK) return rc_lds;
-    hipLaunchKernelGGL(ransac_score_mfma<WPB>, dim3(grid), dim3(WPB * 64), lds, pair->ctx->stream,
-                       pair->d_X[0], pair->d_X[1], pair->ld, pair->n, pair->d_Ecand, h0, count, thr, tile, ntiles,
-                       pair->d_counts, pair->d_key);
+    hipLaunchKernelGGL(ransac_score_mfma<WPB>, dim3(grid), dim3(WPB * 64), lds, stream,
+                       pair->d_X[0], pair->d_X[1], pair->ld, pair->n, s.Ecand, h0, count, thr, tile, ntiles,
+                       s.counts, s.key);
     SFM_HIP_TRY(hipGetLastError());
     pair->last_grid = grid; pair->last_block = WPB * 64; pair->last_lds = (int)lds;
     return SFM_OK;
 }
 
-int launch_score_mfma(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0, uint32_t count)
+int launch_score_mfma(sfm_pair *pair, ShardSlot &s, hipStream_t stream, const sfm_ransac_params &p, uint32_t h0, uint32_t count)
 {
     sfm_ctx *ctx = pair->ctx;
     const int tile = pair->ld < kTileMax ? pair->ld : kTileMax;
@@ -292,7 +292,7 @@ int launch_score_mfma(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0, u
     if (per_cu < 1) per_cu = 1;
     const uint32_t resident = (uint32_t)ctx->num_cus * (uint32_t)per_cu;
     const int grid = (int)(nbb < resident ? nbb : resident);
-    return launch_mfma_t<WPB>(pair, h0, count, p.threshold, tile, ntiles, grid, lds);
+    return launch_mfma_t<WPB>(pair, s, stream, h0, count, p.threshold, tile, ntiles, grid, lds);
 }
 
 } // namespace sfm

@@ -378,7 +378,7 @@ void ransac_score_prefilter_r2(const float *__restrict__ X0, const float *__rest
 } // namespace r2
 using namespace r2;
 
-int launch_score_prefilter_r2(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0, uint32_t count, unsigned long long *key2)
+int launch_score_prefilter_r2(sfm_pair *pair, ShardSlot &s, hipStream_t stream, const sfm_ransac_params &p, uint32_t h0, uint32_t count, unsigned long long *key2)
 {
     sfm_ctx *ctx = pair->ctx;
     PfScales sc;
@@ -395,9 +395,9 @@ int launch_score_prefilter_r2(sfm_pair *pair, const sfm_ransac_params &p, uint32
     if (p.reserved[2] > 0) cols = (uint32_t)p.reserved[2];
     if (cols > iters) cols = iters;
     if (cols < 1) cols = 1;
-    hipLaunchKernelGGL(ransac_score_prefilter_r2, dim3(cols, ntiles), dim3(kPfWaves * 64), kPfLdsBytes, ctx->stream,
-                       pair->d_X[0], pair->d_X[1], pair->ld, pair->n, pair->d_Ecand, h0, count, p.threshold, sc,
-                       pair->d_counts, pair->d_tick, pair->d_key, key2, pair->d_clk);
+    hipLaunchKernelGGL(ransac_score_prefilter_r2, dim3(cols, ntiles), dim3(kPfWaves * 64), kPfLdsBytes, stream,
+                       pair->d_X[0], pair->d_X[1], pair->ld, pair->n, s.Ecand, h0, count, p.threshold, sc,
+                       s.counts, s.tick, s.key, key2, pair->d_clk);
     SFM_HIP_TRY(hipGetLastError());
     pair->last_grid = (int)cols * ntiles; pair->last_block = kPfWaves * 64; pair->last_lds = kPfLdsBytes;
     return SFM_OK;

@@ -10,7 +10,6 @@
 #include <string.h>
 #include <new>
 #include <atomic>
-#include <utility>
 #include <vector>
 #include <algorithm>
 #include <initializer_list>
@@ -602,11 +601,11 @@ int sfm_pair_create(sfm_ctx *ctx, const float h_K[9], const float h_Kinv[9], int
     A(&p->d_E, 9); A(&p->d_P, 64); A(&p->d_Pinv, 64); A(&p->d_Pind, 8);
     A(&p->d_points, (size_t)4 * num_points);
     A(&p->d_mask, (size_t)num_points);
-    A(&p->d_key, 2); A(&p->d_best, 2); A(&p->d_clk, kClkWords); A(&p->d_bound, 10);      // [0] bound (fill_xu_kernel), [2..9] the coordinate boxes (pf_cells_build_kernel)
+    A(&p->slot[0].key, 2); A(&p->d_best, 2); A(&p->d_clk, kClkWords); A(&p->d_bound, 10);      // [0] bound (fill_xu_kernel), [2..9] the coordinate boxes (pf_cells_build_kernel)
     if (rc != SFM_OK) { sfm_pair_destroy(p); return rc; }
     hipError_t e = hipMemcpyAsync(p->d_K, h_K, 9 * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(p->d_Kinv, h_Kinv, 9 * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(p->d_key, 0, 2 * sizeof(unsigned long long), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(p->slot[0].key, 0, 2 * sizeof(unsigned long long), ctx->stream);
     p->state.key_clean = true;
     if (e == hipSuccess) e = hipMemsetAsync(p->d_best, 0, 2 * sizeof(uint32_t), ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(p->d_bound, 0, 10 * sizeof(unsigned long long), ctx->stream);
@@ -635,11 +634,11 @@ int sfm_pair_destroy(sfm_pair *p)
     if (!p) return SFM_OK;
     if (p->ctx) { (void)hipSetDevice(p->ctx->device); (void)hipStreamSynchronize(p->ctx->stream); }
     void *bufs[] = { p->d_K, p->d_Kinv, p->d_U[0], p->d_U[1], p->d_X[0], p->d_X[1], p->d_pts4, p->d_E, p->d_P, p->d_Pinv, p->d_Pind,
-                     p->d_points, p->d_mask, p->d_key, p->d_best, p->d_counts, p->d_Ecand, p->d_clk, p->d_tick,
-                     p->alt_counts, p->alt_Ecand, p->alt_tick, p->alt_key, p->d_pf, p->alt_pf, p->d_bound, p->d_cells, p->d_pts4s, p->d_tile_boxes, p->d_buckets,
+                     p->d_points, p->d_mask, p->d_best, p->d_clk, p->d_bound, p->d_cells, p->d_pts4s, p->d_tile_boxes, p->d_buckets,
                      p->d_rstate, p->d_rpoints, p->d_rreproj, p->d_rwork, p->d_vstate, p->d_vreproj, p->d_vwork, p->d_vhyp, p->d_vcounts, p->d_awork,
                      p->d_lwork, p->d_lhyp };
     for (void *b : bufs) if (b) (void)hipFree(b);
+    for (ShardSlot &s : p->slot) shard_slot_free(s);
     if (p->pipe_stream) { (void)hipStreamSynchronize(p->pipe_stream); (void)hipStreamDestroy(p->pipe_stream); }
     for (hipEvent_t e : p->pipe_final) if (e) (void)hipEventDestroy(e);
     if (p->pipe_call) (void)hipEventDestroy(p->pipe_call);
@@ -700,7 +699,7 @@ static int score_shard(sfm_pair *pair, const sfm_ransac_params *p, uint64_t *d_k
     if (rc != SFM_OK) return rc;
     SFM_FLUSH(pair);
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
-    return launch_ransac_score(pair, *p, h0, count, reinterpret_cast<unsigned long long *>(d_key_out), d_E);
+    return launch_ransac_score(pair, pair->slot[0], pair->ctx->stream, *p, h0, count, reinterpret_cast<unsigned long long *>(d_key_out), d_E);
 }
 
 int sfm_ransac_score(sfm_pair *pair, const sfm_ransac_params *p) { return score_shard(pair, p, nullptr, nullptr); }
@@ -725,31 +724,17 @@ int sfm_ransac_score_into_slot(sfm_pair *pair, const sfm_ransac_params *p, uint6
     int rc = resolve_shard(pair, p, &h0, &count);
     if (rc != SFM_OK) return rc;
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
-    // the launchers work on the pair's current per-shard buffers and the context's stream: lend them slot 1's buffers and
-    // the caller's stream for the duration of the (asynchronous) launches -- kernel arguments are captured at launch
-    if (slot == 1 && !pair->alt_key) {
-        SFM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pair->alt_key), 2 * sizeof(unsigned long long)));
+    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : pair->ctx->stream;
+    if (slot == 1 && !pair->slot[1].key) {
+        SFM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pair->slot[1].key), 2 * sizeof(unsigned long long)));
         // cleared on the stream the launches below go to.  (Until round 6 this was a plain hipMemset: it runs on the NULL stream, which a
         // non-blocking stream does not wait for -- queued behind slot 0's kernels when the context works on the null stream, it cleared slot
         // 1's key while or after slot 1's first fused-kernel launch wrote it: the first pipelined call of a pair on slot 1 could finalize a
         // partial or empty key.  Found by the fuzz's stateful round; profiles/pipelined_burst_case.py.)
-        SFM_HIP_TRY(hipMemsetAsync(pair->alt_key, 0, 2 * sizeof(unsigned long long), hip_stream ? static_cast<hipStream_t>(hip_stream) : pair->ctx->stream));
+        SFM_HIP_TRY(hipMemsetAsync(pair->slot[1].key, 0, 2 * sizeof(unsigned long long), stream));
     }
-    auto swap_slot = [&]() {
-        std::swap(pair->d_counts, pair->alt_counts); std::swap(pair->d_tick, pair->alt_tick);
-        std::swap(pair->d_Ecand, pair->alt_Ecand); std::swap(pair->cap_hyps, pair->alt_cap_hyps);
-        std::swap(pair->d_pf, pair->alt_pf);
-        pair->state.key_clean = false;      // (the flag describes the pair's own key buffer, not the slot's)
-        std::swap(pair->d_key, pair->alt_key);
-    };
-    hipStream_t keep = pair->ctx->stream;
-    if (slot == 1) swap_slot();
-    if (hip_stream) pair->ctx->stream = static_cast<hipStream_t>(hip_stream);
-    rc = launch_ransac_score(pair, *p, h0, count, reinterpret_cast<unsigned long long *>(d_key_out));
-    pair->ctx->stream = keep;
-    if (slot == 1) swap_slot();
-    pair->state.last_count = 0;                   // the candidates / counts of a slot are not what the plain getters describe
-    return rc;
+    if (slot == 1) pair->state.key_clean = false;      // (the flag describes slot[0]'s key: a launch on slot 1 clears its key itself)
+    return launch_ransac_score(pair, pair->slot[slot], stream, *p, h0, count, reinterpret_cast<unsigned long long *>(d_key_out), nullptr, /* serial */ false);
 }
 
 // Image_pair::estimateE for a STREAM of calls: step k runs on slot k % 2 (its own stream and per-shard buffers), so that
@@ -816,7 +801,7 @@ int sfm_ransac_export_key(sfm_pair *pair, uint64_t *d_key_out)
 {
     SFM_REQUIRE(pair && d_key_out, SFM_E_INVALID, "null argument");
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
-    SFM_HIP_TRY(hipMemcpyAsync(d_key_out, pair->d_key, sizeof(uint64_t), hipMemcpyDeviceToDevice, pair->ctx->stream));
+    SFM_HIP_TRY(hipMemcpyAsync(d_key_out, pair->slot[0].key, sizeof(uint64_t), hipMemcpyDeviceToDevice, pair->ctx->stream));
     return SFM_OK;
 }
 
@@ -854,9 +839,9 @@ int sfm_estimate_E(sfm_pair *pair, const sfm_ransac_params *p)
     SFM_FLUSH(pair);
     SFM_REQUIRE(count > 0, SFM_E_INVALID, "empty hypothesis range");
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
-    rc = launch_ransac_score(pair, *p, h0, count);
+    rc = launch_ransac_score(pair, pair->slot[0], pair->ctx->stream, *p, h0, count);
     if (rc != SFM_OK) return rc;
-    rc = launch_ransac_finalize(pair, *p, pair->d_key, 0, true);     // arg-max stays on the device
+    rc = launch_ransac_finalize(pair, *p, pair->slot[0].key, 0, true);     // arg-max stays on the device
     if (rc == SFM_OK) pair->state.E_finalized();
     return rc;
 }
@@ -1816,10 +1801,10 @@ int sfm_pair_device_ptr(sfm_pair *pair, int which, void **d_ptr, size_t *bytes)
     case SFM_BUF_P: p = pair->d_P; b = 256; break;
     case SFM_BUF_PINV: p = pair->d_Pinv; b = 256; break;
     case SFM_BUF_POINTS: p = pair->d_points; b = (size_t)4 * pair->n * 4; break;
-    case SFM_BUF_COUNTS: p = pair->d_counts; b = (size_t)pair->state.last_count * 4; break;
+    case SFM_BUF_COUNTS: p = pair->slot[0].counts; b = (size_t)pair->state.last_count * 4; break;
     case SFM_BUF_MASK: p = pair->d_mask; b = (size_t)pair->n; break;
-    case SFM_BUF_KEY: p = pair->d_key; b = 8; break;
-    case SFM_BUF_ECAND: p = pair->d_Ecand; b = (size_t)pair->state.last_count * 36; break;
+    case SFM_BUF_KEY: p = pair->slot[0].key; b = 8; break;
+    case SFM_BUF_ECAND: p = pair->slot[0].Ecand; b = (size_t)pair->state.last_count * 36; break;
     case SFM_BUF_PIND: p = pair->d_Pind; b = 4; break;
     // the refinement's outputs (buffer_stage: NULL / 0 bytes unless they describe the current points)
     case SFM_BUF_REFINED_POSE: p = pair->d_rstate + refine_pose_offset(); b = 25 * 4; break;
@@ -1832,7 +1817,7 @@ int sfm_pair_device_ptr(sfm_pair *pair, int which, void **d_ptr, size_t *bytes)
 #if SFM_AB
     // lab bench: what the pre-filter works from (profiles/fuzz_case.py): the per-hypothesis records of the last launch (64 bytes each; 16 with the
     // per-tile rule), the bound words (bound, -, eight box words), the cell table
-    case SFM_AB_BUF_PF_RECORDS: p = pair->d_pf; b = (size_t)pair->state.last_count * 64; break;
+    case SFM_AB_BUF_PF_RECORDS: p = pair->slot[0].pf; b = (size_t)pair->state.last_count * 64; break;
     case SFM_AB_BUF_BOUND_WORDS: p = pair->d_bound; b = 10 * sizeof(unsigned long long); break;
     case SFM_AB_BUF_CELLS: p = pair->d_cells; b = pair->d_cells ? ((size_t)pair->cells_mask + 1) * sizeof(uint32_t) : 0; break;
 #endif
@@ -1878,7 +1863,7 @@ int sfm_get_best(sfm_pair *pair, uint32_t *hyp, uint32_t *count)
 int sfm_get_key(sfm_pair *pair, uint64_t *key)
 {
     SFM_REQUIRE(pair && key, SFM_E_INVALID, "null argument");
-    return copy_out(pair, key, pair->d_key, 8);
+    return copy_out(pair, key, pair->slot[0].key, 8);
 }
 
 int sfm_get_inlier_counts(sfm_pair *pair, int32_t *h_counts, size_t capacity)
@@ -1886,7 +1871,7 @@ int sfm_get_inlier_counts(sfm_pair *pair, int32_t *h_counts, size_t capacity)
     SFM_REQUIRE(pair && h_counts, SFM_E_INVALID, "null argument");
     SFM_REQUIRE(capacity >= pair->state.last_count, SFM_E_INVALID, "capacity %zu < %u hypotheses", capacity, pair->state.last_count);
     if (pair->state.last_count == 0) return SFM_OK;
-    return copy_out(pair, h_counts, pair->d_counts, (size_t)pair->state.last_count * 4);
+    return copy_out(pair, h_counts, pair->slot[0].counts, (size_t)pair->state.last_count * 4);
 }
 
 int sfm_get_E_candidates(sfm_pair *pair, float *h_E, size_t capacity_hyps)
@@ -1894,7 +1879,7 @@ int sfm_get_E_candidates(sfm_pair *pair, float *h_E, size_t capacity_hyps)
     SFM_REQUIRE(pair && h_E, SFM_E_INVALID, "null argument");
     SFM_REQUIRE(capacity_hyps >= pair->state.last_count, SFM_E_INVALID, "capacity too small");
     if (pair->state.last_count == 0) return SFM_OK;
-    return copy_out(pair, h_E, pair->d_Ecand, (size_t)pair->state.last_count * 36);
+    return copy_out(pair, h_E, pair->slot[0].Ecand, (size_t)pair->state.last_count * 36);
 }
 
 int sfm_get_inlier_mask(sfm_pair *pair, uint8_t *h_mask)

@@ -236,6 +236,23 @@ inline int allow_big_lds(sfm_ctx *ctx, const void *kernel)
     return SFM_OK;
 }
 
+// The per-shard buffers of a scoring launch, grown on demand (ransac.hip: ensure_hyp_capacity) -- except the key, which the pair
+// allocates.  A launch is handed ONE of the pair's two and the stream it goes to; it touches no other.
+struct ShardSlot {
+    int *counts = nullptr;
+    uint32_t *tick = nullptr;          // pre-filter kernel: per 32-hypothesis group, how many tiles have been added
+    float *Ecand = nullptr;
+    void *pf = nullptr;                // pre-filter kernel: one PfRecord (64 bytes, prefilter_record.hpp) per hypothesis of the shard
+    unsigned long long *key = nullptr; // [0] packed best of the slot's last score, [1] scratch
+    size_t cap_hyps = 0;
+};
+
+inline void shard_slot_free(ShardSlot &s)
+{
+    for (void *b : { (void *)s.counts, (void *)s.tick, (void *)s.Ecand, s.pf, (void *)s.key }) if (b) (void)hipFree(b);
+    s = ShardSlot();
+}
+
 struct sfm_pair {
     sfm_ctx *ctx = nullptr;
     int image_count = 2;
@@ -261,15 +278,13 @@ struct sfm_pair {
     int   *d_Pind = nullptr;           // chosen index (+ 4 cheirality vote counters)
     float *d_points = nullptr;         // 4 x n
     uint8_t *d_mask = nullptr;         // n
-    unsigned long long *d_key = nullptr;   // [0] packed best of last score, [1] scratch
     uint32_t *d_best = nullptr;        // [0] hyp, [1] count of the finalized hypothesis
     // [8 ...]: trace of the last pre-filter scoring launch, kTraceWords per block (sfm_ransac_last_trace)
     unsigned long long *d_clk = nullptr;   // [0] shader-clock ticks, [1] 100 MHz ticks over block 0 of the last ransac_score_waves launch
-    // per-shard buffers, grown on demand
-    int   *d_counts = nullptr;
-    uint32_t *d_tick = nullptr;        // pre-filter kernel: per 32-hypothesis group, how many tiles have been added
-    float *d_Ecand = nullptr;
-    void *d_pf = nullptr;              // pre-filter kernel: one PfRecord (64 bytes, prefilter_record.hpp) per hypothesis of the shard
+    // slot[0]: the serial calls' per-shard buffers (what the getters and a finalize of the pair's own key read), its key allocated with
+    // the pair.  slot[1]: sfm_ransac_score_into_slot's second set -- two shards in flight on two streams -- its key allocated by the first
+    // such call.  The fused / MFMA families reduce into the slot's key, then copy to the caller's.
+    ShardSlot slot[2];
     unsigned long long *d_bound = nullptr; // (fillXU epoch << 32) | bits of the largest |coordinate| <= 48 over all points: atomicMax, never reset;
                                            // words 2..9: the same for the coordinate ranges of the two views (pf_cells_build_kernel; prefilter_math.hpp: pf_box_from_words)
     uint32_t bound_epoch = 0;
@@ -277,18 +292,10 @@ struct sfm_pair {
     hipEvent_t cells_ev = nullptr;     // recorded behind the build: launches on ANOTHER stream (two-slot pipelining) wait for it
     hipStream_t cells_stream = nullptr;
     uint32_t cells_cap = 0, cells_mask = 0, cells_epoch = 0;   // slots allocated / in use - 1 / the fillXU epoch the table was built for
-    size_t cap_hyps = 0;
-    uint32_t cand_h0 = 0, cand_seed = 0;   // what d_Ecand currently holds: shard start, sampler settings
+    uint32_t cand_h0 = 0, cand_seed = 0;   // what slot[0].Ecand holds after a serial score call: shard start, sampler settings
     const int32_t *cand_indices = nullptr;
     int cand_sweeps = 0;
-    bool cand_given = false;               // d_Ecand holds caller-supplied matrices (sfm_ransac_score_candidates), not tuple-derived ones
-    // second set of the per-shard buffers (sfm_ransac_score_into_slot, slot 1): two shards in flight on two streams
-    int   *alt_counts = nullptr;
-    uint32_t *alt_tick = nullptr;
-    float *alt_Ecand = nullptr;
-    void *alt_pf = nullptr;
-    unsigned long long *alt_key = nullptr;   // slot 1's internal key (the fused / MFMA families reduce into the pair's key, then copy)
-    size_t alt_cap_hyps = 0;
+    bool cand_given = false;               // slot[0].Ecand holds caller-supplied matrices (sfm_ransac_score_candidates), not tuple-derived ones
     // sfm_estimate_E_pipelined: odd steps run on this stream, even steps on the context's; one event per slot
     hipStream_t pipe_stream = nullptr;
     hipEvent_t pipe_final[2] = { nullptr, nullptr }, pipe_call = nullptr;
@@ -335,30 +342,32 @@ int pose_chain(sfm_pair *pair, int mode, float *d_record);        // sfm_pose_ch
 int lane_contexts(sfm_ctx *ctx, int n, sfm_ctx **out);
 int start_lanes_after(sfm_ctx *ctx, sfm_ctx *const *lanes, int n, hipEvent_t event);
 
-// ransac.hip
-int launch_ransac_score(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0, uint32_t count, unsigned long long *key2 = nullptr,
-                        const float *d_E_given = nullptr);
+// The scoring launchers work on the slot and the stream they are handed: none of them looks up either in the pair or the context.
+// ransac.hip.  serial: the call owns slot[0] until the caller's next one (score_shard, sfm_estimate_E), so the pair remembers what the
+// slot holds (last_count, cand_*); a call of sfm_ransac_score_into_slot leaves the pair with nothing the plain getters describe.
+int launch_ransac_score(sfm_pair *pair, ShardSlot &slot, hipStream_t stream, const sfm_ransac_params &p, uint32_t h0, uint32_t count,
+                        unsigned long long *key2 = nullptr, const float *d_E_given = nullptr, bool serial = true);
 int launch_ransac_finalize(sfm_pair *pair, const sfm_ransac_params &p, const unsigned long long *d_key, uint32_t hyp_host, bool from_key,
                            hipStream_t stream = nullptr, bool rederive = false);
 int launch_permutation_indices(sfm_ctx *ctx, int n, uint32_t seed, int32_t *d_indices);
 // ransac_prefilter.hip
 bool prefilter_usable(const sfm_pair *pair, const sfm_ransac_params &p, uint32_t count);
 int prefilter_pick_rule(sfm_pair *pair, const sfm_ransac_params &p, uint32_t count);   // the rule of this launch (kPfRuleBandTile / kPfRuleBandPack; lab bench: any), kept in pair->pf_rule
-int launch_score_prefilter(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0, uint32_t count, unsigned long long *key2);
+int launch_score_prefilter(sfm_pair *pair, ShardSlot &slot, hipStream_t stream, const sfm_ransac_params &p, uint32_t h0, uint32_t count, unsigned long long *key2);
 bool prefilter_sums_counts(const sfm_pair *pair, const sfm_ransac_params &p, uint32_t count);          // after prefilter_pick_rule: the launch sums into zeroed counts[], keys from ransac_argmax_counts
-int launch_pf_prep(sfm_pair *pair, const sfm_ransac_params &p, uint32_t count);
+int launch_pf_prep(sfm_pair *pair, ShardSlot &slot, hipStream_t stream, const sfm_ransac_params &p, uint32_t count);         // PfRecords from the slot's Ecand (paths whose solve kernel does not write them)
 int prefilter_tile_points(const sfm_pair *pair, const sfm_ransac_params &p);      // points per scoring tile of a launch on this pair
-int launch_pf_cells(sfm_pair *pair, bool want_sorted = false, int tile = 0);                                            // the pair's cell table, (re)built when the points changed        // PfRecords from d_Ecand (paths whose solve kernel does not write them)
+int launch_pf_cells(sfm_pair *pair, hipStream_t stream, bool want_sorted = false, int tile = 0);                        // the pair's cell table, (re)built when the points changed
 #if SFM_AB
 // ab/ransac_prefilter_r2.hip (the round-2 kernel: sfm_ransac_params.reserved[3] == 2)
-int launch_score_prefilter_r2(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0, uint32_t count, unsigned long long *key2);
+int launch_score_prefilter_r2(sfm_pair *pair, ShardSlot &slot, hipStream_t stream, const sfm_ransac_params &p, uint32_t h0, uint32_t count, unsigned long long *key2);
 // ab/ransac_mfma.hip (SFM_KERNEL_MFMA: E.X on the f32 matrix cores, measured slower)
-int launch_score_mfma(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0, uint32_t count);
+int launch_score_mfma(sfm_pair *pair, ShardSlot &slot, hipStream_t stream, const sfm_ransac_params &p, uint32_t h0, uint32_t count);
 int launch_prefilter_probe(sfm_ctx *ctx, const float *d_E, float thr, float B, const float pt[4], int survive_all, float *d_out);
 int launch_prefilter_band_probe(sfm_ctx *ctx, const float *d_E, float thr, float B, const float box[8], int b_safe, const float pt[4], int survive_all, float *d_out);
 #endif
 // ransac_fused.hip
-int launch_ransac_fused(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0, uint32_t count);
+int launch_ransac_fused(sfm_pair *pair, ShardSlot &slot, hipStream_t stream, const sfm_ransac_params &p, uint32_t h0, uint32_t count);
 int launch_finalize_block(sfm_pair *pair, const sfm_ransac_params &p, const unsigned long long *d_key, uint32_t hyp_host, bool from_key,
                           hipStream_t stream, bool rederive);
 

@@ -22,7 +22,7 @@ struct PairState {
     bool unit_z = false;               // every X z-coordinate is exactly 1 (fillXU with K^-1 last row (0 0 1))
     bool have_pts4 = false;            // d_pts4 describes the current points (fillXU with the unit-z layout)
     bool have_bound = false;           // d_bound describes the current points (fillXU)
-    bool key_clean = false;            // d_key is known to be zero (pair creation, fillXU): the next score launch needs no memset
+    bool key_clean = false;            // slot[0].key is known to be zero (pair creation, fillXU): the next score launch needs no memset
     uint32_t last_count = 0;           // hyp_count of the last score call
 
     bool has(uint32_t stages) const { return (have & stages) == stages; }
@@ -30,7 +30,7 @@ struct PairState {
 
     // the three ways the points change: everything computed from the old ones is stale
     void reset() { have = 0; last_count = 0; }                          // sfm_pair_reset: no points either
-    void points_filled(bool z_is_one)                                   // sfm_fill_xu: fill_xu_kernel zeroes d_key, writes the 16-byte
+    void points_filled(bool z_is_one)                                   // sfm_fill_xu: fill_xu_kernel zeroes slot[0].key, writes the 16-byte
     {                                                                   // records (they stand for the points when every z is 1) and the bound
         have = kPoints; last_count = 0;
         key_clean = true; unit_z = z_is_one; have_pts4 = z_is_one; have_bound = true;

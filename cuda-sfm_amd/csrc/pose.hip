@@ -386,7 +386,7 @@ int launch_pose_chain(sfm_pair *pair, float *d_record)
 int launch_fill_xu(sfm_pair *pair, const sfm_sift_point *d_data)
 {
     hipLaunchKernelGGL(fill_xu_kernel, dim3((pair->ld + 255) / 256), dim3(256), 0, pair->ctx->stream,
-                       d_data, pair->n, pair->ld, pair->d_Kinv, pair->d_U[0], pair->d_U[1], pair->d_X[0], pair->d_X[1], pair->d_key, pair->d_pts4,
+                       d_data, pair->n, pair->ld, pair->d_Kinv, pair->d_U[0], pair->d_U[1], pair->d_X[0], pair->d_X[1], pair->slot[0].key, pair->d_pts4,
                        pair->d_bound, ++pair->bound_epoch);
     SFM_HIP_TRY(hipGetLastError());
     return SFM_OK;

@@ -339,37 +339,42 @@ void ransac_argmax_counts(const int *__restrict__ counts, uint32_t h0, uint32_t 
 // accumulators of the pre-filter kernel: one 64-bit word per hypothesis (count | tiles arrived)
 static size_t tick_words(size_t count) { return 2 * count + 64; }
 
-static int ensure_hyp_capacity(sfm_pair *pair, size_t count)
+// room for `count` hypotheses in the slot; what is enqueued on the launch's stream may still use the old buffers
+static int ensure_hyp_capacity(ShardSlot &s, hipStream_t stream, size_t count)
 {
-    if (count <= pair->cap_hyps) return SFM_OK;
-    SFM_HIP_TRY(hipStreamSynchronize(pair->ctx->stream));
-    if (pair->d_counts) (void)hipFree(pair->d_counts);
-    if (pair->d_Ecand) (void)hipFree(pair->d_Ecand);
-    if (pair->d_tick) (void)hipFree(pair->d_tick);
-    if (pair->d_pf) (void)hipFree(pair->d_pf);
-    pair->d_counts = nullptr; pair->d_Ecand = nullptr; pair->d_tick = nullptr; pair->d_pf = nullptr; pair->cap_hyps = 0;
-    SFM_HIP_TRY(hipMalloc(&pair->d_tick, tick_words(count) * sizeof(uint32_t)));
-    SFM_HIP_TRY(hipMalloc(&pair->d_pf, count * sizeof(PfRecord)));
-    SFM_HIP_TRY(hipMalloc(&pair->d_counts, count * sizeof(int)));
-    SFM_HIP_TRY(hipMalloc(&pair->d_Ecand, count * 9 * sizeof(float)));
-    pair->cap_hyps = count;
+    if (count <= s.cap_hyps) return SFM_OK;
+    SFM_HIP_TRY(hipStreamSynchronize(stream));
+    for (void *b : { (void *)s.counts, (void *)s.Ecand, (void *)s.tick, s.pf }) if (b) (void)hipFree(b);
+    s.counts = nullptr; s.Ecand = nullptr; s.tick = nullptr; s.pf = nullptr; s.cap_hyps = 0;
+    SFM_HIP_TRY(hipMalloc(&s.tick, tick_words(count) * sizeof(uint32_t)));
+    SFM_HIP_TRY(hipMalloc(&s.pf, count * sizeof(PfRecord)));
+    SFM_HIP_TRY(hipMalloc(&s.counts, count * sizeof(int)));
+    SFM_HIP_TRY(hipMalloc(&s.Ecand, count * 9 * sizeof(float)));
+    s.cap_hyps = count;
+    return SFM_OK;
+}
+
+// the keys of a shard's complete counts[] (tile-parallel scoring, the pre-filter's summing launches)
+static int launch_argmax_counts(const ShardSlot &s, hipStream_t stream, uint32_t h0, uint32_t count, unsigned long long *key2)
+{
+    const int ablocks = (int)((count + 4095u) / 4096u);
+    hipLaunchKernelGGL(ransac_argmax_counts, dim3(ablocks < 1024 ? ablocks : 1024), dim3(256), 0, stream, s.counts, h0, count, s.key, key2);
+    SFM_HIP_TRY(hipGetLastError());
     return SFM_OK;
 }
 
 template <int WPB, bool UNITZ, int NH = 1, bool GRID2D = false>
-static int launch_score_t(sfm_pair *pair, uint32_t h0, uint32_t count, float thr, int tile, int ntiles, int grid, size_t lds, unsigned long long *key2)
+static int launch_score_t(sfm_pair *pair, ShardSlot &s, hipStream_t stream, uint32_t h0, uint32_t count, float thr, int tile, int ntiles, int grid, size_t lds, unsigned long long *key2)
 {
     const int rc_lds = allow_big_lds(pair->ctx, reinterpret_cast<const void *>(&ransac_score_waves<WPB, UNITZ, NH, GRID2D>));
     if (rc_lds != SFM_OK) return rc_lds;
-    hipLaunchKernelGGL((ransac_score_waves<WPB, UNITZ, NH, GRID2D>), dim3(grid, GRID2D ? ntiles : 1), dim3(WPB * 64), lds, pair->ctx->stream,
-                       pair->d_X[0], pair->d_X[1], pair->ld, pair->n, pair->d_Ecand, h0, count, thr, tile, ntiles,
-                       pair->d_counts, pair->d_key, key2, pair->d_clk);
+    hipLaunchKernelGGL((ransac_score_waves<WPB, UNITZ, NH, GRID2D>), dim3(grid, GRID2D ? ntiles : 1), dim3(WPB * 64), lds, stream,
+                       pair->d_X[0], pair->d_X[1], pair->ld, pair->n, s.Ecand, h0, count, thr, tile, ntiles,
+                       s.counts, s.key, key2, pair->d_clk);
     SFM_HIP_TRY(hipGetLastError());
     if (GRID2D) {
-        const int ablocks = (int)((count + 4095u) / 4096u);
-        hipLaunchKernelGGL(ransac_argmax_counts, dim3(ablocks < 1024 ? ablocks : 1024), dim3(256), 0, pair->ctx->stream,
-                           pair->d_counts, h0, count, pair->d_key, key2);
-        SFM_HIP_TRY(hipGetLastError());
+        const int rca = launch_argmax_counts(s, stream, h0, count, key2);
+        if (rca != SFM_OK) return rca;
     }
     pair->last_grid = grid * (GRID2D ? ntiles : 1); pair->last_block = WPB * 64; pair->last_lds = (int)lds;
     return SFM_OK;
@@ -382,34 +387,33 @@ static int launch_score_t(sfm_pair *pair, uint32_t h0, uint32_t count, float thr
 // 3 = scalar, 4 = scattered gathers.
 constexpr uint32_t kScalarSolveMax = 262144u;
 
-int launch_ransac_score(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0, uint32_t count, unsigned long long *key2, const float *d_E_given)
+int launch_ransac_score(sfm_pair *pair, ShardSlot &s, hipStream_t stream, const sfm_ransac_params &p, uint32_t h0, uint32_t count,
+                        unsigned long long *key2, const float *d_E_given, bool serial)
 {
     sfm_ctx *ctx = pair->ctx;
-    // which kernel family: decided first, because the lane-solve kernel of the SPLIT family clears the keys itself
-    const uint32_t fused_max_early = p.jacobi_sweeps > 0 ? 4096u : 1024u;
-    int family = p.kernel == SFM_KERNEL_AUTO ? (count <= fused_max_early ? SFM_KERNEL_FUSED : SFM_KERNEL_SPLIT) : p.kernel;
-    if (d_E_given && family == SFM_KERNEL_FUSED) family = SFM_KERNEL_SPLIT;      // the fused kernel solves its own candidates
-    const bool self_clearing = !d_E_given && count > 0 && (family == SFM_KERNEL_SPLIT || family == SFM_KERNEL_PREFILTER);
-    if (!self_clearing) {
-        if (!pair->state.key_clean) SFM_HIP_TRY(hipMemsetAsync(pair->d_key, 0, 2 * sizeof(unsigned long long), ctx->stream));    // (fillXU leaves it cleared)
-        if (key2) SFM_HIP_TRY(hipMemsetAsync(key2, 0, sizeof(unsigned long long), ctx->stream));
-    }
-    pair->state.key_clean = false;
-    pair->state.last_count = count;
-    pair->cand_h0 = h0; pair->cand_seed = p.seed; pair->cand_indices = p.d_indices; pair->cand_sweeps = p.jacobi_sweeps;
-    pair->cand_given = d_E_given != nullptr;
-    if (count == 0) return SFM_OK;
-    int rc = ensure_hyp_capacity(pair, count);
-    if (rc != SFM_OK) return rc;
-
+    // which kernel family: decided first, because the lane-solve kernel of the SPLIT family clears the keys itself.
     // AUTO: few hypotheses are latency-bound -> one hypothesis per wavefront (fused, all waves start
     // at once); many hypotheses are throughput-bound -> lane-parallel solve + wavefront scoring.
     // Crossovers measured with profiles/small_h_bench.py: between 4k and 8k hypotheses with the Jacobi solver,
     // between 1k and 4k with the (much cheaper) Householder solver.
     const uint32_t fused_max = p.jacobi_sweeps > 0 ? 4096u : 1024u;
     int kernel = p.kernel == SFM_KERNEL_AUTO ? (count <= fused_max ? SFM_KERNEL_FUSED : SFM_KERNEL_SPLIT) : p.kernel;
-    if (d_E_given && kernel == SFM_KERNEL_FUSED) kernel = SFM_KERNEL_SPLIT;
-    #if SFM_AB
+    if (d_E_given && kernel == SFM_KERNEL_FUSED) kernel = SFM_KERNEL_SPLIT;      // the fused kernel solves its own candidates
+    const bool self_clearing = !d_E_given && count > 0 && (kernel == SFM_KERNEL_SPLIT || kernel == SFM_KERNEL_PREFILTER);
+    if (!self_clearing) {
+        // (fillXU leaves slot[0]'s key cleared; the flag is down whenever the launch is handed slot[1])
+        if (!pair->state.key_clean) SFM_HIP_TRY(hipMemsetAsync(s.key, 0, 2 * sizeof(unsigned long long), stream));
+        if (key2) SFM_HIP_TRY(hipMemsetAsync(key2, 0, sizeof(unsigned long long), stream));
+    }
+    pair->state.key_clean = false;
+    pair->state.last_count = serial ? count : 0;      // the candidates / counts of a slot call are not what the plain getters describe
+    pair->cand_given = serial && d_E_given != nullptr;
+    if (serial) { pair->cand_h0 = h0; pair->cand_seed = p.seed; pair->cand_indices = p.d_indices; pair->cand_sweeps = p.jacobi_sweeps; }
+    if (count == 0) return SFM_OK;
+    int rc = ensure_hyp_capacity(s, stream, count);
+    if (rc != SFM_OK) return rc;
+
+#if SFM_AB
     if (kernel == SFM_KERNEL_MFMA && pair->n >= 65536) kernel = SFM_KERNEL_SPLIT;   // its packed counters are 16-bit
 #endif
     // matrix-core pre-filter in front of the exact test (ransac_prefilter.hip): AUTO takes it whenever it applies
@@ -419,8 +423,8 @@ int launch_ransac_score(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0,
     if (p.kernel == SFM_KERNEL_AUTO && kernel == SFM_KERNEL_SPLIT && prefilter_usable(pair, p, count) && SFM_SW(p, 3) != 1) kernel = SFM_KERNEL_PREFILTER;
     pair->last_kernel = kernel;
     if (kernel == SFM_KERNEL_FUSED) {
-        rc = launch_ransac_fused(pair, p, h0, count);
-        if (rc == SFM_OK && key2) SFM_HIP_TRY(hipMemcpyAsync(key2, pair->d_key, sizeof(unsigned long long), hipMemcpyDeviceToDevice, ctx->stream));
+        rc = launch_ransac_fused(pair, s, stream, p, h0, count);
+        if (rc == SFM_OK && key2) SFM_HIP_TRY(hipMemcpyAsync(key2, s.key, sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream));
         return rc;
     }
 
@@ -442,7 +446,7 @@ int launch_ransac_score(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0,
 
     const bool timed = ctx->timing && ctx->tcount < sfm_ctx::kTimingSlots;
     hipEvent_t *tev = timed ? ctx->tev[ctx->tcount] : nullptr;
-    if (timed) SFM_HIP_TRY(hipEventRecord(tev[0], ctx->stream));
+    if (timed) SFM_HIP_TRY(hipEventRecord(tev[0], stream));
     const bool pf_tickets = prefilter && (SFM_SW(p, 3) == 2 || SFM_SW(p, 3) == 17);      // (AB build: kernels that sum into counts[] and draw tickets)
     const bool pf_r2 = prefilter && SFM_SW(p, 3) == 2;                   // (AB build) the round-2 kernel: builds its operands itself
     PfScales pf_sc = {};
@@ -451,7 +455,7 @@ int launch_ransac_score(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0,
         // which rule this call runs (per-tile constants over an ordered copy of the correspondences, or -- the first call after a
         // fillXU -- per-hypothesis operands): decided once, remembered in the pair for the launches below
         const int pf_rule = prefilter_pick_rule(pair, p, count);
-        const int rcc = launch_pf_cells(pair, pf_rule == kPfRuleBandTile, prefilter_tile_points(pair, p));
+        const int rcc = launch_pf_cells(pair, stream, pf_rule == kPfRuleBandTile, prefilter_tile_points(pair, p));
         if (rcc != SFM_OK) return rcc;
     }
     // pre-filter kernel, large launches (prefilter_sums_counts): every (hypothesis, tile) adds its count to counts[] and
@@ -460,57 +464,57 @@ int launch_ransac_score(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0,
     // to zeroed counts), cleared the same way.  The per-hypothesis records come from the lane-solve kernel itself on the default path,
     // from pf_prep_kernel otherwise.
     const bool pf_sums = prefilter && !pf_r2 && !pf_tickets && prefilter_sums_counts(pair, p, count);
-    int *zero_counts = (grid2d || pf_tickets || pf_sums) ? pair->d_counts : nullptr;
+    int *zero_counts = (grid2d || pf_tickets || pf_sums) ? s.counts : nullptr;
     const float4 *pts4 = (pair->state.have_pts4 && SFM_SW(p, 0) != 4) ? pair->d_pts4 : nullptr;      // (AB build, reserved[0] == 4: scattered gathers)
     const uint32_t nzero = (!prefilter || pf_sums) ? 0u : (pf_tickets ? (count + (uint32_t)kPfGroup - 1u) / (uint32_t)kPfGroup : 2u * count);
-    uint32_t *zero_ticks = (prefilter && !pf_sums) ? pair->d_tick : nullptr;
+    uint32_t *zero_ticks = (prefilter && !pf_sums) ? s.tick : nullptr;
     if (zero_ticks && d_E_given) {
-        SFM_HIP_TRY(hipMemsetAsync(pair->d_tick, 0, (size_t)nzero * sizeof(uint32_t), ctx->stream));
+        SFM_HIP_TRY(hipMemsetAsync(s.tick, 0, (size_t)nzero * sizeof(uint32_t), stream));
         zero_ticks = nullptr;
     }
     bool need_prep = prefilter && !pf_r2;
     if (d_E_given) {                 // caller-supplied candidates (sfm_ransac_score_candidates): no solve, clear what it would have cleared
-        SFM_HIP_TRY(hipMemcpyAsync(pair->d_Ecand, d_E_given, (size_t)count * 9 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-        if (zero_counts) SFM_HIP_TRY(hipMemsetAsync(pair->d_counts, 0, (size_t)count * sizeof(int), ctx->stream));
+        SFM_HIP_TRY(hipMemcpyAsync(s.Ecand, d_E_given, (size_t)count * 9 * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        if (zero_counts) SFM_HIP_TRY(hipMemsetAsync(s.counts, 0, (size_t)count * sizeof(int), stream));
     }
 #if SFM_AB
     else if (p.reserved[0] == 1 || p.reserved[0] == 7) {     // A/B switch: one hypothesis per lane, registers unconstrained / capped at 168
         auto kern = p.reserved[0] == 1 ? ransac_solve_lanes<1> : ransac_solve_lanes<3>;
-        hipLaunchKernelGGL(kern, dim3((count + 63) / 64), dim3(64), 0, ctx->stream,
+        hipLaunchKernelGGL(kern, dim3((count + 63) / 64), dim3(64), 0, stream,
                            pair->d_X[0], pair->d_X[1], pair->ld, pair->n, p.d_indices, p.seed, h0, count,
-                           p.jacobi_sweeps, pair->d_Ecand, pair->d_key, key2, zero_counts, zero_ticks, nzero);
+                           p.jacobi_sweeps, s.Ecand, s.key, key2, zero_counts, zero_ticks, nzero);
     }
 #endif
     else if (p.jacobi_sweeps <= 0 && (SFM_SW(p, 0) == 3 || (SFM_SW(p, 0) == 0 && (pts4 != nullptr || count <= kScalarSolveMax)))) {     // one hypothesis per lane
         const bool fuse = need_prep && SFM_SW(p, 3) != 3;                // (AB build, reserved[3] == 3: records from the stand-alone kernel)
         const bool tile_rec = !fuse || pair->pf_rule == kPfRuleBandTile;
-        hipLaunchKernelGGL(tile_rec ? ransac_solve_lanes1_qr : ransac_solve_lanes1_qr_rec, dim3((count + 63) / 64), dim3(64), 0, ctx->stream,
+        hipLaunchKernelGGL(tile_rec ? ransac_solve_lanes1_qr : ransac_solve_lanes1_qr_rec, dim3((count + 63) / 64), dim3(64), 0, stream,
                            pair->d_X[0], pair->d_X[1], pair->ld, pair->n, p.d_indices, p.seed, h0, count,
-                           p.jacobi_sweeps, pair->d_Ecand, pair->d_key, key2, zero_counts, zero_ticks, nzero, pts4,
-                           fuse ? reinterpret_cast<PfRecord *>(pair->d_pf) : nullptr, p.threshold, pf_sc, pair->d_bound, pair->d_cells, pair->cells_mask,
+                           p.jacobi_sweeps, s.Ecand, s.key, key2, zero_counts, zero_ticks, nzero, pts4,
+                           fuse ? reinterpret_cast<PfRecord *>(s.pf) : nullptr, p.threshold, pf_sc, pair->d_bound, pair->d_cells, pair->cells_mask,
                            pair->pf_rule);
         if (fuse) need_prep = false;
     }
     else if (p.jacobi_sweeps <= 0)   // default: two hypotheses per lane (packed math), Householder instantiation
-        hipLaunchKernelGGL(ransac_solve_lanes2<true>, dim3((count + 127) / 128), dim3(64), 0, ctx->stream,
+        hipLaunchKernelGGL(ransac_solve_lanes2<true>, dim3((count + 127) / 128), dim3(64), 0, stream,
                            pair->d_X[0], pair->d_X[1], pair->ld, pair->n, p.d_indices, p.seed, h0, count,
-                           p.jacobi_sweeps, pair->d_Ecand, pair->d_key, key2, zero_counts, zero_ticks, nzero, pts4);
+                           p.jacobi_sweeps, s.Ecand, s.key, key2, zero_counts, zero_ticks, nzero, pts4);
 #if SFM_AB
     else if (p.reserved[0] == 2)     // A/B switch: the Jacobi solver two hypotheses per lane, packed (the product's choice up to round 4)
-        hipLaunchKernelGGL(ransac_solve_lanes2<false>, dim3((count + 127) / 128), dim3(64), 0, ctx->stream,
+        hipLaunchKernelGGL(ransac_solve_lanes2<false>, dim3((count + 127) / 128), dim3(64), 0, stream,
                            pair->d_X[0], pair->d_X[1], pair->ld, pair->n, p.d_indices, p.seed, h0, count,
-                           p.jacobi_sweeps, pair->d_Ecand, pair->d_key, key2, zero_counts, zero_ticks, nzero, pts4);
+                           p.jacobi_sweeps, s.Ecand, s.key, key2, zero_counts, zero_ticks, nzero, pts4);
 #endif
     else                             // normal equations + Jacobi: one hypothesis per lane, two wavefronts per SIMD
-        hipLaunchKernelGGL(ransac_solve_lanes<2>, dim3((count + 63) / 64), dim3(64), 0, ctx->stream,
+        hipLaunchKernelGGL(ransac_solve_lanes<2>, dim3((count + 63) / 64), dim3(64), 0, stream,
                            pair->d_X[0], pair->d_X[1], pair->ld, pair->n, p.d_indices, p.seed, h0, count,
-                           p.jacobi_sweeps, pair->d_Ecand, pair->d_key, key2, zero_counts, zero_ticks, nzero);
+                           p.jacobi_sweeps, s.Ecand, s.key, key2, zero_counts, zero_ticks, nzero);
     SFM_HIP_TRY(hipGetLastError());
     if (need_prep) {
-        const int rcp = launch_pf_prep(pair, p, count);
+        const int rcp = launch_pf_prep(pair, s, stream, p, count);
         if (rcp != SFM_OK) return rcp;
     }
-    if (timed) SFM_HIP_TRY(hipEventRecord(tev[1], ctx->stream));
+    if (timed) SFM_HIP_TRY(hipEventRecord(tev[1], stream));
 
     // unit-z layout: fixed 64 KiB (two arrays of kTileMax/2 pair records); generic: 24 B per point
     const bool uz = pair->state.unit_z;
@@ -533,43 +537,38 @@ int launch_ransac_score(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0,
     }
     if (prefilter) {
 #if SFM_AB
-        if (pf_r2) rc = launch_score_prefilter_r2(pair, p, h0, count, key2);
+        if (pf_r2) rc = launch_score_prefilter_r2(pair, s, stream, p, h0, count, key2);
         else
 #endif
-        rc = launch_score_prefilter(pair, p, h0, count, key2);      // (lab bench: the earlier epilogues make the keys themselves)
-        if (rc == SFM_OK && pf_sums) {                              // the keys of the complete counts, in front of whatever the caller enqueues next
-            const int ablocks = (int)((count + 4095u) / 4096u);
-            hipLaunchKernelGGL(ransac_argmax_counts, dim3(ablocks < 1024 ? ablocks : 1024), dim3(256), 0, ctx->stream,
-                               pair->d_counts, h0, count, pair->d_key, key2);
-            SFM_HIP_TRY(hipGetLastError());
-        }
+        rc = launch_score_prefilter(pair, s, stream, p, h0, count, key2);      // (lab bench: the earlier epilogues make the keys themselves)
+        if (rc == SFM_OK && pf_sums) rc = launch_argmax_counts(s, stream, h0, count, key2);      // in front of whatever the caller enqueues next
     }
 #if SFM_AB
     else if (kernel == SFM_KERNEL_MFMA) {
-        rc = launch_score_mfma(pair, p, h0, count);
-        if (rc == SFM_OK && key2) SFM_HIP_TRY(hipMemcpyAsync(key2, pair->d_key, sizeof(unsigned long long), hipMemcpyDeviceToDevice, ctx->stream));
+        rc = launch_score_mfma(pair, s, stream, p, h0, count);
+        if (rc == SFM_OK && key2) SFM_HIP_TRY(hipMemcpyAsync(key2, s.key, sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream));
     }
 #endif
     else if (grid2d) {
-        rc = uz ? (nh == 2 ? launch_score_t<16, true, 2, true>(pair, h0, count, p.threshold, tile, ntiles, grid, lds, key2)
-                           : launch_score_t<16, true, 1, true>(pair, h0, count, p.threshold, tile, ntiles, grid, lds, key2))
-                : (nh == 2 ? launch_score_t<16, false, 2, true>(pair, h0, count, p.threshold, tile, ntiles, grid, lds, key2)
-                           : launch_score_t<16, false, 1, true>(pair, h0, count, p.threshold, tile, ntiles, grid, lds, key2));
+        rc = uz ? (nh == 2 ? launch_score_t<16, true, 2, true>(pair, s, stream, h0, count, p.threshold, tile, ntiles, grid, lds, key2)
+                           : launch_score_t<16, true, 1, true>(pair, s, stream, h0, count, p.threshold, tile, ntiles, grid, lds, key2))
+                : (nh == 2 ? launch_score_t<16, false, 2, true>(pair, s, stream, h0, count, p.threshold, tile, ntiles, grid, lds, key2)
+                           : launch_score_t<16, false, 1, true>(pair, s, stream, h0, count, p.threshold, tile, ntiles, grid, lds, key2));
     }
     else if (uz) switch (wpb) {
-    case 16: rc = nh == 2 ? launch_score_t<16, true, 2>(pair, h0, count, p.threshold, tile, ntiles, grid, lds, key2)
-                          : launch_score_t<16, true>(pair, h0, count, p.threshold, tile, ntiles, grid, lds, key2); break;
-    case 8:  rc = launch_score_t<8, true>(pair, h0, count, p.threshold, tile, ntiles, grid, lds, key2); break;
-    default: rc = launch_score_t<4, true>(pair, h0, count, p.threshold, tile, ntiles, grid, lds, key2); break;
+    case 16: rc = nh == 2 ? launch_score_t<16, true, 2>(pair, s, stream, h0, count, p.threshold, tile, ntiles, grid, lds, key2)
+                          : launch_score_t<16, true>(pair, s, stream, h0, count, p.threshold, tile, ntiles, grid, lds, key2); break;
+    case 8:  rc = launch_score_t<8, true>(pair, s, stream, h0, count, p.threshold, tile, ntiles, grid, lds, key2); break;
+    default: rc = launch_score_t<4, true>(pair, s, stream, h0, count, p.threshold, tile, ntiles, grid, lds, key2); break;
     }
     else switch (wpb) {
-    case 16: rc = nh == 2 ? launch_score_t<16, false, 2>(pair, h0, count, p.threshold, tile, ntiles, grid, lds, key2)
-                          : launch_score_t<16, false>(pair, h0, count, p.threshold, tile, ntiles, grid, lds, key2); break;
-    case 8:  rc = launch_score_t<8, false>(pair, h0, count, p.threshold, tile, ntiles, grid, lds, key2); break;
-    default: rc = launch_score_t<4, false>(pair, h0, count, p.threshold, tile, ntiles, grid, lds, key2); break;
+    case 16: rc = nh == 2 ? launch_score_t<16, false, 2>(pair, s, stream, h0, count, p.threshold, tile, ntiles, grid, lds, key2)
+                          : launch_score_t<16, false>(pair, s, stream, h0, count, p.threshold, tile, ntiles, grid, lds, key2); break;
+    case 8:  rc = launch_score_t<8, false>(pair, s, stream, h0, count, p.threshold, tile, ntiles, grid, lds, key2); break;
+    default: rc = launch_score_t<4, false>(pair, s, stream, h0, count, p.threshold, tile, ntiles, grid, lds, key2); break;
     }
     if (rc == SFM_OK && timed) {
-        SFM_HIP_TRY(hipEventRecord(tev[2], ctx->stream));
+        SFM_HIP_TRY(hipEventRecord(tev[2], stream));
         ctx->tcount++;
     }
     return rc;

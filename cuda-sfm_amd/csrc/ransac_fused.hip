@@ -386,19 +386,19 @@ void ransac_finalize_block(const float *__restrict__ X0, const float *__restrict
 }
 
 template <int WPB, bool UNITZ>
-static int launch_fused_t(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0, uint32_t count, int tile, int ntiles, int grid, size_t lds)
+static int launch_fused_t(sfm_pair *pair, ShardSlot &s, hipStream_t stream, const sfm_ransac_params &p, uint32_t h0, uint32_t count, int tile, int ntiles, int grid, size_t lds)
 {
     const int rc_lds = allow_big_lds(pair->ctx, reinterpret_cast<const void *>(&ransac_fused_waves<WPB, UNITZ>));
     if (rc_lds != SFM_OK) return rc_lds;
-    hipLaunchKernelGGL((ransac_fused_waves<WPB, UNITZ>), dim3(grid), dim3(WPB * 64), lds, pair->ctx->stream,
+    hipLaunchKernelGGL((ransac_fused_waves<WPB, UNITZ>), dim3(grid), dim3(WPB * 64), lds, stream,
                        pair->d_X[0], pair->d_X[1], pair->ld, pair->n, p.d_indices, p.seed, p.jacobi_sweeps,
-                       h0, count, p.threshold, tile, ntiles, pair->d_counts, pair->d_Ecand, pair->d_key);
+                       h0, count, p.threshold, tile, ntiles, s.counts, s.Ecand, s.key);
     SFM_HIP_TRY(hipGetLastError());
     pair->last_grid = grid; pair->last_block = WPB * 64; pair->last_lds = (int)lds;
     return SFM_OK;
 }
 
-int launch_ransac_fused(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0, uint32_t count)
+int launch_ransac_fused(sfm_pair *pair, ShardSlot &s, hipStream_t stream, const sfm_ransac_params &p, uint32_t h0, uint32_t count)
 {
     sfm_ctx *ctx = pair->ctx;
     const int tile = pair->ld < kTileMax ? pair->ld : kTileMax;
@@ -412,13 +412,13 @@ int launch_ransac_fused(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0,
                        9 * 64 * sizeof(uint2);                                                          // tile + wave scratches + Jacobi schedule
     const bool timed = ctx->timing && ctx->tcount < sfm_ctx::kTimingSlots;
     hipEvent_t *tev = timed ? ctx->tev[ctx->tcount] : nullptr;
-    if (timed) { SFM_HIP_TRY(hipEventRecord(tev[0], ctx->stream)); SFM_HIP_TRY(hipEventRecord(tev[1], ctx->stream)); }
+    if (timed) { SFM_HIP_TRY(hipEventRecord(tev[0], stream)); SFM_HIP_TRY(hipEventRecord(tev[1], stream)); }
     int rc;
     switch (wpb) {
-    case 8:  rc = uz ? launch_fused_t<8, true>(pair, p, h0, count, tile, ntiles, grid, lds) : launch_fused_t<8, false>(pair, p, h0, count, tile, ntiles, grid, lds); break;
-    default: rc = uz ? launch_fused_t<4, true>(pair, p, h0, count, tile, ntiles, grid, lds) : launch_fused_t<4, false>(pair, p, h0, count, tile, ntiles, grid, lds); break;
+    case 8:  rc = uz ? launch_fused_t<8, true>(pair, s, stream, p, h0, count, tile, ntiles, grid, lds) : launch_fused_t<8, false>(pair, s, stream, p, h0, count, tile, ntiles, grid, lds); break;
+    default: rc = uz ? launch_fused_t<4, true>(pair, s, stream, p, h0, count, tile, ntiles, grid, lds) : launch_fused_t<4, false>(pair, s, stream, p, h0, count, tile, ntiles, grid, lds); break;
     }
-    if (rc == SFM_OK && timed) { SFM_HIP_TRY(hipEventRecord(tev[2], ctx->stream)); ctx->tcount++; }
+    if (rc == SFM_OK && timed) { SFM_HIP_TRY(hipEventRecord(tev[2], stream)); ctx->tcount++; }
     return rc;
 }
 
@@ -432,7 +432,7 @@ int launch_finalize_block(sfm_pair *pair, const sfm_ransac_params &p, const unsi
     hipLaunchKernelGGL(ransac_finalize_block, dim3(1), dim3(1024), 0, stream,
                        pair->d_X[0], pair->d_X[1], pair->ld, pair->n, p.d_indices, p.seed, p.jacobi_sweeps,
                        d_key, hyp_host, from_key ? 1 : 0,
-                       cand_ok ? pair->d_Ecand : nullptr, pair->cand_h0, pair->state.last_count, p.num_hypotheses,
+                       cand_ok ? pair->slot[0].Ecand : nullptr, pair->cand_h0, pair->state.last_count, p.num_hypotheses,
                        p.threshold, pair->d_E, pair->d_mask, pair->d_best);
     SFM_HIP_TRY(hipGetLastError());
     return SFM_OK;

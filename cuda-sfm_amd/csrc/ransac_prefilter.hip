@@ -973,9 +973,8 @@ void pf_cells_build_kernel(const float4 *__restrict__ pts4, int n, unsigned long
     }
 }
 
-int launch_pf_cells(sfm_pair *pair, bool want_sorted, int tile)
+int launch_pf_cells(sfm_pair *pair, hipStream_t st, bool want_sorted, int tile)
 {
-    hipStream_t st = pair->ctx->stream;
     const bool cells_ok = pair->cells_epoch == pair->bound_epoch && pair->d_cells;                                             // built for the current points
     const bool order_ok = !want_sorted || (pair->sorted_epoch == pair->bound_epoch && pair->boxes_tile == tile && pair->d_pts4s);
     // ... possibly by a launch on another stream (the other slot of a pipelined burst): order this stream behind it
@@ -1043,23 +1042,23 @@ void pf_prep_kernel(const float *__restrict__ Ecand, uint32_t count, float thr, 
     else pf_prep_store(e, thr, B, sc, cells, cells_mask, recs + i);
 }
 
-int launch_pf_prep(sfm_pair *pair, const sfm_ransac_params &p, uint32_t count)
+int launch_pf_prep(sfm_pair *pair, ShardSlot &s, hipStream_t stream, const sfm_ransac_params &p, uint32_t count)
 {
     PfScales sc;
     if (!prefilter_scales(p.threshold, sc)) { set_error("threshold %g outside the pre-filter's range", (double)p.threshold); return SFM_E_INVALID; }
     if (pair->pf_rule == kPfRuleBandTile)
-        hipLaunchKernelGGL(pf_prep_kernel<kPfRuleBandTile>, dim3((count + 255) / 256), dim3(256), 0, pair->ctx->stream,
-                           pair->d_Ecand, count, p.threshold, sc, pair->d_bound, pair->d_cells, pair->cells_mask, reinterpret_cast<PfRecord *>(pair->d_pf));
+        hipLaunchKernelGGL(pf_prep_kernel<kPfRuleBandTile>, dim3((count + 255) / 256), dim3(256), 0, stream,
+                           s.Ecand, count, p.threshold, sc, pair->d_bound, pair->d_cells, pair->cells_mask, reinterpret_cast<PfRecord *>(s.pf));
     else if (pair->pf_rule == kPfRuleBandPack)
-        hipLaunchKernelGGL(pf_prep_kernel<kPfRuleBandPack>, dim3((count + 255) / 256), dim3(256), 0, pair->ctx->stream,
-                           pair->d_Ecand, count, p.threshold, sc, pair->d_bound, pair->d_cells, pair->cells_mask, reinterpret_cast<PfRecord *>(pair->d_pf));
+        hipLaunchKernelGGL(pf_prep_kernel<kPfRuleBandPack>, dim3((count + 255) / 256), dim3(256), 0, stream,
+                           s.Ecand, count, p.threshold, sc, pair->d_bound, pair->d_cells, pair->cells_mask, reinterpret_cast<PfRecord *>(s.pf));
 #if SFM_AB
     else if (pair->pf_rule == kPfRuleBand)
-        hipLaunchKernelGGL(pf_prep_kernel<kPfRuleBand>, dim3((count + 255) / 256), dim3(256), 0, pair->ctx->stream,
-                           pair->d_Ecand, count, p.threshold, sc, pair->d_bound, pair->d_cells, pair->cells_mask, reinterpret_cast<PfRecord *>(pair->d_pf));
+        hipLaunchKernelGGL(pf_prep_kernel<kPfRuleBand>, dim3((count + 255) / 256), dim3(256), 0, stream,
+                           s.Ecand, count, p.threshold, sc, pair->d_bound, pair->d_cells, pair->cells_mask, reinterpret_cast<PfRecord *>(s.pf));
     else
-        hipLaunchKernelGGL(pf_prep_kernel<kPfRuleG>, dim3((count + 255) / 256), dim3(256), 0, pair->ctx->stream,
-                           pair->d_Ecand, count, p.threshold, sc, pair->d_bound, pair->d_cells, pair->cells_mask, reinterpret_cast<PfRecord *>(pair->d_pf));
+        hipLaunchKernelGGL(pf_prep_kernel<kPfRuleG>, dim3((count + 255) / 256), dim3(256), 0, stream,
+                           s.Ecand, count, p.threshold, sc, pair->d_bound, pair->d_cells, pair->cells_mask, reinterpret_cast<PfRecord *>(s.pf));
 #endif
     SFM_HIP_TRY(hipGetLastError());
     return SFM_OK;
@@ -1310,7 +1309,7 @@ bool prefilter_sums_counts(const sfm_pair *pair, const sfm_ransac_params &p, uin
     return product_rule && !variant && !(pf_tail_var(pair, p, count) & kPfVarAnswerEpilogue);
 }
 
-int launch_score_prefilter(sfm_pair *pair, const sfm_ransac_params &p, uint32_t h0, uint32_t count, unsigned long long *key2)
+int launch_score_prefilter(sfm_pair *pair, ShardSlot &s, hipStream_t stream, const sfm_ransac_params &p, uint32_t h0, uint32_t count, unsigned long long *key2)
 {
     sfm_ctx *ctx = pair->ctx;
     PfScales sc;
@@ -1343,9 +1342,9 @@ int launch_score_prefilter(sfm_pair *pair, const sfm_ransac_params &p, uint32_t 
         const int rc_lds = allow_big_lds(ctx, reinterpret_cast<const void *>(kernel));
         if (rc_lds != SFM_OK) return rc_lds;
         const float *x0 = rule == kPfRuleBandTile ? reinterpret_cast<const float *>(pair->d_pts4s) : pair->d_X[0];
-        hipLaunchKernelGGL(kernel, dim3(cols, ntiles), dim3(waves * 64), lds_bytes, ctx->stream,
-                           x0, pair->d_X[1], pair->ld, pair->n, pair->d_Ecand, reinterpret_cast<const PfRecord *>(pair->d_pf), h0, count, p.threshold,
-                           dynamic, tile, pair->d_counts, pair->d_tick, pair->d_key, key2, pair->d_clk, pair->d_bound, pair->d_tile_boxes);
+        hipLaunchKernelGGL(kernel, dim3(cols, ntiles), dim3(waves * 64), lds_bytes, stream,
+                           x0, pair->d_X[1], pair->ld, pair->n, s.Ecand, reinterpret_cast<const PfRecord *>(s.pf), h0, count, p.threshold,
+                           dynamic, tile, s.counts, s.tick, s.key, key2, pair->d_clk, pair->d_bound, pair->d_tile_boxes);
         return SFM_OK;
     };
     int rcl;
