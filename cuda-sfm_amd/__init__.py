@@ -87,6 +87,7 @@ EXPORTS = [
     "sfm_fuse_default_params", "sfm_fuse_chain",
     "sfm_adjust_chain_default_params", "sfm_adjust_chain",
     "sfm_ring_default_params", "sfm_close_ring", "sfm_fuse_ring_default_params", "sfm_fuse_ring",
+    "sfm_adjust_ring_default_params", "sfm_adjust_ring",
 ]
 AB_EXPORTS = ["sfm_ransac_last_phases", "sfm_ransac_last_trace", "sfm_prefilter_probe", "sfm_prefilter_band_probe"]      # include/sfm_amd_ab.h
 if AB:
@@ -272,6 +273,35 @@ class FuseRingReport(C.Structure):
                 ("seam_refined", C.c_int32), ("seam_kept", C.c_int32)]
 
 
+class AdjustRingParams(C.Structure):
+    """sfm_adjust_ring_params (include/sfm_amd.h)."""
+    _fields_ = [("max_iterations", C.c_int32), ("huber_px", C.c_float), ("min_rel_decrease", C.c_float), ("initial_lambda", C.c_float),
+                ("max_track_views", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class AdjustRingIn(C.Structure):
+    """sfm_adjust_ring_in (include/sfm_amd.h): the host array of pair handles, what sfm_fuse_ring wrote and its report."""
+    _fields_ = [("pairs", C.POINTER(C.c_void_p)), ("d_root", C.c_void_p), ("d_cams", C.c_void_p), ("d_track_offset", C.c_void_p),
+                ("d_obs_cam", C.c_void_p), ("d_obs_record", C.c_void_p), ("d_points", C.c_void_p), ("d_flags", C.c_void_p), ("d_counts", C.c_void_p),
+                ("d_ring_report", C.c_void_p)]
+
+
+class AdjustRingReport(C.Structure):
+    """sfm_adjust_ring_report (include/sfm_amd.h): one for the ring."""
+    _fields_ = [("ring_status", C.c_int32), ("status", C.c_int32), ("iterations", C.c_int32), ("accepted", C.c_int32), ("num_cameras", C.c_int32),
+                ("num_tracks", C.c_int32), ("num_seam_tracks", C.c_int32), ("num_observations", C.c_int32), ("num_over_long", C.c_int32),
+                ("initial_rms_px", C.c_float), ("final_rms_px", C.c_float), ("final_cost", C.c_float), ("lambda_", C.c_float)]
+
+
+ADJUST_RING_REPORT_DTYPE = np.dtype([(f if f != "lambda_" else "lambda", "<i4" if t is C.c_int32 else "<f4") for f, t in AdjustRingReport._fields_])
+assert ADJUST_RING_REPORT_DTYPE.itemsize == C.sizeof(AdjustRingReport)
+
+
+class AdjustRingOut(C.Structure):
+    """sfm_adjust_ring_out (include/sfm_amd.h): the caller's device buffers."""
+    _fields_ = [("d_cams", C.c_void_p), ("d_points", C.c_void_p), ("d_used", C.c_void_p), ("d_err", C.c_void_p), ("d_report", C.c_void_p)]
+
+
 FUSE_COUNTS = ("tracks", "observations", "refined", "kept", "segments", "longest_track")      # sfm_fuse_out.d_counts[0..5]
 
 _vp = C.c_void_p
@@ -378,6 +408,9 @@ _lib.sfm_ring_default_params.restype = None
 _lib.sfm_close_ring.argtypes = [_vp, C.POINTER(RingLinkIn), C.c_int, C.POINTER(FusePairIn), C.POINTER(RingParams), C.POINTER(RingOut)]
 _lib.sfm_fuse_ring_default_params.argtypes = [C.POINTER(FuseRingParams)]
 _lib.sfm_fuse_ring_default_params.restype = None
+_lib.sfm_adjust_ring_default_params.argtypes = [C.POINTER(AdjustRingParams)]
+_lib.sfm_adjust_ring_default_params.restype = None
+_lib.sfm_adjust_ring.argtypes = [_vp, C.POINTER(AdjustRingIn), C.c_int, C.POINTER(AdjustRingParams), C.POINTER(AdjustRingOut)]
 _lib.sfm_fuse_ring.argtypes = [_vp, C.POINTER(FusePairIn), C.c_int, C.POINTER(FuseLinkIn), C.POINTER(FuseRingParams), C.POINTER(FuseOut), _vp]
 _lib.sfm_fuse_chain.argtypes = [_vp, C.POINTER(FusePairIn), C.c_int, C.POINTER(FuseLinkIn), C.POINTER(FuseParams), C.POINTER(FuseOut)]
 if AB:
@@ -982,6 +1015,68 @@ def adjust_chain(pairs, fused, **kw):
     adjust_chain_enqueue(ctx, pairs, (root, cams, off, ocam, orec, pts, flags, counts), params, outs)
     ctx.synchronize()
     return adjust_chain_results(outs, k, N, int(counts[0].item()))
+
+
+_ADJUST_RING_FIELDS = {f for f, _ in AdjustRingParams._fields_}
+
+
+def adjust_ring_params(**kw):
+    """sfm_adjust_ring_params with the library's defaults (sfm_adjust_chain's: 10 iterations, Huber 1 px, 1e-6, lambda 1e-3, tracks of
+    at most 8 views), fields overridden by kw."""
+    p = AdjustRingParams()
+    _lib.sfm_adjust_ring_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "reserved":
+            for i, x in enumerate(v):
+                p.reserved[i] = int(x)
+        elif k in _ADJUST_RING_FIELDS:
+            setattr(p, k, v)
+        else:
+            raise TypeError(f"adjust_ring_params: no field {k!r} in sfm_adjust_ring_params")
+    return p
+
+
+def adjust_ring_enqueue(ctx, pairs, fused, params, outs):
+    """sfm_adjust_ring (enqueue only).  pairs: the ImagePairs of the ring; fused: device tensors / pointers (root, cams, track_offset,
+    obs_cam, obs_record, points, flags, counts, ring_report) that fuse_ring_enqueue filled; outs: device tensors / pointers in the
+    order of sfm_adjust_ring_out (err may be None), the report as ADJUST_RING_REPORT_DTYPE.itemsize bytes."""
+    k = len(pairs)
+    handles = (C.c_void_p * max(k, 1))(*[p._h.value if p is not None else None for p in pairs])
+    i = AdjustRingIn(C.cast(handles, C.POINTER(C.c_void_p)), *[_ptr(t) for t in fused]) if fused is not None else None
+    o = AdjustRingOut(*[_ptr(t) for t in outs]) if outs is not None else None
+    _check(_lib.sfm_adjust_ring(ctx._h if ctx is not None else None, C.byref(i) if i is not None else None, k,
+                                C.byref(params) if params is not None else None, C.byref(o) if o is not None else None), "sfm_adjust_ring")
+
+
+def adjust_ring_buffers(device, k, N):
+    """Output tensors of one adjust_ring call in the order of sfm_adjust_ring_out, for k pairs with N records in all."""
+    e = lambda n, dt: torch.empty(int(n), dtype=dt, device=device)
+    return (e(24 * k, torch.float32), e(4 * N, torch.float32), e(N, torch.uint8), e(N, torch.float32),
+            e(ADJUST_RING_REPORT_DTYPE.itemsize, torch.uint8))
+
+
+def adjust_ring_results(outs, k, N, T):
+    """The tensors of adjust_ring_buffers -> a dict of numpy arrays trimmed to the T tracks: cams (k, 2, 12), points (4, T), used (T),
+    err (T), report (one record of ADJUST_RING_REPORT_DTYPE)."""
+    cams, pts, used, err, rep = (t.cpu().numpy() for t in outs)
+    return dict(cams=cams.reshape(k, 2, 12), points=pts.reshape(4, N)[:, :T].copy(), used=used[:T].copy(), err=err[:T].copy(),
+                report=rep.view(ADJUST_RING_REPORT_DTYPE)[0].copy())
+
+
+def adjust_ring(pairs, fused, ring_report, **kw):
+    """One bundle adjustment over a CLOSED ring, seam tracks included, one camera per view.  pairs: the ImagePairs of the ring; fused:
+    the device tensors of a fuse_ring_enqueue call in the order of sfm_fuse_out; ring_report: the device bytes sfm_fuse_ring wrote;
+    kw are AdjustRingParams fields.  Allocates the outputs, waits once and returns adjust_ring_results' dict."""
+    params = adjust_ring_params(**kw)
+    k = len(pairs)
+    ctx = pairs[0].ctx if k else None
+    dev = torch.device("cuda", ctx.device) if k else None
+    N = sum(p.num_points for p in pairs)
+    frames, root, cams, track, off, ocam, orec, pts, flags, err, counts = fused
+    outs = adjust_ring_buffers(dev, k, N) if k else None
+    adjust_ring_enqueue(ctx, pairs, (root, cams, off, ocam, orec, pts, flags, counts, ring_report), params, outs)
+    ctx.synchronize()
+    return adjust_ring_results(outs, k, N, int(counts[0].item()))
 
 
 def sift_temp_layout(width, height, num_octaves=5, scale_up=False):

@@ -210,7 +210,7 @@ struct sfm_ctx {
     sfm::JobArray refine_jobs, register_jobs, view_points_jobs, adjust_jobs, align_jobs, fuse_jobs, chain_jobs, ring_jobs;
     void *fuse_ws = nullptr;           // sfm_fuse_chain: per-node keys, successors, path lengths and classes, the block counts (fuse.hip)
     size_t fuse_ws_bytes = 0;
-    void *chain_ws = nullptr;          // sfm_adjust_chain: states, points, partial bands, the band and the segments (chain_adjust.hip)
+    void *chain_ws = nullptr;          // sfm_adjust_chain and sfm_adjust_ring: states, points, partial bands, the band and the segments (chain_adjust.hip)
     size_t chain_ws_bytes = 0;
     void *ring_ws = nullptr;           // sfm_close_ring: the fp64 frames, weights and running sums, the seam's block partials (ring.hip)
     size_t ring_ws_bytes = 0;
@@ -438,6 +438,9 @@ int launch_fuse_ring(sfm_ctx *ctx, const FusePair *pairs, int num_pairs, const s
 // chain_adjust.hip: one bundle adjustment over a fused chain; pairs: HOST array (X0, X1, K, n, ld resolved by the caller)
 int launch_adjust_chain(sfm_ctx *ctx, const FusePair *pairs, int num_pairs, const sfm_adjust_chain_in &in, const sfm_adjust_chain_params &p,
                         const sfm_adjust_chain_out &out);
+// ring_adjust.hip: the same over a CLOSED ring, one camera per view (the chain's job array and work buffer)
+int launch_adjust_ring(sfm_ctx *ctx, const FusePair *pairs, int num_pairs, const sfm_adjust_ring_in &in, const sfm_adjust_ring_params &p,
+                       const sfm_adjust_ring_out &out);
 
 // ring.hip: the drift of a ring measured and spread over its links; links: HOST array, last: pair k - 1 (points, valid, X1, K, n, ld
 // resolved by the caller)

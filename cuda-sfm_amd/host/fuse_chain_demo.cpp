@@ -13,7 +13,9 @@
 // One `fuse:` line, then the fused cloud of the first segment -- one point per track, where align_pairs_demo writes a feature
 // once per pair that sees it -- as a PLY (default fused_cloud.ply).  With adjust_iterations > 0 (default 0: nothing changes) one
 // SfM::adjust_chain over the fused model follows, one `chain adjust:` line per segment is printed and the PLY holds the adjusted
-// points.  Plain C++: needs only the facade headers and libsfm_amd.so.
+// points.  With `loop`, adjust_iterations > 0 and a ring that closed, SfM::adjust_ring follows as well (one camera per view, the
+// seam tracks used): one `ring adjust:` line behind the `chain adjust:` lines, and the PLY holds ITS points.
+// Plain C++: needs only the facade headers and libsfm_amd.so.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -124,6 +126,13 @@ int main(int argc, char **argv)
                         rep.num_tracks, (double)rep.initial_rms_px, (double)rep.final_rms_px, rep.iterations);
         }
         points = adj.points;
+        if (loop && fused.report.status == SFM_RING_CLOSED) {          // the ring's own adjustment: one camera per view, the seam tracks used
+            const SfM::AdjustedRing ra = SfM::adjust_ring(pairs.data(), count, fused, adjust_iterations);
+            const sfm_adjust_ring_report &rep = ra.report;
+            std::printf("ring adjust: %d cameras, %d tracks, %d seam tracks, rms %.6g -> %.6g px, %d iterations\n", rep.num_cameras, rep.num_tracks,
+                        rep.num_seam_tracks, (double)rep.initial_rms_px, (double)rep.final_rms_px, rep.iterations);
+            points = ra.points;
+        }
     }
 
     // the first segment's tracks: one point each

@@ -789,6 +789,80 @@ inline AdjustedChain adjust_chain(Image_pair *const *pairs, int count, const Fus
     return r;
 }
 
+// what adjust_ring returns, in host memory
+struct AdjustedRing {
+    std::vector<float> cams;            // 24 x count, FusedModel::cams' layout: one camera per VIEW (pair count - 1's camera 2 is pair 0's camera 1)
+    std::vector<float> points;          // 4 x T (leading dimension T)
+    std::vector<uint8_t> used;          // T: the track took part (seam tracks included)
+    std::vector<float> err;             // T: largest pixel error over the track's views under the returned cameras
+    sfm_adjust_ring_report report;
+};
+
+// One bundle adjustment over a CLOSED ring, seam tracks included, view 0 fixed (sfm_adjust_ring): pairs, count: what fuse_ring
+// took; ring: what it returned.  A ring that is not SFM_RING_CLOSED comes back as it went in (report.ring_status says so): adjust
+// such a model by adjust_chain.  The model is uploaded again; one wait at the end.
+inline AdjustedRing adjust_ring(Image_pair *const *pairs, int count, const FusedRing &ring, int max_iterations = 10, int max_track_views = 8)
+{
+    AdjustedRing r;
+    memset(&r.report, 0, sizeof(r.report));
+    const FusedModel &model = ring.model;
+    sfm_ctx *ctx = sfm_facade::context();
+    sfm_adjust_ring_params p;
+    sfm_adjust_ring_default_params(&p);
+    p.max_iterations = max_iterations;
+    p.max_track_views = max_track_views;
+    std::vector<sfm_pair *> handles;
+    size_t N = 0;
+    for (int i = 0; i < count; ++i) { handles.push_back(pairs[i] ? pairs[i]->handle() : nullptr); N += pairs[i] ? (size_t)pairs[i]->numPoints() : 0; }
+    const size_t k = (size_t)(count > 0 ? count : 0), T = (size_t)model.tracks, M = (size_t)model.observations;
+    // inputs and outputs in ONE block, every array at a multiple of 16 bytes
+    auto up = [](size_t b) { return (b + 15) / 16 * 16; };
+    const size_t sizes[14] = { 4 * k, 96 * k, 4 * (N + 1), 8 * N, 8 * N, 16 * N, N, 32, sizeof(sfm_fuse_ring_report), 96 * k, 16 * N, N, 4 * N,
+                               sizeof(sfm_adjust_ring_report) };
+    size_t at[15];
+    at[0] = 0;
+    for (int q = 0; q < 14; ++q) at[q + 1] = at[q] + up(sizes[q] + 1);
+    detail::DeviceBlock mem(at[14]);
+    std::vector<float> pts(4 * N, 0.0f);
+    for (int c = 0; c < 4; ++c) std::copy(model.points.begin() + (size_t)c * T, model.points.begin() + (size_t)c * T + T, pts.begin() + (size_t)c * N);
+    const int32_t counts[8] = { model.tracks, model.observations, model.refined, model.kept, model.segments, model.longest_track, 0, 0 };
+    if (k) {
+        SFM_FACADE_CALL(sfm_copy_to_device(ctx, mem.p + at[0], model.root.data(), 4 * k));
+        SFM_FACADE_CALL(sfm_copy_to_device(ctx, mem.p + at[1], model.cams.data(), 96 * k));
+    }
+    SFM_FACADE_CALL(sfm_copy_to_device(ctx, mem.p + at[2], model.track_offset.data(), 4 * (T + 1)));
+    if (M) {
+        SFM_FACADE_CALL(sfm_copy_to_device(ctx, mem.p + at[3], model.obs_cam.data(), 4 * M));
+        SFM_FACADE_CALL(sfm_copy_to_device(ctx, mem.p + at[4], model.obs_record.data(), 4 * M));
+    }
+    if (N) SFM_FACADE_CALL(sfm_copy_to_device(ctx, mem.p + at[5], pts.data(), 16 * N));
+    if (T) SFM_FACADE_CALL(sfm_copy_to_device(ctx, mem.p + at[6], model.flags.data(), T));
+    SFM_FACADE_CALL(sfm_copy_to_device(ctx, mem.p + at[7], counts, sizeof(counts)));
+    SFM_FACADE_CALL(sfm_copy_to_device(ctx, mem.p + at[8], &ring.report, sizeof(ring.report)));
+    sfm_adjust_ring_in in;
+    in.pairs = handles.data();
+    in.d_root = reinterpret_cast<const int32_t *>(mem.p + at[0]); in.d_cams = reinterpret_cast<const float *>(mem.p + at[1]);
+    in.d_track_offset = reinterpret_cast<const int32_t *>(mem.p + at[2]); in.d_obs_cam = reinterpret_cast<const int32_t *>(mem.p + at[3]);
+    in.d_obs_record = reinterpret_cast<const int32_t *>(mem.p + at[4]); in.d_points = reinterpret_cast<const float *>(mem.p + at[5]);
+    in.d_flags = reinterpret_cast<const uint8_t *>(mem.p + at[6]); in.d_counts = reinterpret_cast<const int32_t *>(mem.p + at[7]);
+    in.d_ring_report = reinterpret_cast<const sfm_fuse_ring_report *>(mem.p + at[8]);
+    sfm_adjust_ring_out o;
+    o.d_cams = reinterpret_cast<float *>(mem.p + at[9]); o.d_points = reinterpret_cast<float *>(mem.p + at[10]);
+    o.d_used = reinterpret_cast<uint8_t *>(mem.p + at[11]); o.d_err = reinterpret_cast<float *>(mem.p + at[12]);
+    o.d_report = reinterpret_cast<sfm_adjust_ring_report *>(mem.p + at[13]);
+    SFM_FACADE_CALL(sfm_adjust_ring(ctx, &in, count, &p, &o));
+    r.cams.resize(24 * k); r.points.resize(4 * T); r.used.resize(T); r.err.resize(T);
+    SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.cams.data(), o.d_cams, 96 * k));
+    SFM_FACADE_CALL(sfm_copy_to_host(ctx, &r.report, o.d_report, sizeof(r.report)));
+    if (T) {
+        SFM_FACADE_CALL(sfm_copy_to_host(ctx, pts.data(), o.d_points, 16 * N));
+        for (int c = 0; c < 4; ++c) std::copy(pts.begin() + (size_t)c * N, pts.begin() + (size_t)c * N + T, r.points.begin() + (size_t)c * T);
+        SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.used.data(), o.d_used, T));
+        SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.err.data(), o.d_err, 4 * T));
+    }
+    return r;
+}
+
 } // namespace SfM
 
 #endif

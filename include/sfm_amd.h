@@ -628,7 +628,7 @@ int  sfm_fuse_chain(sfm_ctx *ctx, const sfm_fuse_pair_in *pairs, int num_pairs, 
  * sfm_refine_two_view's 5 degrees of freedom (t on the unit sphere, the start t normalised), every other camera with
  * sfm_register_view's 6.  Segments are independent Levenberg-Marquardt problems with a report each.
  * A track is used when its flag EQUALS SFM_FUSE_REFINED (a ring's seam tracks, SFM_FUSE_SEAM_*, are therefore not: their views
- * are not consecutive), it has at most max_track_views views, its point is finite and lies in front
+ * are not consecutive; sfm_adjust_ring uses them), it has at most max_track_views views, its point is finite and lies in front
  * of every one of its views under the start cameras; an unused track returns its input column.  A segment whose root camera
  * has fewer than 16 used observations, or any other camera fewer than 6, is SFM_REFINE_DEGENERATE (not an error): its cameras
  * (both input slots) and its tracks' columns are returned as they came in.
@@ -758,7 +758,8 @@ int  sfm_close_ring(sfm_ctx *ctx, const sfm_ring_link_in *links, int num_links, 
  * Points and flags are sfm_fuse_chain's, but a track that crosses the seam (its first observation's pair is larger than its
  * last's) is flagged SFM_FUSE_SEAM_REFINED / SFM_FUSE_SEAM_KEPT; d_counts[2] / [3] count 1 + 3 and 2 + 4.  sfm_adjust_chain uses
  * a track only when its flag EQUALS SFM_FUSE_REFINED, so seam tracks stay out of its banded system (whose views must be
- * consecutive) and come back as they went in: the ring's table may be handed to it as it is.
+ * consecutive) and come back as they went in: the ring's table may be handed to it as it is.  sfm_adjust_ring (below) is the
+ * adjustment that uses them, with one camera for view 0.
  * The call READS the pairs and writes only the caller's buffers: no stage, buffer id or getter belongs to it.  Integer atomics
  * only: two calls give the same bytes. */
 #define SFM_FUSE_SEAM_REFINED 3   /* SFM_FUSE_REFINED of a track that crosses the seam of a ring                     */
@@ -785,6 +786,73 @@ void sfm_fuse_ring_default_params(sfm_fuse_ring_params *p);
  * pairs[i] or links[i]) nothing is written.  The work buffers belong to the context. */
 int  sfm_fuse_ring(sfm_ctx *ctx, const sfm_fuse_pair_in *pairs, int num_pairs, const sfm_fuse_link_in *links,
                    const sfm_fuse_ring_params *p, const sfm_fuse_out *out, sfm_fuse_ring_report *d_report);   /* enqueue only */
+
+/* ---- one bundle adjustment over a closed ring: one camera per view, the seam tracks used ----------
+ * Reads the k pairs of a ring (3..4096), what sfm_fuse_ring wrote for them and its report.  An observation with d_obs_cam = c is
+ * of view ((c >> 1) + (c & 1)) mod k.  View 0 is the fixed [I|0] whichever pair observes it (pair 0's camera 1, pair k - 1's camera
+ * 2, both ends of a track followed round the whole ring); view v >= 1 is unknown camera v - 1, started at slot 2 (v - 1) + 1 of
+ * d_cams: k - 1 cameras.  Camera 0 (view 1) moves with sfm_refine_two_view's 5 degrees of freedom (t on the unit sphere, the
+ * start t normalised), every other camera with sfm_register_view's 6.  Slot 2 (k - 1) + 1 of d_cams is not read; d_root is required
+ * and swept for overlaps like the rest of the table, but not read (a CLOSED ring has one root).
+ * A track is used when its flag is SFM_FUSE_REFINED or SFM_FUSE_SEAM_REFINED, it has at most max_track_views views, its point is
+ * finite and lies in front of every one of its views under the start cameras; an unused track returns its input column.  When
+ * camera 0 has fewer than 16 used observations, or any other camera fewer than 6, the status is SFM_REFINE_DEGENERATE (not an
+ * error): all 24 k camera floats and all columns are returned as they came in.
+ * Residuals are pixels through the observing pair's K, Huber per view, as in sfm_adjust_chain.  The reduced camera system is
+ * cyclic-banded (a band and two corners); the cameras are taken in the order 0, k - 2, 1, k - 3, ..., in which it is block-banded
+ * with min(2 max_track_views, k - 1) block diagonals, and solved by sfm_adjust_chain's banded Cholesky in fp64.
+ * d_ring_report->status != SFM_RING_CLOSED: nothing is adjusted.  Cameras and columns are returned as they came in, d_used is all
+ * zero, and the report holds ring_status and zeros.  Use sfm_adjust_chain on such a table: pair k - 1's second camera must not be
+ * taken for view 0 when the closure was rejected.  The status is read on the device; the launches are the same.
+ * The call READS the pairs and writes only the caller's buffers: no stage, buffer id or getter belongs to it.  No float atomics:
+ * two calls give the same bytes. */
+typedef struct sfm_adjust_ring_params {
+    int32_t max_iterations;                               /* accepted + rejected, 0..50; default 10                    */
+    float   huber_px, min_rel_decrease, initial_lambda;   /* 1.0 / 1e-6 / 1e-3                                          */
+    int32_t max_track_views;                              /* W, 2..16; default 8: longer tracks are not used            */
+    int32_t reserved[4];                                  /* must be zero (else SFM_E_INVALID)                          */
+} sfm_adjust_ring_params;
+typedef struct sfm_adjust_ring_in {    /* pairs: HOST array; the rest DEVICE, what sfm_fuse_ring wrote; all required  */
+    sfm_pair *const *pairs;
+    const int32_t *d_root;             /* k                                                                           */
+    const float   *d_cams;             /* 24 x k                                                                      */
+    const int32_t *d_track_offset;     /* N + 1                                                                       */
+    const int32_t *d_obs_cam;          /* 2N                                                                          */
+    const int32_t *d_obs_record;       /* 2N                                                                          */
+    const float   *d_points;           /* 4 x N                                                                       */
+    const uint8_t *d_flags;            /* N                                                                           */
+    const int32_t *d_counts;           /* 8                                                                           */
+    const sfm_fuse_ring_report *d_ring_report;
+} sfm_adjust_ring_in;
+typedef struct sfm_adjust_ring_report {
+    int32_t ring_status;               /* SFM_RING_* of d_ring_report; the rest is zero unless it is SFM_RING_CLOSED  */
+    int32_t status;                    /* SFM_REFINE_*                                                                */
+    int32_t iterations, accepted;
+    int32_t num_cameras;               /* k - 1                                                                       */
+    int32_t num_tracks;                /* used tracks                                                                 */
+    int32_t num_seam_tracks;           /* of them: SFM_FUSE_SEAM_REFINED                                              */
+    int32_t num_observations;          /* the used tracks' observations                                               */
+    int32_t num_over_long;             /* tracks with more than max_track_views views                                 */
+    float   initial_rms_px, final_rms_px;      /* sqrt(sum of squares / (2 num_observations))                         */
+    float   final_cost, lambda;
+} sfm_adjust_ring_report;
+typedef struct sfm_adjust_ring_out {   /* DEVICE buffers of the caller; all required unless marked                    */
+    float   *d_cams;       /* 24 x k, the layout of sfm_fuse_out.d_cams: camera 1 of pair p + 1 is the bytes of camera 2 of
+                              pair p, camera 1 of pair 0 is its input slot, camera 2 of pair k - 1 is the bytes of camera 1
+                              of pair 0                                                                                */
+    float   *d_points;     /* 4 x N, leading dimension N                                                              */
+    uint8_t *d_used;       /* N: 1 = the track was used                                                               */
+    float   *d_err;        /* N, optional: the largest pixel error over the track's views under the returned cameras,
+                              +inf behind a camera; written for every track                                           */
+    sfm_adjust_ring_report *d_report;
+} sfm_adjust_ring_out;
+void sfm_adjust_ring_default_params(sfm_adjust_ring_params *p);
+/* num_pairs 3..4096, N (the pairs' records in all) at most 2^26.  Every pair belongs to ctx, is listed once and needs its
+ * normalised observations and K (the points stage).  No output may overlap an input (d_ring_report included) or another output.
+ * Every check precedes the first enqueue: on SFM_E_INVALID / SFM_E_STATE (the text names pairs[i]) nothing is written.  The work
+ * buffer belongs to the context. */
+int  sfm_adjust_ring(sfm_ctx *ctx, const sfm_adjust_ring_in *in, int num_pairs, const sfm_adjust_ring_params *p,
+                     const sfm_adjust_ring_out *out);                            /* enqueue only */
 
 /* ---- accessors (the reference keeps these private; needed for parity checks) ------------------ */
 #define SFM_BUF_X0      0   /* float 3 x ld   normalised coords image 1 (ld = sfm_pair_ld)   */
