@@ -125,7 +125,7 @@ $(GEOMTEST): tests/cpp/geom_test.cpp $(PKG)/host/geomFuncs.h $(PKG)/host/sfm_io.
 
 # CPU-only: the host-compiled arithmetic check of the non-GPU tests (the fakeccl target, which needs the gfx950 build and the RCCL
 # header, is a target of its own and part of `all`)
-hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libchainadjustcheck.so tests/hostcheck/libringcheck.so tests/hostcheck/libfuseringcheck.so tests/hostcheck/libringadjustcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/hostcheck/pfdecodecheck
+hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libchainadjustcheck.so tests/hostcheck/libringcheck.so tests/hostcheck/libfuseringcheck.so tests/hostcheck/libringadjustcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/hostcheck/pfdecodecheck tests/hostcheck/libpfpaircheck.so
 
 # TEST HARNESS: comm.cpp linked against a shared-memory stand-in for the nine RCCL calls it makes, so that a 1-GPU box can run the
 # exchange code with two real ranks (tests/test_gpu_fakeccl.py); the product's libsfm_amd_rccl.so is linked against librccl
@@ -202,6 +202,11 @@ tests/hostcheck/libpfldscheck.so: tests/hostcheck/pfldscheck.hip $(CSRC)/prefilt
 tests/hostcheck/pfdecodecheck: tests/hostcheck/pfdecodecheck.hip $(CSRC)/prefilter_math.hpp $(CSRC)/prefilter_lds.hpp $(CSRC)/prefilter_record.hpp $(CSRC)/device_math.hpp
 	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -Wno-pass-failed -o $@ $<
 
+# the per-tile rule's operands built once per hypothesis (prefilter_record.hpp: pf_tile_operands_full, the paired passes) against the
+# per-half build of the single passes, host-compiled for tests/test_pf_pair_host.py
+tests/hostcheck/libpfpaircheck.so: tests/hostcheck/pfpaircheck.hip $(CSRC)/prefilter_record.hpp $(CSRC)/prefilter_math.hpp $(CSRC)/device_math.hpp
+	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
+
 # the job layout and matcher-launch grouping of a batched sfm_process_pairs call (pairs_batch.hpp), host-compiled for
 # tests/test_pairs_plan_host.py
 tests/hostcheck/libpairsplancheck.so: tests/hostcheck/pairsplancheck.hip $(CSRC)/pairs_batch.hpp $(CSRC)/common.hpp $(CSRC)/pair_state.hpp include/sfm_amd.h
@@ -217,7 +222,7 @@ tests/hostcheck/libbufferrangescheck.so: tests/hostcheck/bufferrangescheck.cpp $
 	g++ -O2 -std=c++17 -Wall -fPIC -shared -o $@ $<
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(APDEMO) $(FCDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libchainadjustcheck.so tests/hostcheck/libringcheck.so tests/hostcheck/libfuseringcheck.so tests/hostcheck/libringadjustcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/hostcheck/pfdecodecheck tests/fake_ccl/libsfm_amd_fakeccl.so
+	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(APDEMO) $(FCDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libchainadjustcheck.so tests/hostcheck/libringcheck.so tests/hostcheck/libfuseringcheck.so tests/hostcheck/libringadjustcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/hostcheck/pfdecodecheck tests/hostcheck/libpfpaircheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all ab oracle hostcheck fakeccl clean

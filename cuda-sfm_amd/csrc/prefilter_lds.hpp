@@ -20,7 +20,11 @@ constexpr int kPfRing = 128;             // survivor ring entries (8 bytes) per 
 constexpr int kPfERow = 10;                                   // floats per hypothesis reserved in the E table (9 used): etab[32 k + row] -- a lane's nine
                                                               // reads for a random row hit bank (row mod 32) + const, so distinct rows never conflict
                                                               // (row-major 40-byte rows put rows r and r + 16 on the same banks: 19 % of the LDS cycles were conflicts)
-constexpr int kPfWaveBytes = 32 * kPfERow * 4 + 32 * 4;
+// A wavefront's table holds the rows of ONE unit of its work: 32 (a pass), or 64 for the per-tile rule's paired passes (lane l = hypothesis
+// 64 j + l, two scans of 32 rows each): etab[rows k + row].  A scan touches 32 consecutive rows of one half, so its distinct rows sit on
+// distinct banks exactly as with 32 rows; the other half's rows are only touched by the other scan, the install and the epilogue.
+constexpr int kPfPassRows = 32, kPfPairRows = 64;
+constexpr int pf_wave_bytes(int rows) { return rows * kPfERow * 4 + rows * 4; }
 // The map for a tile of `tile` points (a multiple of 32); an even number of 32-point blocks is staged (the scan takes two per iteration).
 template <int RULE> struct PfLds {
     static constexpr int kFragsPerBlock = RULE == kPfRuleG ? 3 : 2;
@@ -28,15 +32,16 @@ template <int RULE> struct PfLds {
     static constexpr int kFrag = 0;
     static constexpr int kTileMax = kPfTileMax;
     int staged, pts, ring, wave, next, lut, bytes;
-    __host__ __device__ explicit PfLds(int tile, int ring_entries = kPfRing, int entry_bytes = 8)
+    // rows: hypotheses in a wavefront's table; the default is the product's largest block (the band rules' paired passes)
+    __host__ __device__ explicit PfLds(int tile, int ring_entries = kPfRing, int entry_bytes = 8, int rows = RULE == kPfRuleG ? kPfPassRows : kPfPairRows)
     {
         staged = (tile + 63) & ~63;                           // points staged: whole iterations of two blocks (beyond `tile`: padding)
         pts = kFrag + (staged / 32) * kBlockBytes;            // float4 (x2x, x1x, x2y, x1y) per point
         ring = pts + staged * 16;                             // the wavefronts' survivor rings, 1024 bytes each, 1024-byte aligned (a slot's
                                                               // address is (offset & 1023) | base: one v_and_or_b32): staged is a multiple of 64
         ring = (ring + ring_entries * entry_bytes - 1) & ~(ring_entries * entry_bytes - 1);
-        wave = ring + kPfWaves * ring_entries * entry_bytes;  // per wavefront: E table 9 x 32 floats (component-major), 32 counters
-        next = wave + kPfWaves * kPfWaveBytes;                // the block's pass counter
+        wave = ring + kPfWaves * ring_entries * entry_bytes;  // per wavefront: E table 9 x rows floats (component-major), rows counters
+        next = wave + kPfWaves * pf_wave_bytes(rows);         // the block's pass counter
         lut = next + 16;                                      // packed scan: survivor bit -> (accumulator row, step), 32 bytes (pf_pack_code)
         bytes = lut + 32;
     }
@@ -59,6 +64,17 @@ constexpr unsigned long long kPfSumCountsMin = 1ull << 21;
 static inline bool pf_sums_counts_at(unsigned count, int ld, int tile)
 {
     return (unsigned long long)count * (unsigned long long)((ld + tile - 1) / tile) >= kPfSumCountsMin;
+}
+
+// Which launches of the per-tile rule prepare two passes at once (ransac_prefilter.hip: kPair).  A pair doubles the grain of the
+// hand-out: the wavefronts of a block finish within one PAIR of each other, and what the shared preparation saves must pay for that
+// tail.  A launch of c partial counts gives each wavefront of a full chip (256 blocks of 16) c / 2^18 pairs.  Measured on bench.py's
+// pipelined step at 4096 points (profiles/NOTES_r11.md): 64 pairs per wavefront 4.1 % shorter, 16 pairs (the headline) 2.8 % shorter,
+// 8 pairs (524288 hypotheses) 1.2 % LONGER -- so pairs from 2^22 partial counts on, single passes with the summing epilogue below.
+constexpr unsigned long long kPfPairPassesMin = 1ull << 22;
+static inline bool pf_pairs_passes_at(unsigned count, int ld, int tile)
+{
+    return (unsigned long long)count * (unsigned long long)((ld + tile - 1) / tile) >= kPfPairPassesMin;
 }
 
 } // namespace sfm

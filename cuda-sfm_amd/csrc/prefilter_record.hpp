@@ -199,18 +199,41 @@ __device__ __forceinline__ uint32_t pf_tile_flags(const float e[9], float B, con
     return (scan ? kPfTileFlagScan : 0u) | (b_safe ? kPfTileFlagBSafe : 0u);
 }
 
+#endif
+
 // this lane's half (k-slots 8 half .. 8 half + 7 of either k-step) of the coefficient fragments of hypothesis e for a tile whose
 // points lie in `box`: the very values pf_band_store would put into a record for the same sigma
-__device__ __forceinline__ void pf_tile_operands(const float e[9], uint32_t flags, float dn, float lin, float thr, float B, const PfBox &box, int half, h8 &n0, h8 &n1)
+// (d_mine: the divisor this half bounds, prefilter_band_divisor_max(e, lin, box, half); d_other: the other half's)
+SFM_HD void pf_tile_operands_half(const float e[9], uint32_t flags, float dn, float thr, float B, int half, float d_mine, float d_other, h8 &n0, h8 &n1)
 {
-    // each half of the wavefront bounds ONE divisor over its view's box (lanes l and l + 32 hold the same hypothesis) and hands it over
-    const float d_mine = prefilter_band_divisor_max(e, lin, box, half);
-    const float d_other = __shfl_xor(d_mine, 32);
     const float sigma = prefilter_band_sigma_from_maxima(dn, thr, B, half ? d_other : d_mine, half ? d_mine : d_other, (flags & kPfTileFlagBSafe) != 0u, kPfBandTopPack);
     _Float16 ns[kPfSlots];
     prefilter_band_hyp_slots(e, sigma, ns);
 #pragma unroll
     for (int j = 0; j < 8; ++j) { n0[j] = half ? ns[8 + j] : ns[j]; n1[j] = half ? ns[24 + j] : ns[16 + j]; }
+}
+
+// The whole of it in ONE lane (paired passes: lane l holds hypothesis 64 j + l): both divisors bounded here, sigma and all 32 k-slots by
+// the same functions in the same order -- x0 | y0 = k-slots 0..7 | 8..15 of k-step 0, x1 | y1 of k-step 1, bit for bit what
+// pf_tile_operands_half gives the lower | upper half.  Exchanging the upper 32 lanes of x with the lower 32 of y (v_permlane32_swap)
+// leaves the A fragments of hypotheses 0..31 in x and those of hypotheses 32..63 in y.
+SFM_HD void pf_tile_operands_full(const float e[9], uint32_t flags, float dn, float lin, float thr, float B, const PfBox &box, h8 &x0, h8 &y0, h8 &x1, h8 &y1)
+{
+    const float Da = prefilter_band_divisor_max(e, lin, box, 0), Db = prefilter_band_divisor_max(e, lin, box, 1);
+    const float sigma = prefilter_band_sigma_from_maxima(dn, thr, B, Da, Db, (flags & kPfTileFlagBSafe) != 0u, kPfBandTopPack);
+    _Float16 ns[kPfSlots];
+    prefilter_band_hyp_slots(e, sigma, ns);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { x0[j] = ns[j]; y0[j] = ns[8 + j]; x1[j] = ns[16 + j]; y1[j] = ns[24 + j]; }
+}
+
+#if defined(__HIPCC__)
+__device__ __forceinline__ void pf_tile_operands(const float e[9], uint32_t flags, float dn, float lin, float thr, float B, const PfBox &box, int half, h8 &n0, h8 &n1)
+{
+    // each half of the wavefront bounds ONE divisor over its view's box (lanes l and l + 32 hold the same hypothesis) and hands it over
+    const float d_mine = prefilter_band_divisor_max(e, lin, box, half);
+    const float d_other = __shfl_xor(d_mine, 32);
+    pf_tile_operands_half(e, flags, dn, thr, B, half, d_mine, d_other, n0, n1);
 }
 
 // The two A fragments of a lane out of its half of a band-rule record (r0 = words 0..3, r1 = words 4..7 of the half).

@@ -17,6 +17,8 @@
 //         3 x ds_read_b128 -> 3 MFMAs (G: 1, nt: 2) -> per accumulator v_fma (G - nt^2), v_alignbit (its sign bit)
 //     software-pipelined by hand: while the vector unit scans the accumulators of step k, the matrix cores work on step
 //     k + 1 and the fragments of step k + 2 are on their way from LDS (two accumulator sets, sched_group_barrier);
+//     round 11, per-tile rule, large launches: the passes come in PAIRS -- 64 hypotheses, one per lane, prepared at once and scanned in
+//     two halves (kPair below);
 //   * lanes with a surviving pair append one word per two steps to the wavefront's ring in LDS; 64 entries at a time go
 //     through the exact filter, one entry per lane, and inliers bump the hypothesis' counter in LDS;
 //   * partial counts reach counts[] through integer atomics (order-independent, so the result is deterministic): large launches
@@ -182,6 +184,11 @@ constexpr int kPfVarDrainLocal = 2;         // in the drain a lane works through
 constexpr int kPfVarClosedDecode = 4;       // a survivor's bit position is decoded by arithmetic (pf_pack_code_closed) instead of the 32-byte table in LDS
 constexpr int kPfVarAnswerEpilogue = 8;     // one returning 64-bit atomic per (hypothesis, tile); the last tile's lane stores the count and owns the key
 constexpr int kPfVarDrainK1 = 16, kPfVarDrainK7 = 32;      // the drain's cap: 1 or 7 further survivors per lane
+// Round 11: VAR = 0 of the per-tile rule prepares TWO passes at once -- a wavefront's unit of work is a pair of consecutive passes, lane l
+// holds hypothesis 64 j + l, every lane builds the operands of its OWN hypothesis (pf_tile_operands_full) and eight v_permlane32_swap
+// turn them into the A fragments of the two scans: one fetch, one build, one install and one epilogue per 64 hypotheses instead of two,
+// each of which ran the same arithmetic in lanes l and l + 32.  This bit keeps round 9's one pass at a time (lab bench: reserved[1] = 20).
+constexpr int kPfVarSinglePass = 64;
 
 // FL2 (experiment): a ring of 256 entries, flushed 128 at a time -- two entries per lane, their LDS reads issued together
 // WIDE (experiment): ring entries of 16 bytes that cover FOUR steps (two conversions): half as many appends
@@ -191,8 +198,12 @@ constexpr int kPfVarDrainK1 = 16, kPfVarDrainK7 = 32;      // the drain's cap: 1
 // of the NEXT pipelined call is meant to run next to it (sfm_estimate_E_pipelined), so 4 scoring wavefronts must leave a solve wavefront's
 // registers free on every SIMD: 4 x 96 + 88 (ransac_solve_lanes1_qr: 88, allocated in eights) = 472 of 512.  The two instances the
 // product runs are compiled for five wavefronts per SIMD, which caps them at 96; the lab bench's variants keep the default.
+// The paired passes of the per-tile rule (VAR = 0) hold the second scan's fragments -- eight registers -- across the first scan: that
+// instance may take 104 (4 x 104 + 88 = 504), which no whole number of wavefronts per SIMD asks for, so it is compiled for four and
+// held to 104 by tests/test_register_budget.py.
 constexpr int pf_score_waves_per_simd(int var, int rule, int fl2, int pipe, int wide, int prio)
 {
+    if (var == 0 && rule == kPfRuleBandTile && !fl2 && !pipe && !wide && !prio) return 4;
     return ((var & kPfVarTickets) == 0 && (rule == kPfRuleBandTile || rule == kPfRuleBandPack) && !fl2 && !pipe && !wide && !prio) ? 5 : 4;
 }
 
@@ -228,33 +239,39 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
 #define PF_PHASE(k) do { } while (0)
 #endif
     const int half = lane >> 5, row = lane & 31;
-    const uint32_t npass = (count + (uint32_t)kPfGroup - 1u) / (uint32_t)kPfGroup;
-    const uint32_t nstatic = gridDim.x * (uint32_t)W;             // passes handed out by position
+    uint32_t npass = (count + (uint32_t)kPfGroup - 1u) / (uint32_t)kPfGroup;
+    const uint32_t nstatic = gridDim.x * (uint32_t)W;             // passes (paired: pairs of passes) handed out by position
     using LT = PfLds<RULE>;
     constexpr bool kBand = RULE != kPfRuleG, kTile = RULE == kPfRuleBandTile, kPack = RULE == kPfRuleBandPack || kTile;
     static_assert(!(FL2 && kPack) && !((VAR & kPfVarTickets) && kPack), "the recorded variants were built on the v_alignbit scan");
     // the pass tail of round 9: the product's two rules (and their lab-bench twins with the parts that did not pay switched on)
     constexpr bool kTail9 = kPack && W == 16 && !FL2 && !PIPE && !WIDE && !PRIO && !(VAR & kPfVarTickets);
     static_assert(kTail9 || (VAR & ~kPfVarTickets) == 0, "the pass-tail switches belong to the product's two rules");
+    static_assert(!(VAR & kPfVarSinglePass) || (kTile && VAR == kPfVarSinglePass), "single passes: the per-tile rule's summing instance");
+    // paired passes: the unit of work is 64 hypotheses (two scans of 32) prepared at once, one hypothesis per lane
+    constexpr bool kPair = kTile && kTail9 && VAR == 0;
+    constexpr int kRows = kPair ? kPfPairRows : kPfPassRows, kUnit = kRows;       // rows of the wavefront's table = hypotheses per unit
     constexpr int kDrainMore = !kTail9 ? 0 : (VAR & kPfVarDrainK1) ? 1 : (VAR & kPfVarDrainK7) ? 7 : (VAR & kPfVarDrainLocal) ? 3 : 0;
     constexpr bool kDecodeTable = !(kTail9 && (VAR & kPfVarClosedDecode));
     constexpr bool kSumCounts = kTail9 && !(VAR & kPfVarAnswerEpilogue);
     constexpr int kRing = FL2 ? 256 : kPfRing;
     constexpr int kEnt = WIDE ? 16 : 8;                       // bytes per ring entry
     static_assert(!WIDE || (kPack && !PIPE && !FL2), "wide entries: the packed scan's plain loop only");
-    const LT L(tile, kRing, kEnt);
-    float *etab = reinterpret_cast<float *>(smem + L.wave + wave * kPfWaveBytes);
-    int *cnt = reinterpret_cast<int *>(etab + 32 * kPfERow);
+    if (kPair) npass = (npass + 1u) >> 1;                         // from here on: units of work
+    const LT L(tile, kRing, kEnt, kRows);
+    float *etab = reinterpret_cast<float *>(smem + L.wave + wave * pf_wave_bytes(kRows));
+    int *cnt = reinterpret_cast<int *>(etab + kRows * kPfERow);
 
     // Operands of hypothesis (32 ps + row): this lane's half of the three A fragments and (lanes 0..31) its zero-divisor
     // flag and its E row.  Rows beyond the range repeat the last hypothesis (never counted).
     PfFrags afrag = {};
+    h8 bfrag_n0 = {}, bfrag_n1 = {};                         // paired passes: the second scan's fragments
     uint32_t key0 = 0u;
     float rec_dn = 0.0f, rec_lin = 0.0f;                     // tile rule: the rest of the record fetch_pass has just read
     float e_row[9] = {};
     auto fetch_pass = [&](uint32_t pass, PfFrags &af, uint32_t &k0, float (&e)[9], float &dn, float &lin) {
-        const uint32_t hf = pass * (uint32_t)kPfGroup;
-        const uint32_t h = hf + (uint32_t)min(row, (int)min((uint32_t)kPfGroup, count - hf) - 1);
+        const uint32_t hf = pass * (uint32_t)kUnit;
+        const uint32_t h = hf + (uint32_t)min(kPair ? lane : row, (int)min((uint32_t)kUnit, count - hf) - 1);
         if (kTile) {                                                                  // E and the flag word; the operands are derived at install time
             const float *src = Ecand + 9 * (size_t)h;
 #pragma unroll
@@ -274,10 +291,11 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
         }
     };
     auto install_rows = [&](const float (&e)[9]) {          // E table and counters of a pass (the previous pass' ring is drained, its counters are out)
-        if (half == 0) {
+        if (kPair || half == 0) {
+            const int r = kPair ? lane : row;
 #pragma unroll
-            for (int k = 0; k < 9; ++k) etab[32 * k + row] = e[kPfESlot[k]];
-            cnt[row] = 0;
+            for (int k = 0; k < 9; ++k) etab[kRows * k + r] = e[kPfESlot[k]];
+            cnt[r] = 0;
         }
     };
     // the first pass' operands are requested before the tile is staged: their way through the memory system overlaps it
@@ -355,8 +373,23 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
         int half_l = half;
         float thr_l = thr, B_l = pf_B;
         asm volatile("" : "+v"(half_l), "+s"(thr_l), "+s"(B_l));
-        pf_tile_operands(e, fl, dn, lin, thr_l, B_l, tbox, half_l, afrag.n0, afrag.n1);
         key0 = fl & kPfTileFlagScan;
+        if constexpr (kPair) {
+            // every lane its own hypothesis; x = k-slots 0..7, y = k-slots 8..15 of a k-step.  v_permlane32_swap exchanges the upper 32
+            // lanes of x with the lower 32 of y: x = the A fragment of hypotheses 0..31 (first scan), y = that of 32..63 (second scan)
+            h8 x0, y0, x1, y1;
+            pf_tile_operands_full(e, fl, dn, lin, thr_l, B_l, tbox, x0, y0, x1, y1);
+            u4v xa = __builtin_bit_cast(u4v, x0), ya = __builtin_bit_cast(u4v, y0), xb = __builtin_bit_cast(u4v, x1), yb = __builtin_bit_cast(u4v, y1);
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const u2v sa = __builtin_amdgcn_permlane32_swap(xa[w], ya[w], false, false);
+                const u2v sb = __builtin_amdgcn_permlane32_swap(xb[w], yb[w], false, false);
+                xa[w] = sa.x; ya[w] = sa.y; xb[w] = sb.x; yb[w] = sb.y;
+            }
+            afrag.n0 = __builtin_bit_cast(h8, xa); afrag.n1 = __builtin_bit_cast(h8, xb);
+            bfrag_n0 = __builtin_bit_cast(h8, ya); bfrag_n1 = __builtin_bit_cast(h8, yb);
+        } else
+        pf_tile_operands(e, fl, dn, lin, thr_l, B_l, tbox, half_l, afrag.n0, afrag.n1);
     };
     if (kTile) {
 #pragma unroll
@@ -392,8 +425,11 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
     // ---- 32 hypotheses per pass of this wavefront (no block-level synchronisation from here on)
     while (have) {
         SFM_PHASE("pass_begin");
-        const uint32_t h_first = ps * (uint32_t)kPfGroup;
-        const int nvalid = (int)min((uint32_t)kPfGroup, count - h_first);
+        const uint32_t h_first = ps * (uint32_t)kUnit;
+        const int nvalid_unit = (int)min((uint32_t)kUnit, count - h_first);
+        // a scan's 32 rows: `nvalid` of them are hypotheses, `hoff` is the first one's row in the table (paired: 32 x scan)
+        int nvalid = min(nvalid_unit, kPfGroup), hoff = 0;
+        const int nscan = (kPair && nvalid_unit > kPfGroup) ? 2 : 1;
 #if SFM_AB
         const bool probe1 = probe && passes_done == 0u;
 #endif
@@ -408,32 +444,31 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
         // zero divisors (prefilter_math.hpp (3)): a hypothesis whose record says "cannot tell" (~0.5 %: its first divisor can
         // vanish in a grid cell that some point of the pair occupies, or no small set of cells could be named) is checked
         // against every point of the tile, one hypothesis at a time by the whole wavefront
-        {
-            const bool scan = key0 != 0u;                               // (the flag sits in the upper half's part of the record)
-            const unsigned long long sm = __ballot(scan);
-            uint32_t todo = (uint32_t)sm | (uint32_t)(sm >> 32);
+        // (paired: the flag is the lane's own -- the ballot's low word names rows of the first scan, its high word rows of the second)
+        const unsigned long long scan_rows = __ballot(key0 != 0u);
+        int head = 0, nq = 0;                       // ring state (wave-uniform)
+        auto patch_zero_divisor_rows = [&](int sc) {
+            uint32_t todo = kPair ? (uint32_t)(sc ? scan_rows >> 32 : scan_rows) : ((uint32_t)scan_rows | (uint32_t)(scan_rows >> 32));
             uint32_t survive = 0u;                                      // rows whose pairs must all survive in this tile
             while (todo) {
-                const int r = __builtin_ctz(todo);
+                const int r = __builtin_ctz(todo) + hoff;
                 todo &= todo - 1u;
-                const float se[6] = { etab[6 * 32 + r], etab[2 * 32 + r], etab[r], etab[3 * 32 + r], etab[7 * 32 + r], etab[4 * 32 + r] };          // e0 .. e5 (slots 6 2 0 3 7 4)
+                const float se[6] = { etab[6 * kRows + r], etab[2 * kRows + r], etab[r], etab[3 * kRows + r], etab[7 * kRows + r], etab[4 * kRows + r] };          // e0 .. e5 (slots 6 2 0 3 7 4)
                 bool z = false;
                 for (int j = 0; j < L.staged / 64; ++j) {
                     const float4 q = pts[j * 64 + lane];
                     z = z || prefilter_zero_divisor(se, q.x, q.z);              // NaN padding never compares equal to 0
                 }
-                if (__ballot(z) != 0ull) survive |= 1u << r;
+                if (__ballot(z) != 0ull) survive |= 1u << (r - hoff);
             }
             if (survive != 0u && ((survive >> row) & 1u)) {             // nt = 0, G = 2^-10 for real points (prefilter_hyp_slots)
                 const h8 zero = {};
                 afrag.n0 = zero; afrag.n1 = zero; afrag.t = zero;
                 if (half) { afrag.n1[3] = (_Float16)1.0f; afrag.t[7] = (_Float16)0.0009765625f; }      // k-slots 27 and 15
             }
-        }
-        PF_PHASE(3);
+        };
 
         // ---- the scan: two accumulator sets; while set A is scanned the MFMAs of the next step fill set B
-        int head = 0, nq = 0;                       // ring state (wave-uniform)
         // a lane's point in 32-point block 0 (LDS byte address, a multiple of 16) | its accumulator-row offset 4 (lane >> 5)
         const uint32_t lane_tag = (uint32_t)(size_t)(lds_cf4 *)pts + (uint32_t)(row * 16) + (uint32_t)(half * 4);
         // the exact decision for the FIRST surviving pair of a ring entry's mask; the survivor leaves the mask
@@ -455,11 +490,11 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
             }
             if (hl < nvalid) {
                 const f4v q = *(lds_cf4 *)((__attribute__((address_space(3))) const unsigned char *)0 + ((tag & ~15u) + ((uint32_t)sub << 9)));
-                lds_cf *e = etab_l + hl;
-                const v2f p0 = { e[0], e[32] }, p1 = { e[64], e[96] }, p2 = { e[128], e[160] }, p3 = { e[192], e[224] };      // (e2 e6) (e1 e3) (e5 e7) (e0 e4): one ds_read2_b32 each
-                const float e8 = e[256];
+                lds_cf *e = etab_l + hl + hoff;
+                const v2f p0 = { e[0], e[kRows] }, p1 = { e[2 * kRows], e[3 * kRows] }, p2 = { e[4 * kRows], e[5 * kRows] }, p3 = { e[6 * kRows], e[7 * kRows] };      // (e2 e6) (e1 e3) (e5 e7) (e0 e4): one ds_read2_b32 each (64 rows: ds_read2st64_b32)
+                const float e8 = e[8 * kRows];
                 if (pf_exact_inlier(p0, p1, p2, p3, e8, v2f{ q.x, q.y }, v2f{ q.z, q.w }, band))
-                    __hip_atomic_fetch_add(cnt_l + hl, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_add(cnt_l + hl + hoff, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         };
         auto flush = [&](int m, auto more_c) {
@@ -554,6 +589,9 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
             nq += __builtin_popcountll(moreA) + __builtin_popcountll(moreB) - 128;
         };
 
+        for (int sc = 0; ; ++sc) {
+        patch_zero_divisor_rows(sc);
+        PF_PHASE(3);
         if constexpr (kPack && PIPE) {
         // ---- packed scan, software-pipelined over FOUR accumulator sets: while the conversion and the bit picking work on the two
         // sets of the previous two steps, the four MFMAs of the next two steps go out between them, one at a time (a wavefront that
@@ -702,6 +740,13 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
             }
         }
         }
+        if (sc + 1 >= nscan) break;
+        // paired passes: the ring is drained between the scans as at every pass boundary (its entries name rows of THIS scan), then the
+        // second scan's fragments and rows take over
+        while (nq > 0) flush(min(nq, 64), kDrain);
+        afrag.n0 = bfrag_n0; afrag.n1 = bfrag_n1;
+        hoff = kPfGroup; nvalid = nvalid_unit - kPfGroup;
+        }
         PF_PHASE(4);
         SFM_PHASE("pass_end_fetch_next");
         // the next pass' operands: requested now, they arrive while the ring is drained and the counts go out
@@ -748,7 +793,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
         // atomic per (hypothesis, tile) that has inliers, whose answer nobody waits for -- a sum needs none.  The keys come from
         // ransac_argmax_counts behind this launch (ransac.hip), as on the tile-parallel path of the plain kernel.  A wavefront's LDS
         // operations complete in order: the counters are read before install_rows clears them.
-        if (lane < nvalid) {
+        if (lane < nvalid_unit) {
             const int c = cnt[lane];
             if (c) __hip_atomic_fetch_add(&counts[h_first + lane], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -1239,7 +1284,7 @@ static int pf_rule_switch(const sfm_ransac_params &p)      // lab bench: the rul
     if (SFM_SW(p, 3) == 5 || SFM_SW(p, 1) == 5 || SFM_SW(p, 1) == 7 || SFM_SW(p, 1) == 9) return kPfRuleBand;
     if (SFM_SW(p, 3) == 6 || SFM_SW(p, 1) == 11 || SFM_SW(p, 1) == 12) return kPfRuleBandPack;
     if (SFM_SW(p, 3) == 7 || SFM_SW(p, 1) == 13 || SFM_SW(p, 1) == 14 || SFM_SW(p, 1) == 15) return kPfRuleBandTile;
-    return -1;
+    return -1;          // (reserved[1] = 19 / 20, paired / single passes of the summing per-tile instance, leave the rule to the product's choice)
 }
 
 // The product's choice.  Per-tile band constants (tiles = runs of a Morton-ordered copy of the correspondences, sigma and the coefficient
@@ -1286,17 +1331,24 @@ int prefilter_tile_points(const sfm_pair *pair, const sfm_ransac_params &p) { re
 // kPfSumCountsMin (hypothesis, tile) partial counts per launch on (prefilter_lds.hpp: pf_sums_counts_at), round 4's epilogue below that.
 // Lab bench: reserved[3] = 8 + (1: the drain works through further survivors locally, 2: table-free decode, 4: round 4's epilogue at every
 // size); reserved[1] = 18: counts are summed at every size; 16 / 17: the same with the drain's cap at 1 / 7 further survivors (per-tile form).
+// Round 11: the per-tile rule's summing instance prepares two passes at once (VAR = 0) where pf_pairs_passes_at says so -- from 2^22
+// partial counts per launch on, 16 pairs per wavefront of a full chip -- and runs round 9's single passes (kPfVarSinglePass) below that.
+// Lab bench: reserved[1] = 19 sums at every size with paired passes, 20 sums at every size with single passes (both leave the
+// per-hypothesis rule of a first call as it is).
 static int pf_tail_var(const sfm_pair *pair, const sfm_ransac_params &p, uint32_t count)
 {
     const bool large = pf_sums_counts_at(count, pair->ld, pf_tile_of(pair, p));
+    if (SFM_SW(p, 1) == 19) return 0;
+    if (SFM_SW(p, 1) == 20) return pair->pf_rule == kPfRuleBandTile ? kPfVarSinglePass : 0;
     if (pair->pf_rule == kPfRuleBandTile && SFM_SW(p, 1) == 16) return kPfVarDrainK1;
     if (pair->pf_rule == kPfRuleBandTile && SFM_SW(p, 1) == 17) return kPfVarDrainK7;
     int var = 0;
     const bool lab = SFM_SW(p, 3) >= 8 && SFM_SW(p, 3) < 16;
     if (lab && (SFM_SW(p, 3) & 1)) var |= kPfVarDrainLocal;
     if (lab && (SFM_SW(p, 3) & 2)) var |= kPfVarClosedDecode;
-    const bool sum = (lab && (SFM_SW(p, 3) & 4)) ? false : (large || (SFM_SW(p, 1) >= 16 && SFM_SW(p, 1) <= 18));
+    const bool sum = (lab && (SFM_SW(p, 3) & 4)) ? false : (large || (SFM_SW(p, 1) >= 16 && SFM_SW(p, 1) <= 18));     // (19, 20: answered above)
     if (!sum) var |= kPfVarAnswerEpilogue;
+    if (var == 0 && pair->pf_rule == kPfRuleBandTile && !pf_pairs_passes_at(count, pair->ld, pf_tile_of(pair, p))) var = kPfVarSinglePass;
     return var;
 }
 
@@ -1321,7 +1373,13 @@ int launch_score_prefilter(sfm_pair *pair, ShardSlot &s, hipStream_t stream, con
     const int tile = pf_tile_of(pair, p);
     const int ntiles = (pair->ld + tile - 1) / tile;
     const uint32_t npass = (count + (uint32_t)kPfGroup - 1u) / (uint32_t)kPfGroup;
-    const uint32_t iters = (npass + (uint32_t)waves - 1) / (uint32_t)waves;       // block iterations per tile
+    const int rule = pair->pf_rule;
+    const int tail_var = pf_tail_var(pair, p, count);
+    const bool wide = rule == kPfRuleBandTile && SFM_SW(p, 1) == 13;                     // (AB build: 16-byte ring entries covering four steps)
+    // (the instance the chain below picks for paired passes: <16, 0, kPfRuleBandTile> with none of the recorded variants' switches)
+    const bool paired_units = rule == kPfRuleBandTile && tail_var == 0 && waves == kPfWaves && !wide && SFM_SW(p, 1) != 14 && SFM_SW(p, 1) != 15;
+    const uint32_t nunits = paired_units ? (npass + 1u) / 2u : npass;             // what a wavefront takes at a time: a pass, or a pair of passes
+    const uint32_t iters = (nunits + (uint32_t)waves - 1) / (uint32_t)waves;      // block iterations per tile
     // one block per CU is resident (152 KiB of LDS), so the grid is at most one block per CU, spread over the tiles: columns =
     // floor(CUs / tiles).  Until round 4 sixteen tiles got two blocks per CU queued up (32 columns): the second block of a CU
     // pays the tile staging and the end-of-block tail once more -- 16384 x 65536: 0.1557 -> 0.1475 ms with 16 columns, 16384 x 2^20
@@ -1332,11 +1390,9 @@ int launch_score_prefilter(sfm_pair *pair, ShardSlot &s, hipStream_t stream, con
     if (cols < 1) cols = 1;
     const int dynamic = SFM_SW(p, 1) == 2 ? 0 : 1;                               // (AB build, reserved[1] == 2: static striding)
     const int var = SFM_SW(p, 3) >= 16 ? SFM_SW(p, 3) - 16 : 0;                 // (AB build, reserved[3] = 16 + VAR bits)
-    const int rule = pair->pf_rule;
-    const int tail_var = pf_tail_var(pair, p, count);
     const bool fl2 = rule == kPfRuleBand && waves == kPfWaves && SFM_SW(p, 1) == 9;      // (AB build: 256-entry ring, two entries per lane per flush)
-    const bool wide = rule == kPfRuleBandTile && SFM_SW(p, 1) == 13;                     // (AB build: 16-byte ring entries covering four steps)
-    const int lds_bytes = wide ? PfLds<kPfRuleBand>(tile, kPfRing, 16).bytes : fl2 ? PfLds<kPfRuleBand>(tile, 256).bytes : rule != kPfRuleG ? PfLds<kPfRuleBand>(tile).bytes : PfLds<kPfRuleG>(tile).bytes;
+    const int lds_bytes = wide ? PfLds<kPfRuleBand>(tile, kPfRing, 16, kPfPassRows).bytes : fl2 ? PfLds<kPfRuleBand>(tile, 256, 8, kPfPassRows).bytes
+                        : rule != kPfRuleG ? PfLds<kPfRuleBand>(tile, kPfRing, 8, paired_units ? kPfPairRows : kPfPassRows).bytes : PfLds<kPfRuleG>(tile).bytes;
     if (lds_bytes > 160 * 1024) { set_error("pre-filter tile of %d points needs %d bytes of LDS", tile, lds_bytes); return SFM_E_INVALID; }
     auto launch = [&](auto kernel) -> int {
         const int rc_lds = allow_big_lds(ctx, reinterpret_cast<const void *>(kernel));
@@ -1360,7 +1416,7 @@ int launch_score_prefilter(sfm_pair *pair, ShardSlot &s, hipStream_t stream, con
     else if (wide) rcl = launch(&ransac_score_prefilter<16, 0, kPfRuleBandTile, 0, 0, 1>);
     else if (rule == kPfRuleBandTile && SFM_SW(p, 1) == 14) rcl = launch(&ransac_score_prefilter<16, 0, kPfRuleBandTile, 0, 0, 0, 1>);     // (s_setprio experiments)
     else if (rule == kPfRuleBandTile && SFM_SW(p, 1) == 15) rcl = launch(&ransac_score_prefilter<16, 0, kPfRuleBandTile, 0, 0, 0, 2>);
-    else if (tail_var != 0 && tail_var != kPfVarAnswerEpilogue) {                                                                          // (round 9's pass tail: the parts that did not pay)
+    else if (tail_var != 0 && tail_var != kPfVarAnswerEpilogue && tail_var != kPfVarSinglePass) {                                                                          // (round 9's pass tail: the parts that did not pay)
         rcl = SFM_E_INVALID;
 #define PF_TAIL_CASE(V) case V: rcl = rule == kPfRuleBandPack ? launch(&ransac_score_prefilter<16, V, kPfRuleBandPack>) : launch(&ransac_score_prefilter<16, V, kPfRuleBandTile>); break
         switch (tail_var) {
@@ -1376,6 +1432,7 @@ int launch_score_prefilter(sfm_pair *pair, ShardSlot &s, hipStream_t stream, con
     if (tail_var & kPfVarAnswerEpilogue) rcl = rule == kPfRuleBandPack ? launch(&ransac_score_prefilter<16, kPfVarAnswerEpilogue, kPfRuleBandPack>)
                                                                        : launch(&ransac_score_prefilter<16, kPfVarAnswerEpilogue, kPfRuleBandTile>);
     else if (rule == kPfRuleBandPack) rcl = launch(&ransac_score_prefilter<16, 0, kPfRuleBandPack>);
+    else if (tail_var == kPfVarSinglePass) rcl = launch(&ransac_score_prefilter<16, kPfVarSinglePass, kPfRuleBandTile>);
     else rcl = launch(&ransac_score_prefilter<16, 0, kPfRuleBandTile>);
     (void)var; (void)fl2; (void)wide; (void)tail_var;
     if (rcl != SFM_OK) return rcl;

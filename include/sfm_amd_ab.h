@@ -38,6 +38,10 @@ extern "C" {
  *       on every call; 18 the pre-filter launch sums its counts into counts[] without waiting for an answer, keys from ransac_argmax_counts
  *       behind it, at EVERY size (the product: from 2^21 (hypothesis, tile) partial counts per launch on); 16 / 17 the same, and in the drain
  *       a lane works through up to 1 / 7 further survivors of its ring entry before the rest is re-queued (per-tile form);
+ *       19 the per-tile form prepares TWO passes at once, one hypothesis per lane, at EVERY size, with the summing epilogue (the product:
+ *       from 2^22 partial counts per launch on; profiles/NOTES_r11.md: the headline step 2.8 % shorter, 8 pairs per wavefront 1.2 % longer);
+ *       20 the single passes it replaced, with the summing epilogue, at every size (the product: between 2^21 and 2^22 partial counts) --
+ *       19 and 20 leave the choice between the per-hypothesis and the per-tile form to the product's rule (combine with [3] = 7);
  *   [2] k > 0: minimum hypothesis batches per scoring block (default 8); pre-filter kernel: grid columns;
  *   [3] 1 AUTO never picks SFM_KERNEL_PREFILTER; 2 the round-2 pre-filter kernel (csrc/ab/ransac_prefilter_r2.hip);
  *       3 per-hypothesis records from the stand-alone kernel instead of the lane-solve kernel; 4 the G rule of rounds 2-4

@@ -1,7 +1,7 @@
 """When do the blocks and wavefronts of ransac_score_prefilter start and finish inside ONE launch (sfm_ransac_last_trace)?
 Prints, per configuration: kernel span, block lifetimes (percentiles), how far the wavefront ends of a block are spread,
 per-XCC mean lifetime, and the mean number of wavefronts still running per CU over the span (what the VALU can overlap).
-Run on the GPU box: python profiles/trace_probe.py [hyps ...]"""
+Run on the GPU box: python profiles/trace_probe.py [--sw1=N] [hyps ...]   (--sw1: reserved[1] of the lab bench, e.g. 19 / 20 = paired / single passes)"""
 import json, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -11,6 +11,8 @@ from cuda_sfm_amd_ab import synth
 
 dev = torch.device("cuda", 0)
 ctx = S.Context(0, torch.cuda.current_stream().cuda_stream)
+SW1 = [int(a[6:]) for a in sys.argv[1:] if a.startswith("--sw1=")]
+sys.argv = [a for a in sys.argv if not a.startswith("--sw1=")]
 cases = [(4096, int(h)) for h in sys.argv[1:]] or [(4096, 1 << 20), (4096, 131072), (16384, 1 << 20)]
 for n, H in cases:
     scene = synth.two_view_scene(n)
@@ -18,6 +20,8 @@ for n, H in cases:
     pair = S.ImagePair(ctx, scene["K"], scene["Kinv"], 2, n)
     pair.fillXU(d_sift)
     p = S.default_params(n, num_hypotheses=H, kernel=S.KERNEL_PREFILTER)
+    if SW1:
+        p.reserved[1] = SW1[0]
     for _ in range(10):
         pair.ransac_score(p)
     torch.cuda.synchronize()
@@ -33,7 +37,7 @@ for n, H in cases:
     spread = wave_end.max(axis=1) - wave_end.min(axis=1)
     # mean number of live wavefronts (of 16 per block) over the kernel span
     live = (wave_end - start[:, None]).sum() / (span * len(t))
-    out = {"matches": n, "hypotheses": H, "blocks": len(t), "span_us": round(span, 1), "last_start_us": round(float(start.max()), 1),
+    out = {"sw1": SW1[0] if SW1 else 0, "matches": n, "hypotheses": H, "blocks": len(t), "span_us": round(span, 1), "last_start_us": round(float(start.max()), 1),
            "block_lifetime_us_p0_10_50_90_100": [round(float(x), 1) for x in np.percentile(life, [0, 10, 50, 90, 100])],
            "block_end_us_p10_50_90": [round(float(x), 1) for x in np.percentile(blk_end, [10, 50, 90])],
            "wave_end_spread_in_block_us_p50_90_100": [round(float(x), 1) for x in np.percentile(spread, [50, 90, 100])],
