@@ -125,7 +125,7 @@ $(GEOMTEST): tests/cpp/geom_test.cpp $(PKG)/host/geomFuncs.h $(PKG)/host/sfm_io.
 
 # CPU-only: the host-compiled arithmetic check of the non-GPU tests (the fakeccl target, which needs the gfx950 build and the RCCL
 # header, is a target of its own and part of `all`)
-hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libchainadjustcheck.so tests/hostcheck/libringcheck.so tests/hostcheck/libfuseringcheck.so tests/hostcheck/libringadjustcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/hostcheck/pfdecodecheck tests/hostcheck/libpfpaircheck.so
+hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libchainadjustcheck.so tests/hostcheck/libringcheck.so tests/hostcheck/libfuseringcheck.so tests/hostcheck/libringadjustcheck.so tests/hostcheck/libintersectcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/hostcheck/pfdecodecheck tests/hostcheck/libpfpaircheck.so
 
 # TEST HARNESS: comm.cpp linked against a shared-memory stand-in for the nine RCCL calls it makes, so that a 1-GPU box can run the
 # exchange code with two real ranks (tests/test_gpu_fakeccl.py); the product's libsfm_amd_rccl.so is linked against librccl
@@ -192,6 +192,13 @@ tests/hostcheck/libfuseringcheck.so: tests/hostcheck/fuseringcheck.hip $(CSRC)/f
 tests/hostcheck/libringadjustcheck.so: tests/hostcheck/ringadjustcheck.hip $(CSRC)/ring_adjust_math.hpp $(CSRC)/chain_adjust_math.hpp $(CSRC)/fuse_math.hpp $(CSRC)/view_points_math.hpp $(CSRC)/register_math.hpp $(CSRC)/refine_math.hpp $(CSRC)/device_math.hpp include/sfm_amd.h
 	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
 
+# the arithmetic of sfm_intersect_tracks (intersect_math.hpp over fuse_math.hpp: the linear intersection, the eligibility test, the
+# start choice, the class mapping) and a serial driver of the whole call that walks every track in list order, for
+# tests/test_intersect_host.py and the byte comparison of tests/test_gpu_intersect.py; the no-scratch pin of intersect.hip reads
+# $(BUILD)/intersect.usage.txt, which the object rule above writes
+tests/hostcheck/libintersectcheck.so: tests/hostcheck/intersectcheck.hip $(CSRC)/intersect_math.hpp $(CSRC)/chain_adjust_math.hpp $(CSRC)/fuse_math.hpp $(CSRC)/view_points_math.hpp $(CSRC)/register_math.hpp $(CSRC)/refine_math.hpp $(CSRC)/device_math.hpp include/sfm_amd.h
+	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
+
 # the scoring block's dynamic LDS size (prefilter_lds.hpp), host-compiled for tests/test_register_budget.py
 tests/hostcheck/libpfldscheck.so: tests/hostcheck/pfldscheck.hip $(CSRC)/prefilter_lds.hpp $(CSRC)/prefilter_record.hpp $(CSRC)/prefilter_math.hpp $(CSRC)/device_math.hpp
 	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
@@ -222,7 +229,7 @@ tests/hostcheck/libbufferrangescheck.so: tests/hostcheck/bufferrangescheck.cpp $
 	g++ -O2 -std=c++17 -Wall -fPIC -shared -o $@ $<
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(APDEMO) $(FCDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libchainadjustcheck.so tests/hostcheck/libringcheck.so tests/hostcheck/libfuseringcheck.so tests/hostcheck/libringadjustcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/hostcheck/pfdecodecheck tests/hostcheck/libpfpaircheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
+	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(APDEMO) $(FCDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libchainadjustcheck.so tests/hostcheck/libringcheck.so tests/hostcheck/libfuseringcheck.so tests/hostcheck/libringadjustcheck.so tests/hostcheck/libintersectcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/hostcheck/pfdecodecheck tests/hostcheck/libpfpaircheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all ab oracle hostcheck fakeccl clean

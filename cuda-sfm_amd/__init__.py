@@ -88,6 +88,7 @@ EXPORTS = [
     "sfm_adjust_chain_default_params", "sfm_adjust_chain",
     "sfm_ring_default_params", "sfm_close_ring", "sfm_fuse_ring_default_params", "sfm_fuse_ring",
     "sfm_adjust_ring_default_params", "sfm_adjust_ring",
+    "sfm_intersect_default_params", "sfm_intersect_tracks",
 ]
 AB_EXPORTS = ["sfm_ransac_last_phases", "sfm_ransac_last_trace", "sfm_prefilter_probe", "sfm_prefilter_band_probe"]      # include/sfm_amd_ab.h
 if AB:
@@ -302,7 +303,25 @@ class AdjustRingOut(C.Structure):
     _fields_ = [("d_cams", C.c_void_p), ("d_points", C.c_void_p), ("d_used", C.c_void_p), ("d_err", C.c_void_p), ("d_report", C.c_void_p)]
 
 
+class IntersectParams(C.Structure):
+    """sfm_intersect_params (include/sfm_amd.h)."""
+    _fields_ = [("threshold_px", C.c_float), ("max_iterations", C.c_int32), ("huber_px", C.c_float), ("min_rel_decrease", C.c_float),
+                ("initial_lambda", C.c_float), ("wave_min_views", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class IntersectIn(C.Structure):
+    """sfm_intersect_in (include/sfm_amd.h): the host array of pair handles, a track table in sfm_fuse_out's layout, a camera table."""
+    _fields_ = [("pairs", C.POINTER(C.c_void_p)), ("d_cams", C.c_void_p), ("d_track_offset", C.c_void_p), ("d_obs_cam", C.c_void_p),
+                ("d_obs_record", C.c_void_p), ("d_points", C.c_void_p), ("d_flags", C.c_void_p), ("d_counts", C.c_void_p), ("d_skip", C.c_void_p)]
+
+
+class IntersectOut(C.Structure):
+    """sfm_intersect_out (include/sfm_amd.h): the caller's device buffers."""
+    _fields_ = [("d_points", C.c_void_p), ("d_flags", C.c_void_p), ("d_err", C.c_void_p), ("d_counts", C.c_void_p)]
+
+
 FUSE_COUNTS = ("tracks", "observations", "refined", "kept", "segments", "longest_track")      # sfm_fuse_out.d_counts[0..5]
+INTERSECT_COUNTS = ("tracks", "intersected", "refined", "kept", "copied", "from_linear", "no_start", "promoted")      # sfm_intersect_out.d_counts
 
 _vp = C.c_void_p
 _lib.sfm_last_error.restype = C.c_char_p
@@ -411,6 +430,9 @@ _lib.sfm_fuse_ring_default_params.restype = None
 _lib.sfm_adjust_ring_default_params.argtypes = [C.POINTER(AdjustRingParams)]
 _lib.sfm_adjust_ring_default_params.restype = None
 _lib.sfm_adjust_ring.argtypes = [_vp, C.POINTER(AdjustRingIn), C.c_int, C.POINTER(AdjustRingParams), C.POINTER(AdjustRingOut)]
+_lib.sfm_intersect_default_params.argtypes = [C.POINTER(IntersectParams)]
+_lib.sfm_intersect_default_params.restype = None
+_lib.sfm_intersect_tracks.argtypes = [_vp, C.POINTER(IntersectIn), C.c_int, C.POINTER(IntersectParams), C.POINTER(IntersectOut)]
 _lib.sfm_fuse_ring.argtypes = [_vp, C.POINTER(FusePairIn), C.c_int, C.POINTER(FuseLinkIn), C.POINTER(FuseRingParams), C.POINTER(FuseOut), _vp]
 _lib.sfm_fuse_chain.argtypes = [_vp, C.POINTER(FusePairIn), C.c_int, C.POINTER(FuseLinkIn), C.POINTER(FuseParams), C.POINTER(FuseOut)]
 if AB:
@@ -1077,6 +1099,71 @@ def adjust_ring(pairs, fused, ring_report, **kw):
     adjust_ring_enqueue(ctx, pairs, (root, cams, off, ocam, orec, pts, flags, counts, ring_report), params, outs)
     ctx.synchronize()
     return adjust_ring_results(outs, k, N, int(counts[0].item()))
+
+
+_INTERSECT_FIELDS = {f for f, _ in IntersectParams._fields_}
+
+
+def intersect_params(**kw):
+    """sfm_intersect_params with the library's defaults (sfm_fuse_params' own: 4 px, 5 iterations, Huber 1 px, 1e-6, lambda 1e-3;
+    wave_min_views 0 = the library's split between the lane and the wavefront kernel), fields overridden by kw."""
+    p = IntersectParams()
+    _lib.sfm_intersect_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "reserved":
+            for i, x in enumerate(v):
+                p.reserved[i] = int(x)
+        elif k in _INTERSECT_FIELDS:
+            setattr(p, k, v)
+        else:
+            raise TypeError(f"intersect_params: no field {k!r} in sfm_intersect_params")
+    return p
+
+
+def intersect_tracks_enqueue(ctx, pairs, table, params, outs):
+    """sfm_intersect_tracks (enqueue only).  pairs: the ImagePairs of the table; table: device tensors / pointers (cams, track_offset,
+    obs_cam, obs_record, points, flags, counts, skip) -- a track table in sfm_fuse_out's layout, any camera table in that layout,
+    skip None or one byte per track; outs: device tensors / pointers in the order of sfm_intersect_out (err may be None)."""
+    k = len(pairs)
+    handles = (C.c_void_p * max(k, 1))(*[p._h.value if p is not None else None for p in pairs])
+    i = IntersectIn(C.cast(handles, C.POINTER(C.c_void_p)), *[_ptr(t) for t in table]) if table is not None else None
+    o = IntersectOut(*[_ptr(t) for t in outs]) if outs is not None else None
+    _check(_lib.sfm_intersect_tracks(ctx._h if ctx is not None else None, C.byref(i) if i is not None else None, k,
+                                     C.byref(params) if params is not None else None, C.byref(o) if o is not None else None), "sfm_intersect_tracks")
+
+
+def intersect_tracks_buffers(device, N):
+    """Output tensors of one intersect_tracks call in the order of sfm_intersect_out, for N records in all."""
+    e = lambda n, dt: torch.empty(int(n), dtype=dt, device=device)
+    return (e(4 * N, torch.float32), e(N, torch.uint8), e(N, torch.float32), e(8, torch.int32))
+
+
+def intersect_tracks_results(outs, N, T):
+    """The tensors of intersect_tracks_buffers -> a dict of numpy arrays trimmed to the T tracks: points (4, T), flags (T), err (T),
+    and counts as a dict (INTERSECT_COUNTS)."""
+    pts, flags, err, counts = (t.cpu().numpy() for t in outs)
+    return dict(points=pts.reshape(4, N)[:, :T].copy(), flags=flags[:T].copy(), err=err[:T].copy(),
+                counts={name: int(counts[i]) for i, name in enumerate(INTERSECT_COUNTS)})
+
+
+def intersect_tracks(pairs, fused, cams=None, skip=None, **kw):
+    """Every track of a fused table intersected over all its views under a camera table.  pairs: the ImagePairs of the table; fused:
+    the device tensors of a fuse_chain_enqueue / fuse_ring_enqueue call in the order of sfm_fuse_out; cams: a device tensor of 24 k
+    floats (adjust_chain's or adjust_ring's cameras), None = the table's own; skip: None or a device tensor of one byte per track
+    (an adjustment's used flags: those tracks are copied through); kw are IntersectParams fields.  Allocates the outputs, waits
+    once and returns intersect_tracks_results' dict."""
+    params = intersect_params(**kw)
+    k = len(pairs)
+    if k == 0:                                                                 # no pair, no context: nothing to enqueue
+        return dict(counts=dict.fromkeys(INTERSECT_COUNTS, 0))
+    ctx = pairs[0].ctx
+    dev = torch.device("cuda", ctx.device)
+    N = sum(p.num_points for p in pairs)
+    frames, root, own, track, off, ocam, orec, pts, flags, err, counts = fused
+    outs = intersect_tracks_buffers(dev, N)
+    intersect_tracks_enqueue(ctx, pairs, (cams if cams is not None else own, off, ocam, orec, pts, flags, counts, skip), params, outs)
+    ctx.synchronize()
+    return intersect_tracks_results(outs, N, int(counts[0].item()))
 
 
 def sift_temp_layout(width, height, num_octaves=5, scale_up=False):

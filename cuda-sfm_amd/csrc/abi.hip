@@ -1757,6 +1757,68 @@ int sfm_adjust_ring(sfm_ctx *ctx, const sfm_adjust_ring_in *in, int num_pairs, c
     return launch_adjust_ring(ctx, fp.data(), num_pairs, *in, *p, *out);        // reads the pairs: no stage changes
 }
 
+// ---- every track of a fused table intersected under a given camera table (intersect.hip) -----------
+void sfm_intersect_default_params(sfm_intersect_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->threshold_px = 4.0f;
+    p->max_iterations = 5;
+    p->huber_px = 1.0f;
+    p->min_rel_decrease = 1e-6f;
+    p->initial_lambda = 1e-3f;
+    p->wave_min_views = 0;                                // the library's default (intersect_math.hpp)
+}
+
+int sfm_intersect_tracks(sfm_ctx *ctx, const sfm_intersect_in *in, int num_pairs, const sfm_intersect_params *p, const sfm_intersect_out *out)
+{
+    // sfm_adjust_chain's contract in its order: the checks that need no device first, all of them before anything is enqueued
+    SFM_REQUIRE(p, SFM_E_INVALID, "null params");
+    SFM_REQUIRE(num_pairs >= 0 && num_pairs <= 4096, SFM_E_INVALID, "num_pairs %d outside 0..4096", num_pairs);
+    int rc = check_lm_params(*p, "sfm_intersect_params", 50);
+    if (rc != SFM_OK) return rc;
+    SFM_REQUIRE(isfinite(p->threshold_px) && p->threshold_px > 0.0f, SFM_E_INVALID, "threshold_px must be finite and > 0");
+    SFM_REQUIRE(p->wave_min_views == 0 || p->wave_min_views >= 2, SFM_E_INVALID, "wave_min_views %d is neither 0 nor at least 2", p->wave_min_views);
+    if (num_pairs == 0) return SFM_OK;
+    SFM_REQUIRE(ctx && in && out, SFM_E_INVALID, "null context, in or out");
+    SFM_REQUIRE(in->pairs && in->d_cams && in->d_track_offset && in->d_obs_cam && in->d_obs_record && in->d_points && in->d_flags && in->d_counts,
+                SFM_E_INVALID, "every field of sfm_intersect_in but d_skip is required");
+    SFM_REQUIRE(out->d_points && out->d_flags && out->d_counts, SFM_E_INVALID, "every buffer of sfm_intersect_out but d_err is required");
+    rc = list_entries_present(in->pairs, num_pairs, "pairs[%d]: null pair");
+    if (rc == SFM_OK) rc = list_one_context_each_once(in->pairs, num_pairs, ctx, "pairs[%d]: the pair belongs to another context", "pairs", "",
+                                                      "a table holds a pair once");
+    if (rc != SFM_OK) return rc;
+    long long total = 0;
+    for (int i = 0; i < num_pairs; ++i) total += in->pairs[i]->n;
+    SFM_REQUIRE(total <= (1ll << 26), SFM_E_INVALID, "%lld records in all: more than 2^26", total);
+    {
+        // no output on an input or on another output: every range its own owner, so the sweep is the whole check
+        const size_t N = (size_t)total, k = (size_t)num_pairs;
+        std::vector<BufferRange> r = {
+            { in->d_cams, k * 96, false, 0, "in.d_cams" }, { in->d_track_offset, (N + 1) * 4, false, 1, "in.d_track_offset" },
+            { in->d_obs_cam, N * 8, false, 2, "in.d_obs_cam" }, { in->d_obs_record, N * 8, false, 3, "in.d_obs_record" },
+            { in->d_points, N * 16, false, 4, "in.d_points" }, { in->d_flags, N, false, 5, "in.d_flags" },
+            { in->d_counts, 32, false, 6, "in.d_counts" }, { in->d_skip, N, false, 7, "in.d_skip" },
+            { out->d_points, N * 16, true, 8, "out.d_points" }, { out->d_flags, N, true, 9, "out.d_flags" },
+            { out->d_err, N * 4, true, 10, "out.d_err" }, { out->d_counts, 32, true, 11, "out.d_counts" } };
+        if (const RangeConflict c = first_conflict_across_owners(r))
+            SFM_REQUIRE(false, SFM_E_INVALID, "%s overlaps %s", c.a->out ? c.a->name : c.b->name, c.a->out ? c.b->name : c.a->name);      // the output first
+    }
+    rc = list_flush(in->pairs, num_pairs);
+    if (rc == SFM_OK) rc = list_stages(in->pairs, num_pairs, "pairs", "", [](int) { return (uint32_t)kPoints; });
+    if (rc != SFM_OK) return rc;
+    SFM_HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<FusePair> fp((size_t)num_pairs);
+    for (int i = 0; i < num_pairs; ++i) {
+        const sfm_pair *pr = in->pairs[i];
+        FusePair &f = fp[(size_t)i];
+        memset(&f, 0, sizeof(f));
+        f.X0 = pr->d_X[0]; f.X1 = pr->d_X[1]; f.K = pr->d_K;                    // what fuse_view reads
+        f.n = pr->n; f.ld = pr->ld;
+    }
+    return launch_intersect_tracks(ctx, fp.data(), num_pairs, *in, *p, *out);   // reads the pairs: no stage changes
+}
+
 // ---- a ring of aligned pairs closed: the drift spread over the links (ring.hip) -------------------
 void sfm_ring_default_params(sfm_ring_params *p)
 {

@@ -210,7 +210,7 @@ struct sfm_ctx {
     sfm::JobArray refine_jobs, register_jobs, view_points_jobs, adjust_jobs, align_jobs, fuse_jobs, chain_jobs, ring_jobs;
     void *fuse_ws = nullptr;           // sfm_fuse_chain: per-node keys, successors, path lengths and classes, the block counts (fuse.hip)
     size_t fuse_ws_bytes = 0;
-    void *chain_ws = nullptr;          // sfm_adjust_chain and sfm_adjust_ring: states, points, partial bands, the band and the segments (chain_adjust.hip)
+    void *chain_ws = nullptr;          // sfm_adjust_chain and sfm_adjust_ring: states, points, partial bands, the band and the segments (chain_adjust.hip); sfm_intersect_tracks: the list of long tracks
     size_t chain_ws_bytes = 0;
     void *ring_ws = nullptr;           // sfm_close_ring: the fp64 frames, weights and running sums, the seam's block partials (ring.hip)
     size_t ring_ws_bytes = 0;
@@ -441,6 +441,9 @@ int launch_adjust_chain(sfm_ctx *ctx, const FusePair *pairs, int num_pairs, cons
 // ring_adjust.hip: the same over a CLOSED ring, one camera per view (the chain's job array and work buffer)
 int launch_adjust_ring(sfm_ctx *ctx, const FusePair *pairs, int num_pairs, const sfm_adjust_ring_in &in, const sfm_adjust_ring_params &p,
                        const sfm_adjust_ring_out &out);
+// intersect.hip: every track of a fused table intersected under a camera table (the chain's job array and work buffer)
+int launch_intersect_tracks(sfm_ctx *ctx, const FusePair *pairs, int num_pairs, const sfm_intersect_in &in, const sfm_intersect_params &p,
+                            const sfm_intersect_out &out);
 
 // ring.hip: the drift of a ring measured and spread over its links; links: HOST array, last: pair k - 1 (points, valid, X1, K, n, ld
 // resolved by the caller)

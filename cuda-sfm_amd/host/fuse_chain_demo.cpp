@@ -15,6 +15,10 @@
 // SfM::adjust_chain over the fused model follows, one `chain adjust:` line per segment is printed and the PLY holds the adjusted
 // points.  With `loop`, adjust_iterations > 0 and a ring that closed, SfM::adjust_ring follows as well (one camera per view, the
 // seam tracks used): one `ring adjust:` line behind the `chain adjust:` lines, and the PLY holds ITS points.
+// An adjustment moves every camera and rewrites only the tracks it used, so behind the last adjustment SfM::intersect_tracks brings
+// every other track (kept, over-long, seam tracks of a plain chain adjustment) under the adjusted cameras, the used ones skipped:
+// one `intersect:` line with its eight counts -- on stderr: stdout keeps exactly the lines it had with an adjustment -- and the PLY
+// holds its points.  Without an adjustment there is no such line and nothing changes.
 // Plain C++: needs only the facade headers and libsfm_amd.so.
 #include <algorithm>
 #include <cmath>
@@ -126,13 +130,20 @@ int main(int argc, char **argv)
                         rep.num_tracks, (double)rep.initial_rms_px, (double)rep.final_rms_px, rep.iterations);
         }
         points = adj.points;
+        std::vector<float> cams = adj.cams;
+        std::vector<uint8_t> used = adj.used;
         if (loop && fused.report.status == SFM_RING_CLOSED) {          // the ring's own adjustment: one camera per view, the seam tracks used
             const SfM::AdjustedRing ra = SfM::adjust_ring(pairs.data(), count, fused, adjust_iterations);
             const sfm_adjust_ring_report &rep = ra.report;
             std::printf("ring adjust: %d cameras, %d tracks, %d seam tracks, rms %.6g -> %.6g px, %d iterations\n", rep.num_cameras, rep.num_tracks,
                         rep.num_seam_tracks, (double)rep.initial_rms_px, (double)rep.final_rms_px, rep.iterations);
-            points = ra.points;
+            points = ra.points; cams = ra.cams; used = ra.used;
         }
+        // the tracks the last adjustment did not use, under its cameras: one consistent cloud
+        const SfM::IntersectedTracks it = SfM::intersect_tracks(pairs.data(), count, model, cams.data(), points.data(), used.data());
+        std::fprintf(stderr, "intersect: %d tracks, %d intersected, %d refined, %d kept, %d copied, %d from the linear start, %d without a start, %d promoted\n",
+                    it.counts[0], it.counts[1], it.counts[2], it.counts[3], it.counts[4], it.counts[5], it.counts[6], it.counts[7]);
+        points = it.points;
     }
 
     // the first segment's tracks: one point each

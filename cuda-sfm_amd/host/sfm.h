@@ -863,6 +863,78 @@ inline AdjustedRing adjust_ring(Image_pair *const *pairs, int count, const Fused
     return r;
 }
 
+// what intersect_tracks returns, in host memory
+struct IntersectedTracks {
+    std::vector<float> points;          // 4 x T (leading dimension T)
+    std::vector<uint8_t> flags;         // T: SFM_FUSE_*, every track in the class it came in
+    std::vector<float> err;             // T: largest pixel error over the track's views
+    int32_t counts[8];                  // tracks, re-intersected, REFINED class, KEPT class, copied through, started from the linear
+                                        // intersection, without an eligible start, promoted
+};
+
+// Every track of a fused model intersected over all its views under a camera table (sfm_intersect_tracks): pairs, count: what
+// fuse_chain / fuse_ring took; model: what it returned; cams: 24 x count floats in FusedModel::cams' layout (an adjustment's cameras),
+// null = the model's own; points: 4 x T, the columns to start from (an adjustment's points), null = the model's own; skip: T bytes
+// (an adjustment's used flags: those tracks are copied through), or null.  The model is uploaded again; one wait at the end.
+inline IntersectedTracks intersect_tracks(Image_pair *const *pairs, int count, const FusedModel &model, const float *cams = nullptr,
+                                          const float *points = nullptr, const uint8_t *skip = nullptr, int max_iterations = 5,
+                                          float threshold_px = 4.0f)
+{
+    IntersectedTracks r;
+    memset(r.counts, 0, sizeof(r.counts));
+    if (count <= 0) return r;
+    sfm_ctx *ctx = sfm_facade::context();
+    sfm_intersect_params p;
+    sfm_intersect_default_params(&p);
+    p.max_iterations = max_iterations;
+    p.threshold_px = threshold_px;
+    std::vector<sfm_pair *> handles;
+    size_t N = 0;
+    for (int i = 0; i < count; ++i) { handles.push_back(pairs[i] ? pairs[i]->handle() : nullptr); N += pairs[i] ? (size_t)pairs[i]->numPoints() : 0; }
+    const size_t k = (size_t)count, T = (size_t)model.tracks, M = (size_t)model.observations;
+    // inputs and outputs in ONE block, every array at a multiple of 16 bytes
+    auto up = [](size_t b) { return (b + 15) / 16 * 16; };
+    const size_t sizes[12] = { 96 * k, 4 * (N + 1), 8 * N, 8 * N, 16 * N, N, 32, N, 16 * N, N, 4 * N, 32 };
+    size_t at[13];
+    at[0] = 0;
+    for (int q = 0; q < 12; ++q) at[q + 1] = at[q] + up(sizes[q] + 1);
+    detail::DeviceBlock mem(at[12]);
+    const float *src = points ? points : model.points.data();
+    std::vector<float> pts(4 * N, 0.0f);
+    for (int c = 0; c < 4; ++c) std::copy(src + (size_t)c * T, src + (size_t)c * T + T, pts.begin() + (size_t)c * N);
+    const int32_t counts[8] = { model.tracks, model.observations, model.refined, model.kept, model.segments, model.longest_track, 0, 0 };
+    SFM_FACADE_CALL(sfm_copy_to_device(ctx, mem.p + at[0], cams ? cams : model.cams.data(), 96 * k));
+    SFM_FACADE_CALL(sfm_copy_to_device(ctx, mem.p + at[1], model.track_offset.data(), 4 * (T + 1)));
+    if (M) {
+        SFM_FACADE_CALL(sfm_copy_to_device(ctx, mem.p + at[2], model.obs_cam.data(), 4 * M));
+        SFM_FACADE_CALL(sfm_copy_to_device(ctx, mem.p + at[3], model.obs_record.data(), 4 * M));
+    }
+    if (N) SFM_FACADE_CALL(sfm_copy_to_device(ctx, mem.p + at[4], pts.data(), 16 * N));
+    if (T) SFM_FACADE_CALL(sfm_copy_to_device(ctx, mem.p + at[5], model.flags.data(), T));
+    SFM_FACADE_CALL(sfm_copy_to_device(ctx, mem.p + at[6], counts, sizeof(counts)));
+    if (T && skip) SFM_FACADE_CALL(sfm_copy_to_device(ctx, mem.p + at[7], skip, T));
+    sfm_intersect_in in;
+    in.pairs = handles.data();
+    in.d_cams = reinterpret_cast<const float *>(mem.p + at[0]); in.d_track_offset = reinterpret_cast<const int32_t *>(mem.p + at[1]);
+    in.d_obs_cam = reinterpret_cast<const int32_t *>(mem.p + at[2]); in.d_obs_record = reinterpret_cast<const int32_t *>(mem.p + at[3]);
+    in.d_points = reinterpret_cast<const float *>(mem.p + at[4]); in.d_flags = reinterpret_cast<const uint8_t *>(mem.p + at[5]);
+    in.d_counts = reinterpret_cast<const int32_t *>(mem.p + at[6]);
+    in.d_skip = skip ? reinterpret_cast<const uint8_t *>(mem.p + at[7]) : nullptr;
+    sfm_intersect_out o;
+    o.d_points = reinterpret_cast<float *>(mem.p + at[8]); o.d_flags = reinterpret_cast<uint8_t *>(mem.p + at[9]);
+    o.d_err = reinterpret_cast<float *>(mem.p + at[10]); o.d_counts = reinterpret_cast<int32_t *>(mem.p + at[11]);
+    SFM_FACADE_CALL(sfm_intersect_tracks(ctx, &in, count, &p, &o));
+    r.points.resize(4 * T); r.flags.resize(T); r.err.resize(T);
+    SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.counts, o.d_counts, sizeof(r.counts)));
+    if (T) {
+        SFM_FACADE_CALL(sfm_copy_to_host(ctx, pts.data(), o.d_points, 16 * N));
+        for (int c = 0; c < 4; ++c) std::copy(pts.begin() + (size_t)c * N, pts.begin() + (size_t)c * N + T, r.points.begin() + (size_t)c * T);
+        SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.flags.data(), o.d_flags, T));
+        SFM_FACADE_CALL(sfm_copy_to_host(ctx, r.err.data(), o.d_err, 4 * T));
+    }
+    return r;
+}
+
 } // namespace SfM
 
 #endif

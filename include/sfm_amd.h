@@ -854,6 +854,60 @@ void sfm_adjust_ring_default_params(sfm_adjust_ring_params *p);
 int  sfm_adjust_ring(sfm_ctx *ctx, const sfm_adjust_ring_in *in, int num_pairs, const sfm_adjust_ring_params *p,
                      const sfm_adjust_ring_out *out);                            /* enqueue only */
 
+/* ---- every track of a fused table intersected again under a given camera table --------------------
+ * Reads the pairs, a track table in sfm_fuse_out's layout (a chain, a chain with cuts or a ring) and ANY camera table in that
+ * layout -- sfm_fuse_chain's, sfm_adjust_chain's or sfm_adjust_ring's: slot d_obs_cam[o] of d_cams holds the camera of
+ * observation o.  An adjustment moves every camera and rewrites only the columns of the tracks it used; this call brings the
+ * others (KEPT, SEAM_KEPT, over-long, seam tracks after sfm_adjust_chain, tracks that started behind a camera) into the same frame.
+ * Per track t < T = d_counts[0] (the others are not touched):
+ *   copied through -- its flag is not 1..4, it has fewer than two views, or d_skip[t] != 0: column and flag as they came in, d_err
+ *     the largest pixel error over its views under d_cams at that column (+inf behind a camera: sfm_adjust_chain's rule).  With
+ *     d_skip = sfm_adjust_*_out.d_used the jointly adjusted points stay.
+ *   else two start candidates: C, the input column X / W, and L, the linear intersection of the views' rays (per view the rows
+ *     (x r3 - r1) X = t1 - x t3 and (y r3 - r2) X = t2 - y t3; the 3 x 3 normal equations in fp64 in list order; a singular system
+ *     gives no L).  A candidate is eligible when it is finite and in front of every view.  The start is the eligible candidate with
+ *     the smaller robust cost, C on a tie; with none the column and flag come back as they came in and d_err is +inf.
+ *   from the start sfm_fuse_chain's point Levenberg-Marquardt over all views and its acceptance test at threshold_px: accepted, the
+ *     result is stored with SFM_FUSE_REFINED (SFM_FUSE_SEAM_REFINED where the input flag was 3 or 4), else the START with the KEPT
+ *     flag of the same class; d_err is the largest pixel error at the LM result.
+ * Tracks of at least wave_min_views views are intersected by one wavefront each, the others by one lane each; the bytes written do
+ * not depend on that split.  The call READS the pairs and writes only the caller's buffers: no stage, buffer id or getter belongs
+ * to it.  Integer atomics only: two calls give the same bytes. */
+typedef struct sfm_intersect_params {
+    float   threshold_px;                                 /* acceptance, the registration's inlier test; default 4.0 */
+    int32_t max_iterations;                               /* point LM, accepted + rejected, 0..50; default 5         */
+    float   huber_px, min_rel_decrease, initial_lambda;   /* 1.0 / 1e-6 / 1e-3                                        */
+    int32_t wave_min_views;                               /* 0 = the library's default (32), else 2..INT32_MAX: a pure
+                                                             performance knob                                         */
+    int32_t reserved[4];                                  /* must be zero (else SFM_E_INVALID)                        */
+} sfm_intersect_params;
+typedef struct sfm_intersect_in {      /* pairs: HOST array; the rest DEVICE, in sfm_fuse_out's layout; all required unless marked */
+    sfm_pair *const *pairs;
+    const float   *d_cams;             /* 24 x k                                                                      */
+    const int32_t *d_track_offset;     /* N + 1                                                                       */
+    const int32_t *d_obs_cam;          /* 2N                                                                          */
+    const int32_t *d_obs_record;       /* 2N                                                                          */
+    const float   *d_points;           /* 4 x N, leading dimension N                                                  */
+    const uint8_t *d_flags;            /* N                                                                           */
+    const int32_t *d_counts;           /* 8: [0] = T and [1] = M are read, on the device                              */
+    const uint8_t *d_skip;             /* N, optional: != 0 = the track is copied through                             */
+} sfm_intersect_in;
+typedef struct sfm_intersect_out {     /* DEVICE buffers of the caller; all required unless marked                    */
+    float   *d_points;     /* 4 x N, leading dimension N                                                              */
+    uint8_t *d_flags;      /* N                                                                                       */
+    float   *d_err;        /* N, optional                                                                             */
+    int32_t *d_counts;     /* 8: T, re-intersected, REFINED + SEAM_REFINED, KEPT + SEAM_KEPT (both of the re-intersected),
+                              copied through, started from L, without an eligible start, promoted (KEPT class in, REFINED
+                              class out)                                                                              */
+} sfm_intersect_out;
+void sfm_intersect_default_params(sfm_intersect_params *p);
+/* num_pairs 0..4096, N (the pairs' records in all) at most 2^26.  Zero pairs is SFM_OK and writes nothing.  Every pair belongs
+ * to ctx, is listed once and needs its normalised observations and K (the points stage).  No output may overlap an input (d_skip
+ * included) or another output.  Every check precedes the first enqueue: on SFM_E_INVALID / SFM_E_STATE (the text names pairs[i])
+ * nothing is written.  The table is trusted as sfm_adjust_chain trusts it.  The work buffer belongs to the context. */
+int  sfm_intersect_tracks(sfm_ctx *ctx, const sfm_intersect_in *in, int num_pairs, const sfm_intersect_params *p,
+                          const sfm_intersect_out *out);                         /* enqueue only */
+
 /* ---- accessors (the reference keeps these private; needed for parity checks) ------------------ */
 #define SFM_BUF_X0      0   /* float 3 x ld   normalised coords image 1 (ld = sfm_pair_ld)   */
 #define SFM_BUF_X1      1
