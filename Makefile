@@ -137,10 +137,12 @@ $(FAKECCL): $(CSRC)/comm.cpp tests/fake_ccl/fake_ccl.cpp include/sfm_amd_comm.h 
 tests/hostcheck/libhostcheck.so: tests/hostcheck/hostcheck.hip $(CSRC)/device_math.hpp $(CSRC)/sift_math.hpp $(CSRC)/prefilter_math.hpp $(CSRC)/match_prefilter_math.hpp
 	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
 
-# the two-view bundle adjustment's per-point arithmetic (refinecheck.hip) and the LM control (lmcheck.hip) of refine_math.hpp,
-# host-compiled for tests/test_refine_host.py and tests/test_lm_control_host.py
-tests/hostcheck/librefinecheck.so: tests/hostcheck/refinecheck.hip tests/hostcheck/lmcheck.hip $(CSRC)/refine_math.hpp $(CSRC)/device_math.hpp include/sfm_amd.h
-	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ tests/hostcheck/refinecheck.hip tests/hostcheck/lmcheck.hip
+# the two-view bundle adjustment's per-point arithmetic (refinecheck.hip), a serial driver of the whole call (refineruncheck.hip:
+# rc_run, the fp64 sums in the solve block's order) and the LM control (lmcheck.hip) of refine_math.hpp, host-compiled for
+# tests/test_refine_host.py, tests/test_refine_run_host.py, tests/test_lm_control_host.py and the byte comparison of
+# tests/test_gpu_refine_host_build.py
+tests/hostcheck/librefinecheck.so: tests/hostcheck/refinecheck.hip tests/hostcheck/refineruncheck.hip tests/hostcheck/lmcheck.hip $(CSRC)/refine_math.hpp $(CSRC)/device_math.hpp include/sfm_amd.h
+	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ tests/hostcheck/refinecheck.hip tests/hostcheck/refineruncheck.hip tests/hostcheck/lmcheck.hip
 
 # the view registration's arithmetic (register_math.hpp: P3P, sampler, inlier test, pose Jacobian), host-compiled for
 # tests/test_register_host.py and the count parity of tests/test_gpu_register.py

@@ -73,7 +73,10 @@ __device__ __forceinline__ void refine_start_block(const RefineArgs &a, const in
     bool pass = false;
     if (j < a.n && a.mask[j]) {
         float pt[4];
-        triangulate_point(a.X0[j], a.X0[(size_t)a.ld + j], a.X1[j], a.X1[(size_t)a.ld + j], Pm, kRefineSweeps, pt);
+        // the rays as the residuals see them: x / z, y / z (z = 1 after fillXU, where the division changes nothing; sfm_set_points
+        // takes any z)
+        const float z0 = a.X0[2 * (size_t)a.ld + j], z1 = a.X1[2 * (size_t)a.ld + j];
+        triangulate_point(a.X0[j] / z0, a.X0[(size_t)a.ld + j] / z0, a.X1[j] / z1, a.X1[(size_t)a.ld + j] / z1, Pm, kRefineSweeps, pt);
         float z2 = Pm[8] * pt[0];
 #pragma unroll
         for (int k = 1; k < 4; ++k) z2 = fmaf(Pm[8 + k], pt[k], z2);
@@ -320,12 +323,14 @@ __device__ __forceinline__ void refine_finish_block(const RefineArgs &a, const i
 #pragma unroll
     for (int k = 0; k < 16; ++k) Pm[k] = Po[k];
     const int k = a.slot[j];
+    const float z1 = a.X0[2 * (size_t)a.ld + j], z2 = a.X1[2 * (size_t)a.ld + j];
+    const float o[4] = { a.X0[j] / z1, a.X0[(size_t)a.ld + j] / z1, a.X1[j] / z2, a.X1[(size_t)a.ld + j] / z2 };
     float pt[4];
     if (k >= 0) {
         const float4 X = a.Xa[k];
         pt[0] = X.x; pt[1] = X.y; pt[2] = X.z; pt[3] = 1.0f;
     } else {
-        triangulate_point(a.X0[j], a.X0[(size_t)a.ld + j], a.X1[j], a.X1[(size_t)a.ld + j], Pm, kRefineSweeps, pt);
+        triangulate_point(o[0], o[1], o[2], o[3], Pm, kRefineSweeps, pt);     // on the rays the error below is measured on
     }
 #pragma unroll
     for (int c = 0; c < 4; ++c) a.points[(size_t)c * a.n + j] = pt[c];
@@ -338,8 +343,6 @@ __device__ __forceinline__ void refine_finish_block(const RefineArgs &a, const i
         P.b1[r] = 0.0f; P.b2[r] = 0.0f;
     }
     const RefineCam K = { a.K[0], a.K[1], a.K[4] };
-    const float z1 = a.X0[2 * (size_t)a.ld + j], z2 = a.X1[2 * (size_t)a.ld + j];
-    const float o[4] = { a.X0[j] / z1, a.X0[(size_t)a.ld + j] / z1, a.X1[j] / z2, a.X1[(size_t)a.ld + j] / z2 };
     float r[4], d1, d2;
     refine_residual(K, P, o, pt, r, d1, d2);
     const float e = fmaxf(sqrtf(r[0] * r[0] + r[1] * r[1]), sqrtf(r[2] * r[2] + r[3] * r[3]));
