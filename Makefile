@@ -125,7 +125,7 @@ $(GEOMTEST): tests/cpp/geom_test.cpp $(PKG)/host/geomFuncs.h $(PKG)/host/sfm_io.
 
 # CPU-only: the host-compiled arithmetic check of the non-GPU tests (the fakeccl target, which needs the gfx950 build and the RCCL
 # header, is a target of its own and part of `all`)
-hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libchainadjustcheck.so tests/hostcheck/libringcheck.so tests/hostcheck/libfuseringcheck.so tests/hostcheck/libringadjustcheck.so tests/hostcheck/libintersectcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/hostcheck/pfdecodecheck tests/hostcheck/libpfpaircheck.so
+hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libchainadjustcheck.so tests/hostcheck/libringcheck.so tests/hostcheck/libfuseringcheck.so tests/hostcheck/libringadjustcheck.so tests/hostcheck/libintersectcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/hostcheck/pfdecodecheck tests/hostcheck/libpfpaircheck.so tests/hostcheck/libpfringcheck.so
 
 # TEST HARNESS: comm.cpp linked against a shared-memory stand-in for the nine RCCL calls it makes, so that a 1-GPU box can run the
 # exchange code with two real ranks (tests/test_gpu_fakeccl.py); the product's libsfm_amd_rccl.so is linked against librccl
@@ -216,6 +216,11 @@ tests/hostcheck/pfdecodecheck: tests/hostcheck/pfdecodecheck.hip $(CSRC)/prefilt
 tests/hostcheck/libpfpaircheck.so: tests/hostcheck/pfpaircheck.hip $(CSRC)/prefilter_record.hpp $(CSRC)/prefilter_math.hpp $(CSRC)/device_math.hpp
 	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
 
+# the row a ring entry of the paired passes decides on (prefilter_math.hpp: pf_ring_row and the tag's scan bit), host-compiled for
+# tests/test_pf_ring_carry_host.py
+tests/hostcheck/libpfringcheck.so: tests/hostcheck/pfringcheck.hip $(CSRC)/prefilter_math.hpp $(CSRC)/device_math.hpp
+	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
+
 # the job layout and matcher-launch grouping of a batched sfm_process_pairs call (pairs_batch.hpp), host-compiled for
 # tests/test_pairs_plan_host.py
 tests/hostcheck/libpairsplancheck.so: tests/hostcheck/pairsplancheck.hip $(CSRC)/pairs_batch.hpp $(CSRC)/common.hpp $(CSRC)/pair_state.hpp include/sfm_amd.h
@@ -231,7 +236,7 @@ tests/hostcheck/libbufferrangescheck.so: tests/hostcheck/bufferrangescheck.cpp $
 	g++ -O2 -std=c++17 -Wall -fPIC -shared -o $@ $<
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(APDEMO) $(FCDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libchainadjustcheck.so tests/hostcheck/libringcheck.so tests/hostcheck/libfuseringcheck.so tests/hostcheck/libringadjustcheck.so tests/hostcheck/libintersectcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/hostcheck/pfdecodecheck tests/hostcheck/libpfpaircheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
+	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(APDEMO) $(FCDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libchainadjustcheck.so tests/hostcheck/libringcheck.so tests/hostcheck/libfuseringcheck.so tests/hostcheck/libringadjustcheck.so tests/hostcheck/libintersectcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/hostcheck/pfdecodecheck tests/hostcheck/libpfpaircheck.so tests/hostcheck/libpfringcheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all ab oracle hostcheck fakeccl clean

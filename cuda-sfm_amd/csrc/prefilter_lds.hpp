@@ -21,8 +21,12 @@ constexpr int kPfERow = 10;                                   // floats per hypo
                                                               // reads for a random row hit bank (row mod 32) + const, so distinct rows never conflict
                                                               // (row-major 40-byte rows put rows r and r + 16 on the same banks: 19 % of the LDS cycles were conflicts)
 // A wavefront's table holds the rows of ONE unit of its work: 32 (a pass), or 64 for the per-tile rule's paired passes (lane l = hypothesis
-// 64 j + l, two scans of 32 rows each): etab[rows k + row].  A scan touches 32 consecutive rows of one half, so its distinct rows sit on
-// distinct banks exactly as with 32 rows; the other half's rows are only touched by the other scan, the install and the epilogue.
+// 64 j + l, two scans of 32 rows each): etab[rows k + row].  A scan's own survivors touch 32 consecutive rows of one half, so their
+// distinct rows sit on distinct banks exactly as with 32 rows.  The ring is carried from a pair's first scan into its second (an entry
+// names its scan), so a flush that mixes carried and new entries can read rows r and r + 32 of one component together: a two-way
+// conflict, possible only in the flushes that still hold carried entries -- the first one or two of a second scan and their re-queues.
+// Measured: 5 % more bank-conflict cycles per launch (0.87e6 of 9e7 LDS-active cycles) with 4.7 % fewer LDS instructions
+// (profiles/NOTES_r12.md) -- not worth another layout.
 constexpr int kPfPassRows = 32, kPfPairRows = 64;
 constexpr int pf_wave_bytes(int rows) { return rows * kPfERow * 4 + rows * 4; }
 // The map for a tile of `tile` points (a multiple of 32); an even number of 32-point blocks is staged (the scan takes two per iteration).
@@ -42,8 +46,9 @@ template <int RULE> struct PfLds {
         ring = (ring + ring_entries * entry_bytes - 1) & ~(ring_entries * entry_bytes - 1);
         wave = ring + kPfWaves * ring_entries * entry_bytes;  // per wavefront: E table 9 x rows floats (component-major), rows counters
         next = wave + kPfWaves * pf_wave_bytes(rows);         // the block's pass counter
-        lut = next + 16;                                      // packed scan: survivor bit -> (accumulator row, step), 32 bytes (pf_pack_code)
-        bytes = lut + 32;
+        lut = next + 16;                                      // packed scan: survivor bit -> (accumulator row, step), 32 bytes (pf_pack_code);
+                                                              // paired passes: (survivor bit, half, scan) -> (row of 64, step), 128 bytes (pf_ring_lut_entry)
+        bytes = lut + kPfRingLutBytes;                        // (the same map for every instance: the 32-byte table sits at its start)
     }
 };
 static_assert(kPfRing * 8 == 1024, "ring slots are addressed with (offset & 1023) | base");

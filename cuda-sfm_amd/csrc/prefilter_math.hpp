@@ -579,6 +579,27 @@ constexpr bool pf_pack_code_closed_ok()
 }
 static_assert(pf_pack_code_closed_ok(), "pf_pack_code_closed: the closed form is not the table's permutation");
 
+// A ring entry's tag (ransac_prefilter.hip): the LDS byte address of the lane's point, a multiple of 16 (tag & ~15u), with the lane's
+// half in bit 2 (4 (lane >> 5): the accumulator-row offset of that half) and, in the paired passes, the scan that wrote the entry in
+// bit 3; bits 0 and 1 are free.  (tag & 12) names half and scan together.
+constexpr uint32_t kPfTagHalf = 4u, kPfTagScan = 8u;
+// The row of a survivor among the 64 of a pair's table: its accumulator's row offset (pf_pack_code's low five bits), its lane half's 4
+// and 32 for the second scan -- v_and + v_lshl_add on top of the single scan's row.
+SFM_HD constexpr int pf_ring_row(uint32_t code, uint32_t tag)
+{
+    return (int)(code & 31u) + (int)(tag & kPfTagHalf) + (int)((tag & kPfTagScan) << 2);
+}
+// What the paired passes' flush runs: the decode table holds the finished row for each (half, scan) -- four copies of pf_pack_code's 32
+// entries, 128 bytes -- so that the entry's tag enters the table's index (v_and + v_lshl_or, beside the clz of the mask) and nothing is
+// added to what comes out: entry = row among 64 | step << 6.
+constexpr int kPfRingLutBytes = 128;
+SFM_HD constexpr uint32_t pf_ring_lut_index(int b, uint32_t tag) { return (uint32_t)b | ((tag & (kPfTagHalf | kPfTagScan)) << 3); }
+SFM_HD constexpr uint32_t pf_ring_lut_entry(uint32_t index)
+{
+    const uint32_t code = pf_pack_code((int)(index & 31u));
+    return (uint32_t)pf_ring_row(code, (index >> 5) << 2) | ((code >> 5) << 6);
+}
+
 // The same as a shift out of a 64-bit constant (what the kernel runs): field f = 2 j + s of the survivor at bit (31 - b).  Bits 31 - b
 // and 30 - b (b even) share the even position p = 30 - b of the merged registers, whose field among the 16 of its half is 4 bits of
 // the table; the odd bit belongs to the second half (registers 3..5: + 16).

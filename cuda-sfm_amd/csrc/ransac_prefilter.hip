@@ -189,6 +189,10 @@ constexpr int kPfVarDrainK1 = 16, kPfVarDrainK7 = 32;      // the drain's cap: 1
 // turn them into the A fragments of the two scans: one fetch, one build, one install and one epilogue per 64 hypotheses instead of two,
 // each of which ran the same arithmetic in lanes l and l + 32.  This bit keeps round 9's one pass at a time (lab bench: reserved[1] = 20).
 constexpr int kPfVarSinglePass = 64;
+// Round 12: the ring is no longer emptied between the two scans of a pair -- an entry says in bit 3 of its tag which scan wrote it
+// (kPfTagScan, prefilter_math.hpp: pf_ring_row), so the first scan's leftovers ride in the second scan's full flushes.  This bit keeps
+// round 11's drain between the scans (lab bench: reserved[1] = 21).
+constexpr int kPfVarPairDrain = 128;
 
 // FL2 (experiment): a ring of 256 entries, flushed 128 at a time -- two entries per lane, their LDS reads issued together
 // WIDE (experiment): ring entries of 16 bytes that cover FOUR steps (two conversions): half as many appends
@@ -203,7 +207,7 @@ constexpr int kPfVarSinglePass = 64;
 // held to 104 by tests/test_register_budget.py.
 constexpr int pf_score_waves_per_simd(int var, int rule, int fl2, int pipe, int wide, int prio)
 {
-    if (var == 0 && rule == kPfRuleBandTile && !fl2 && !pipe && !wide && !prio) return 4;
+    if ((var == 0 || var == kPfVarPairDrain) && rule == kPfRuleBandTile && !fl2 && !pipe && !wide && !prio) return 4;
     return ((var & kPfVarTickets) == 0 && (rule == kPfRuleBandTile || rule == kPfRuleBandPack) && !fl2 && !pipe && !wide && !prio) ? 5 : 4;
 }
 
@@ -249,7 +253,10 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
     static_assert(kTail9 || (VAR & ~kPfVarTickets) == 0, "the pass-tail switches belong to the product's two rules");
     static_assert(!(VAR & kPfVarSinglePass) || (kTile && VAR == kPfVarSinglePass), "single passes: the per-tile rule's summing instance");
     // paired passes: the unit of work is 64 hypotheses (two scans of 32) prepared at once, one hypothesis per lane
-    constexpr bool kPair = kTile && kTail9 && VAR == 0;
+    static_assert(!(VAR & kPfVarPairDrain) || (kTile && VAR == kPfVarPairDrain), "paired passes drained between the scans: the per-tile rule's summing instance");
+    constexpr bool kPair = kTile && kTail9 && (VAR == 0 || VAR == kPfVarPairDrain);
+    // the ring is carried across the boundary between a pair's scans: its entries name their scan themselves
+    constexpr bool kCarry = kPair && VAR == 0;
     constexpr int kRows = kPair ? kPfPairRows : kPfPassRows, kUnit = kRows;       // rows of the wavefront's table = hypotheses per unit
     constexpr int kDrainMore = !kTail9 ? 0 : (VAR & kPfVarDrainK1) ? 1 : (VAR & kPfVarDrainK7) ? 7 : (VAR & kPfVarDrainLocal) ? 3 : 0;
     constexpr bool kDecodeTable = !(kTail9 && (VAR & kPfVarClosedDecode));
@@ -312,6 +319,9 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
     // memory would balance the blocks too, but 131072 device-scope atomics on one address take 1.5 ms.)
     uint32_t *next_idx = reinterpret_cast<uint32_t *>(smem + L.next);
     if (threadIdx.x == 0) *next_idx = (uint32_t)W;
+    if constexpr (kCarry) {                                   // (bit, half, scan) -> row of the pair's 64 | step << 6
+        if (threadIdx.x < kPfRingLutBytes) smem[L.lut + threadIdx.x] = (unsigned char)pf_ring_lut_entry(threadIdx.x);
+    } else
     if (kPack && kDecodeTable && threadIdx.x < 32) smem[L.lut + threadIdx.x] = (unsigned char)pf_pack_code((int)threadIdx.x);
     // tile rule: the pair's bound and this tile's boxes (pf_bucket_scatter_kernel, once per fillXU) are requested now and used after the staging
     float pf_B = 0.0f;
@@ -421,6 +431,9 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
     lds_ch8 *frag_lane = (lds_ch8 *)(smem + LT::kFrag) + lane;
     const ThrBand band = make_band(thr);
     uint32_t passes_done = 0;
+#if SFM_AB
+    uint32_t carried = 0;                                 // ring entries held when a second scan began, over this wavefront's pairs (clk[6] >> 32)
+#endif
 
     // ---- 32 hypotheses per pass of this wavefront (no block-level synchronisation from here on)
     while (have) {
@@ -432,6 +445,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
         const int nscan = (kPair && nvalid_unit > kPfGroup) ? 2 : 1;
 #if SFM_AB
         const bool probe1 = probe && passes_done == 0u;
+        unsigned long long w_scan_end = 0;
 #endif
         // the next pass of this wavefront: asked for now, needed when this one is done
         uint32_t ps_next = ps + nstatic;
@@ -470,17 +484,21 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
 
         // ---- the scan: two accumulator sets; while set A is scanned the MFMAs of the next step fill set B
         // a lane's point in 32-point block 0 (LDS byte address, a multiple of 16) | its accumulator-row offset 4 (lane >> 5)
-        const uint32_t lane_tag = (uint32_t)(size_t)(lds_cf4 *)pts + (uint32_t)(row * 16) + (uint32_t)(half * 4);
+        // (carried ring: | kPfTagScan from the second scan of a pair on -- wave-uniform, folded in once when that scan starts)
+        uint32_t lane_tag = (uint32_t)(size_t)(lds_cf4 *)pts + (uint32_t)(row * 16) + (uint32_t)(half * 4);
         // the exact decision for the FIRST surviving pair of a ring entry's mask; the survivor leaves the mask
         // entry = { 32-bit mask of surviving accumulators (bit 31 - r: accumulator r of the pair's first point block, bit 15 - r:
-        // of its second), LDS byte address of the lane's point in the pair's first block | 4 (lane >> 5) }.
+        // of its second), LDS byte address of the lane's point in the pair's first block | 4 (lane >> 5) | 8 (scan of a pair) }.
         auto decide_first = [&](uint32_t &rest, uint32_t tag) {
             const int b = __builtin_clz(rest);                                  // the first surviving accumulator of the first step that has one
             rest &= ~(0x80000000u >> b);
             // G rule: bit 31 - r = accumulator r of the first step, 15 - r of the second; band rule: 31 - 2 r and 30 - 2 r; packed
             // scan: pf_pack_code through the table (lab bench: as arithmetic on b, about seven vector instructions -- measured slower)
             int hl, sub;
-            if (kPack) {
+            if constexpr (kCarry) {                                             // the entry's own row among the pair's 64: the tag picks the table's copy
+                const uint32_t code = (uint32_t)lut_l[pf_ring_lut_index(b, tag)];
+                hl = (int)(code & 63u); sub = (int)(code >> 6);
+            } else if (kPack) {
                 const uint32_t code = kDecodeTable ? (uint32_t)lut_l[b] : pf_pack_code_closed(b);
                 hl = (int)(code & 31u) + (int)(tag & 4u); sub = (int)(code >> 5);
             } else {
@@ -488,13 +506,16 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
                 sub = kBand ? b & 1 : b >> 4;
                 hl = r + (r & 12) + (int)(tag & 4u);                            // accumulator row = local hypothesis: (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
             }
-            if (hl < nvalid) {
+            // carried ring: hl is a row of the pair's table and every row below nvalid_unit is a hypothesis -- a second scan exists only
+            // when nvalid_unit > 32, so first-scan rows always pass, as they do with (hoff, nvalid) = (0, 32)
+            const int row_end = kCarry ? nvalid_unit : nvalid, row_first = kCarry ? 0 : hoff;
+            if (hl < row_end) {
                 const f4v q = *(lds_cf4 *)((__attribute__((address_space(3))) const unsigned char *)0 + ((tag & ~15u) + ((uint32_t)sub << 9)));
-                lds_cf *e = etab_l + hl + hoff;
+                lds_cf *e = etab_l + hl + row_first;
                 const v2f p0 = { e[0], e[kRows] }, p1 = { e[2 * kRows], e[3 * kRows] }, p2 = { e[4 * kRows], e[5 * kRows] }, p3 = { e[6 * kRows], e[7 * kRows] };      // (e2 e6) (e1 e3) (e5 e7) (e0 e4): one ds_read2_b32 each (64 rows: ds_read2st64_b32)
                 const float e8 = e[8 * kRows];
                 if (pf_exact_inlier(p0, p1, p2, p3, e8, v2f{ q.x, q.y }, v2f{ q.z, q.w }, band))
-                    __hip_atomic_fetch_add(cnt_l + hl + hoff, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_add(cnt_l + hl + row_first, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         };
         auto flush = [&](int m, auto more_c) {
@@ -591,7 +612,10 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
 
         for (int sc = 0; ; ++sc) {
         patch_zero_divisor_rows(sc);
-        PF_PHASE(3);
+#if SFM_AB
+        if (sc == 0) PF_PHASE(3);
+        else if (probe1) reinterpret_cast<uint32_t *>(clk + 3)[1] = (uint32_t)(wall_clock64() - w_scan_end);       // first scan's end -> second scan's start
+#endif
         if constexpr (kPack && PIPE) {
         // ---- packed scan, software-pipelined over FOUR accumulator sets: while the conversion and the bit picking work on the two
         // sets of the previous two steps, the four MFMAs of the next two steps go out between them, one at a time (a wavefront that
@@ -741,9 +765,17 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
         }
         }
         if (sc + 1 >= nscan) break;
-        // paired passes: the ring is drained between the scans as at every pass boundary (its entries name rows of THIS scan), then the
-        // second scan's fragments and rows take over
-        while (nq > 0) flush(min(nq, 64), kDrain);
+        // paired passes: the second scan's fragments and rows take over.  What the ring still holds stays in it -- from here on an
+        // appended entry carries the scan bit, so a flush decides either kind on its own rows.  (kPfVarPairDrain: round 11's drain here,
+        // as at every pass boundary, with entries that name rows of the scan in progress.)
+#if SFM_AB
+        if (probe1) w_scan_end = wall_clock64();
+#endif
+        if constexpr (kCarry) lane_tag |= kPfTagScan;
+        else while (nq > 0) flush(min(nq, 64), kDrain);
+#if SFM_AB
+        carried += (uint32_t)nq;
+#endif
         afrag.n0 = bfrag_n0; afrag.n1 = bfrag_n1;
         hoff = kPfGroup; nvalid = nvalid_unit - kPfGroup;
         }
@@ -854,6 +886,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
     SFM_PHASE("kernel_end");
     if (probe) { clk[6] = passes_done; clk[0] = clock64() - c0; clk[1] = wall_clock64() - w0; }
 #if SFM_AB
+    if (probe) clk[6] |= (unsigned long long)carried << 32;
     if (trace && lane == 0) {
         const unsigned long long tend = wall_clock64();
         trace[4 + wave] = tend;
@@ -1284,7 +1317,7 @@ static int pf_rule_switch(const sfm_ransac_params &p)      // lab bench: the rul
     if (SFM_SW(p, 3) == 5 || SFM_SW(p, 1) == 5 || SFM_SW(p, 1) == 7 || SFM_SW(p, 1) == 9) return kPfRuleBand;
     if (SFM_SW(p, 3) == 6 || SFM_SW(p, 1) == 11 || SFM_SW(p, 1) == 12) return kPfRuleBandPack;
     if (SFM_SW(p, 3) == 7 || SFM_SW(p, 1) == 13 || SFM_SW(p, 1) == 14 || SFM_SW(p, 1) == 15) return kPfRuleBandTile;
-    return -1;          // (reserved[1] = 19 / 20, paired / single passes of the summing per-tile instance, leave the rule to the product's choice)
+    return -1;          // (reserved[1] = 19 / 20 / 21, paired / single / paired-and-drained passes of the summing per-tile instance, leave the rule to the product's choice)
 }
 
 // The product's choice.  Per-tile band constants (tiles = runs of a Morton-ordered copy of the correspondences, sigma and the coefficient
@@ -1335,18 +1368,21 @@ int prefilter_tile_points(const sfm_pair *pair, const sfm_ransac_params &p) { re
 // partial counts per launch on, 16 pairs per wavefront of a full chip -- and runs round 9's single passes (kPfVarSinglePass) below that.
 // Lab bench: reserved[1] = 19 sums at every size with paired passes, 20 sums at every size with single passes (both leave the
 // per-hypothesis rule of a first call as it is).
+// Round 12: the paired passes carry the survivor ring from a pair's first scan into its second (an entry names its scan).  Lab bench:
+// reserved[1] = 21 is 19 with round 11's drain between the scans (kPfVarPairDrain), so that the two can be alternated on one box.
 static int pf_tail_var(const sfm_pair *pair, const sfm_ransac_params &p, uint32_t count)
 {
     const bool large = pf_sums_counts_at(count, pair->ld, pf_tile_of(pair, p));
     if (SFM_SW(p, 1) == 19) return 0;
     if (SFM_SW(p, 1) == 20) return pair->pf_rule == kPfRuleBandTile ? kPfVarSinglePass : 0;
+    if (SFM_SW(p, 1) == 21) return pair->pf_rule == kPfRuleBandTile ? kPfVarPairDrain : 0;
     if (pair->pf_rule == kPfRuleBandTile && SFM_SW(p, 1) == 16) return kPfVarDrainK1;
     if (pair->pf_rule == kPfRuleBandTile && SFM_SW(p, 1) == 17) return kPfVarDrainK7;
     int var = 0;
     const bool lab = SFM_SW(p, 3) >= 8 && SFM_SW(p, 3) < 16;
     if (lab && (SFM_SW(p, 3) & 1)) var |= kPfVarDrainLocal;
     if (lab && (SFM_SW(p, 3) & 2)) var |= kPfVarClosedDecode;
-    const bool sum = (lab && (SFM_SW(p, 3) & 4)) ? false : (large || (SFM_SW(p, 1) >= 16 && SFM_SW(p, 1) <= 18));     // (19, 20: answered above)
+    const bool sum = (lab && (SFM_SW(p, 3) & 4)) ? false : (large || (SFM_SW(p, 1) >= 16 && SFM_SW(p, 1) <= 18));     // (19 .. 21: answered above)
     if (!sum) var |= kPfVarAnswerEpilogue;
     if (var == 0 && pair->pf_rule == kPfRuleBandTile && !pf_pairs_passes_at(count, pair->ld, pf_tile_of(pair, p))) var = kPfVarSinglePass;
     return var;
@@ -1376,8 +1412,8 @@ int launch_score_prefilter(sfm_pair *pair, ShardSlot &s, hipStream_t stream, con
     const int rule = pair->pf_rule;
     const int tail_var = pf_tail_var(pair, p, count);
     const bool wide = rule == kPfRuleBandTile && SFM_SW(p, 1) == 13;                     // (AB build: 16-byte ring entries covering four steps)
-    // (the instance the chain below picks for paired passes: <16, 0, kPfRuleBandTile> with none of the recorded variants' switches)
-    const bool paired_units = rule == kPfRuleBandTile && tail_var == 0 && waves == kPfWaves && !wide && SFM_SW(p, 1) != 14 && SFM_SW(p, 1) != 15;
+    // (the instances the chain below picks for paired passes: <16, 0 or kPfVarPairDrain, kPfRuleBandTile> with none of the recorded variants' switches)
+    const bool paired_units = rule == kPfRuleBandTile && (tail_var == 0 || tail_var == kPfVarPairDrain) && waves == kPfWaves && !wide && SFM_SW(p, 1) != 14 && SFM_SW(p, 1) != 15;
     const uint32_t nunits = paired_units ? (npass + 1u) / 2u : npass;             // what a wavefront takes at a time: a pass, or a pair of passes
     const uint32_t iters = (nunits + (uint32_t)waves - 1) / (uint32_t)waves;      // block iterations per tile
     // one block per CU is resident (152 KiB of LDS), so the grid is at most one block per CU, spread over the tiles: columns =
@@ -1423,6 +1459,7 @@ int launch_score_prefilter(sfm_pair *pair, ShardSlot &s, hipStream_t stream, con
         PF_TAIL_CASE(2); PF_TAIL_CASE(4); PF_TAIL_CASE(6); PF_TAIL_CASE(10); PF_TAIL_CASE(12); PF_TAIL_CASE(14);
         case kPfVarDrainK1: rcl = launch(&ransac_score_prefilter<16, kPfVarDrainK1, kPfRuleBandTile>); break;
         case kPfVarDrainK7: rcl = launch(&ransac_score_prefilter<16, kPfVarDrainK7, kPfRuleBandTile>); break;
+        case kPfVarPairDrain: rcl = launch(&ransac_score_prefilter<16, kPfVarPairDrain, kPfRuleBandTile>); break;
         default: set_error("pass-tail switches %d: no such instance", tail_var); break;
         }
 #undef PF_TAIL_CASE

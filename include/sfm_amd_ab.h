@@ -41,7 +41,9 @@ extern "C" {
  *       19 the per-tile form prepares TWO passes at once, one hypothesis per lane, at EVERY size, with the summing epilogue (the product:
  *       from 2^22 partial counts per launch on; profiles/NOTES_r11.md: the headline step 2.8 % shorter, 8 pairs per wavefront 1.2 % longer);
  *       20 the single passes it replaced, with the summing epilogue, at every size (the product: between 2^21 and 2^22 partial counts) --
- *       19 and 20 leave the choice between the per-hypothesis and the per-tile form to the product's rule (combine with [3] = 7);
+ *       21 the paired passes of 19 with the survivor ring EMPTIED between a pair's two scans, as in round 11 (the product and 19 carry the
+ *       first scan's leftover entries into the second scan's flushes: an entry's tag names its scan; profiles/NOTES_r12.md) --
+ *       19, 20 and 21 leave the choice between the per-hypothesis and the per-tile form to the product's rule (combine with [3] = 7);
  *   [2] k > 0: minimum hypothesis batches per scoring block (default 8); pre-filter kernel: grid columns;
  *   [3] 1 AUTO never picks SFM_KERNEL_PREFILTER; 2 the round-2 pre-filter kernel (csrc/ab/ransac_prefilter_r2.hip);
  *       3 per-hypothesis records from the stand-alone kernel instead of the lane-solve kernel; 4 the G rule of rounds 2-4
@@ -60,7 +62,10 @@ extern "C" {
 /* Where block 0 of the last pre-filter scoring launch (SFM_KERNEL_PREFILTER) spent its time: ticks[0] shader-clock ticks and
  * ticks[1] 100 MHz ticks over its lifetime (as above); 100 MHz ticks since its start at: [2] tile staged, [3] first pass'
  * coefficients prepared, [4] first 32-hypothesis block scanned and drained, [5] first pass done (counts and ticket out),
- * [6] number of passes wavefront 0 ran.  Zero where the kernel that ran has no such probe.  Synchronises. */
+ * [6] number of passes wavefront 0 ran (paired passes: pairs) in the low 32 bits; paired passes also leave in [6] >> 32 the ring entries
+ * wavefront 0 held when a second scan began, summed over its pairs (0 when the ring is emptied between the scans), and in [3] >> 32 the
+ * ticks from the end of its first pair's first scan to the start of that pair's second ([3]'s low 32 bits: the stamp).
+ * Zero where the kernel that ran has no such probe.  Synchronises. */
 int sfm_ransac_last_phases(sfm_pair *pair, uint64_t ticks[8]);
 /* Profiling aid: when did every block / wavefront of the last pre-filter scoring launch start and finish?  20 words per
  * block (up to 1024 blocks, in blockIdx.y * gridDim.x + blockIdx.x order): [0] start and [1] end of its first wavefront,

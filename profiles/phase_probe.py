@@ -1,7 +1,8 @@
 """Where block 0 of ransac_score_prefilter spends its time (sfm_ransac_last_phases), per shard size and grid width.
 python profiles/phase_probe.py LABEL [reserved1 [reserved3 [samples]]]: 2^20 hypotheses only, with those lab-bench switches
 (include/sfm_amd_ab.h), `samples` launches stamped, each line tagged LABEL and carrying the drain (ring_drained - first_block_scanned)
-and the epilogue (first_pass_done - ring_drained) -- profiles/r09_phase_probe.txt."""
+and the epilogue (first_pass_done - ring_drained) -- profiles/r09_phase_probe.txt; paired passes also carry the time from the end
+of the first pair's first scan to the start of its second and the ring entries held there (profiles/r12_phase_probe.txt)."""
 import json
 import os
 import sys
@@ -29,9 +30,11 @@ for H, cols in cases:
         pair.estimateE(p)
     ctx.kernel_timing(True) if hasattr(ctx, "kernel_timing") else None
     pair.estimateE(p)
-    t = pair.last_phases()
+    t = [int(v) for v in pair.last_phases()]
+    boundary_ticks, held = t[3] >> 32, t[6] >> 32          # paired passes: first scan's end -> second scan's start; ring entries held at second scans
+    t[3] &= 0xFFFFFFFF; t[6] &= 0xFFFFFFFF
     us = lambda k: round(t[k] / 100.0, 2)
     tag = {"build": label, "reserved": [0, r1, cols, r3], "drain_us": round((t[7] - t[4]) / 100.0, 2), "epilogue_us": round((t[5] - t[7]) / 100.0, 2)} if label else {}
     print(json.dumps({**tag, "hypotheses": H, "grid": pair.last_launch()["grid"], "block0_lifetime_us": us(1), "tile_staged_us": us(2), "first_pass_prepared_us": us(3),
-                      "first_block_scanned_us": us(4), "ring_drained_us": us(7), "first_pass_done_us": us(5), "passes_of_wave0": t[6],
+                      "first_block_scanned_us": us(4), "ring_drained_us": us(7), "first_pass_done_us": us(5), "passes_of_wave0": t[6], "scan_boundary_us": round(boundary_ticks / 100.0, 2), "entries_held_at_second_scans": held,
                       "shader_mhz": round(100.0 * t[0] / max(t[1], 1))}), flush=True)
