@@ -21,7 +21,7 @@ SRCS     := $(wildcard $(CSRC)/*.hip)
 SRCS_AB  := $(wildcard $(CSRC)/ab/*.hip)
 OBJS     := $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(SRCS))
 OBJS_AB  := $(patsubst $(CSRC)/%.hip,$(BUILD_AB)/%.o,$(SRCS)) $(patsubst $(CSRC)/ab/%.hip,$(BUILD_AB)/ab_%.o,$(SRCS_AB))
-HDRS     := $(wildcard $(CSRC)/*.hpp) include/sfm_amd.h include/sfm_amd_ab.h
+HDRS     := $(wildcard $(CSRC)/*.hpp) $(wildcard $(CSRC)/*.inc) include/sfm_amd.h include/sfm_amd_ab.h
 
 DEMO     := $(PKG)/host/two_view_demo
 HDEMO    := $(PKG)/host/homography_demo
@@ -31,11 +31,12 @@ RPDEMO   := $(PKG)/host/refine_pairs_demo
 RVDEMO   := $(PKG)/host/register_views_demo
 APDEMO   := $(PKG)/host/align_pairs_demo
 FCDEMO   := $(PKG)/host/fuse_chain_demo
+GMDEMO   := $(PKG)/host/guided_match_demo
 
 IOTEST   := tests/cpp/io_test
 GEOMTEST := tests/cpp/geom_test
 
-all: $(LIB) $(LIB_AB) $(COMMLIB) $(BUILD)/ransac.s $(BUILD)/view_points.s oracle hostcheck fakeccl $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(APDEMO) $(FCDEMO) $(IOTEST) $(GEOMTEST)
+all: $(LIB) $(LIB_AB) $(COMMLIB) $(BUILD)/ransac.s $(BUILD)/view_points.s oracle hostcheck fakeccl $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(APDEMO) $(FCDEMO) $(GMDEMO) $(IOTEST) $(GEOMTEST)
 
 # the product's objects come with the compiler's resource-usage report (registers, scratch, LDS of every kernel) next to them:
 # $(BUILD)/<source>.usage.txt, read by tests/test_register_budget.py; warnings and errors of the compile are still shown
@@ -117,6 +118,9 @@ $(APDEMO): $(PKG)/host/align_pairs_demo.cpp $(PKG)/host/sfm.h $(PKG)/host/sfm_io
 $(FCDEMO): $(PKG)/host/fuse_chain_demo.cpp $(PKG)/host/sfm.h $(PKG)/host/sfm_io.h $(PKG)/host/cudaSift.h include/sfm_amd.h $(LIB)
 	g++ -O2 -std=c++14 -Wall -o $@ $< -L$(PKG)/lib -lsfm_amd -Wl,-rpath,'$$ORIGIN/../lib' -Wl,-rpath,/opt/rocm/lib
 
+$(GMDEMO): $(PKG)/host/guided_match_demo.cpp $(PKG)/host/sfm.h $(PKG)/host/sfm_io.h $(PKG)/host/cudaSift.h include/sfm_amd.h $(LIB)
+	g++ -O2 -std=c++14 -Wall -o $@ $< -L$(PKG)/lib -lsfm_amd -Wl,-rpath,'$$ORIGIN/../lib' -Wl,-rpath,/opt/rocm/lib
+
 $(IOTEST): tests/cpp/io_test.cpp $(PKG)/host/sfm_io.h $(PKG)/host/cudaSift.h include/sfm_amd.h
 	g++ -O2 -std=c++14 -Wall -o $@ $<
 
@@ -125,7 +129,7 @@ $(GEOMTEST): tests/cpp/geom_test.cpp $(PKG)/host/geomFuncs.h $(PKG)/host/sfm_io.
 
 # CPU-only: the host-compiled arithmetic check of the non-GPU tests (the fakeccl target, which needs the gfx950 build and the RCCL
 # header, is a target of its own and part of `all`)
-hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libchainadjustcheck.so tests/hostcheck/libringcheck.so tests/hostcheck/libfuseringcheck.so tests/hostcheck/libringadjustcheck.so tests/hostcheck/libintersectcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/hostcheck/pfdecodecheck tests/hostcheck/libpfpaircheck.so tests/hostcheck/libpfringcheck.so
+hostcheck: tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libchainadjustcheck.so tests/hostcheck/libringcheck.so tests/hostcheck/libfuseringcheck.so tests/hostcheck/libringadjustcheck.so tests/hostcheck/libintersectcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/hostcheck/pfdecodecheck tests/hostcheck/libpfpaircheck.so tests/hostcheck/libpfringcheck.so tests/hostcheck/libmatchguidedcheck.so
 
 # TEST HARNESS: comm.cpp linked against a shared-memory stand-in for the nine RCCL calls it makes, so that a 1-GPU box can run the
 # exchange code with two real ranks (tests/test_gpu_fakeccl.py); the product's libsfm_amd_rccl.so is linked against librccl
@@ -221,6 +225,13 @@ tests/hostcheck/libpfpaircheck.so: tests/hostcheck/pfpaircheck.hip $(CSRC)/prefi
 tests/hostcheck/libpfringcheck.so: tests/hostcheck/pfringcheck.hip $(CSRC)/prefilter_math.hpp $(CSRC)/device_math.hpp
 	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
 
+# the gate of sfm_match_guided and the arithmetic of sfm_pair_fundamental (match_guided_math.hpp) with a serial driver of the whole
+# call (its own top-2 rule, score chain and emit formulae), for tests/test_match_guided_host.py and the field-by-field comparison
+# of tests/test_gpu_match_guided.py; the no-scratch pin of match_guided.hip reads $(BUILD)/match_guided.usage.txt, which the object
+# rule above writes
+tests/hostcheck/libmatchguidedcheck.so: tests/hostcheck/matchguidedcheck.hip $(CSRC)/match_guided_math.hpp $(CSRC)/device_math.hpp include/sfm_amd.h
+	$(HIPCC) -x hip --cuda-host-only -O2 -ffp-contract=off -mfma -fPIC -shared -Wno-pass-failed -o $@ $<
+
 # the job layout and matcher-launch grouping of a batched sfm_process_pairs call (pairs_batch.hpp), host-compiled for
 # tests/test_pairs_plan_host.py
 tests/hostcheck/libpairsplancheck.so: tests/hostcheck/pairsplancheck.hip $(CSRC)/pairs_batch.hpp $(CSRC)/common.hpp $(CSRC)/pair_state.hpp include/sfm_amd.h
@@ -236,7 +247,7 @@ tests/hostcheck/libbufferrangescheck.so: tests/hostcheck/bufferrangescheck.cpp $
 	g++ -O2 -std=c++17 -Wall -fPIC -shared -o $@ $<
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(APDEMO) $(FCDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libchainadjustcheck.so tests/hostcheck/libringcheck.so tests/hostcheck/libfuseringcheck.so tests/hostcheck/libringadjustcheck.so tests/hostcheck/libintersectcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/hostcheck/pfdecodecheck tests/hostcheck/libpfpaircheck.so tests/hostcheck/libpfringcheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
+	rm -rf $(BUILD) $(LIB) $(LIB_AB) $(DEMO) $(HDEMO) $(SDEMO) $(MAINAPP) $(RPDEMO) $(RVDEMO) $(APDEMO) $(FCDEMO) $(GMDEMO) $(IOTEST) $(GEOMTEST) tests/hostcheck/libhostcheck.so tests/hostcheck/librefinecheck.so tests/hostcheck/libregistercheck.so tests/hostcheck/libviewpointscheck.so tests/hostcheck/libadjustcheck.so tests/hostcheck/libaligncheck.so tests/hostcheck/libfusecheck.so tests/hostcheck/libchainadjustcheck.so tests/hostcheck/libringcheck.so tests/hostcheck/libfuseringcheck.so tests/hostcheck/libringadjustcheck.so tests/hostcheck/libintersectcheck.so tests/hostcheck/libpairstatecheck.so tests/hostcheck/libbufferrangescheck.so tests/hostcheck/libpfldscheck.so tests/hostcheck/libpairsplancheck.so tests/hostcheck/pfdecodecheck tests/hostcheck/libpfpaircheck.so tests/hostcheck/libpfringcheck.so tests/hostcheck/libmatchguidedcheck.so tests/fake_ccl/libsfm_amd_fakeccl.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all ab oracle hostcheck fakeccl clean

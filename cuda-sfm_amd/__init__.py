@@ -70,6 +70,7 @@ EXPORTS = [
     "sfm_ctx_synchronize", "sfm_ctx_own_stream", "sfm_ctx_get_stream", "sfm_ctx_get_device", "sfm_ctx_timer_start", "sfm_ctx_timer_stop", "sfm_ctx_kernel_timing",
     "sfm_ctx_kernel_timing_read", "sfm_device_alloc", "sfm_device_free", "sfm_copy_to_device", "sfm_copy_to_host",
     "sfm_copy_to_host_2d", "sfm_copy_to_device_2d", "sfm_find_homography", "sfm_sift_temp_layout", "sfm_extract_sift", "sfm_extract_sift_begin", "sfm_extract_sift_end", "sfm_match", "sfm_match_soa",
+    "sfm_match_guided_default_params", "sfm_match_guided", "sfm_pair_fundamental",
     "sfm_pair_create", "sfm_pair_destroy", "sfm_pair_reset", "sfm_get_result", "sfm_fill_xu", "sfm_set_points", "sfm_ransac_default_params",
     "sfm_ransac_permutation_indices", "sfm_estimate_E", "sfm_ransac_score", "sfm_ransac_score_candidates", "sfm_ransac_score_into", "sfm_ransac_finalize",
     "sfm_ransac_finalize_key", "sfm_ransac_finalize_key_on", "sfm_ransac_score_into_slot", "sfm_estimate_E_pipelined", "sfm_pair_flush", "sfm_ransac_export_key", "sfm_pose_candidates", "sfm_choose_pose", "sfm_triangulate", "sfm_pose_chain",
@@ -102,6 +103,11 @@ class RansacParams(C.Structure):
         ("seed", C.c_uint32), ("d_indices", C.c_void_p), ("threshold", C.c_float),
         ("jacobi_sweeps", C.c_int32), ("kernel", C.c_int32), ("reserved", C.c_int32 * 4),
     ]
+
+
+class MatchGuidedParams(C.Structure):
+    """sfm_match_guided_params (include/sfm_amd.h)."""
+    _fields_ = [("band_px", C.c_float), ("reserved", C.c_int32 * 4)]
 
 
 class RefineParams(C.Structure):
@@ -351,6 +357,10 @@ _lib.sfm_find_homography.argtypes = [_vp, _vp, C.c_int, _vp, C.POINTER(C.c_int),
                                      C.c_float, C.c_uint32, _vp, _vp, _vp]
 _lib.sfm_match.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int]
 _lib.sfm_match_soa.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]
+_lib.sfm_match_guided_default_params.argtypes = [C.POINTER(MatchGuidedParams)]
+_lib.sfm_match_guided_default_params.restype = None
+_lib.sfm_match_guided.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.POINTER(MatchGuidedParams)]
+_lib.sfm_pair_fundamental.argtypes = [_vp, C.c_int, _vp]
 _lib.sfm_pair_create.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(_vp)]
 _lib.sfm_pair_destroy.argtypes = [_vp]
 _lib.sfm_fill_xu.argtypes = [_vp, _vp]
@@ -478,6 +488,27 @@ def default_params(num_points, **kw):
             v = _ptr(v)
         setattr(p, k, v)
     return p
+
+
+def match_guided_params(**kw):
+    """sfm_match_guided_params with the library's default (a band of 4 px), fields overridden by kw."""
+    p = MatchGuidedParams()
+    _lib.sfm_match_guided_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "reserved":
+            for i, x in enumerate(v):
+                p.reserved[i] = int(x)
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def match_guided(ctx, d_sift1, n1, d_sift2, n2, d_F, **kw):
+    """sfm_match_guided (enqueue only): the descriptor match of d_sift1 against the rows of d_sift2 inside the epipolar band of
+    d_F (9 device floats, u2^T F u1 = 0, pixels); kw: the fields of sfm_match_guided_params (band_px)."""
+    p = match_guided_params(**kw)
+    _check(_lib.sfm_match_guided(ctx._h if ctx is not None else None, _ptr(d_sift1), int(n1), _ptr(d_sift2), int(n2), _ptr(d_F), C.byref(p)),
+           "sfm_match_guided")
 
 
 def refine_params(**kw):
@@ -1455,6 +1486,14 @@ class ImagePair:
         P = np.empty((4, 4), np.float32); E = np.empty((3, 3), np.float32)
         _check(_lib.sfm_get_refined_pose(self._h, P.ctypes.data_as(_vp), E.ctypes.data_as(_vp)), "sfm_get_refined_pose")
         return P, E
+
+    def fundamental(self, refined=True, out=None):
+        """sfm_pair_fundamental (enqueue only): the pair's F for match_guided as a 9-float device tensor (u1 = the records'
+        xpos / ypos, u2 = their match_xpos / match_ypos), from the refined E or (refined=False) the E of estimateE."""
+        if out is None:
+            out = torch.empty(9, dtype=torch.float32, device=torch.device("cuda", self.ctx.device))
+        _check(_lib.sfm_pair_fundamental(self._h, 1 if refined else 0, _ptr(out)), "sfm_pair_fundamental")
+        return out
 
     def get_refined_points(self):
         return self._get(_lib.sfm_get_refined_points, "sfm_get_refined_points", (4, self.num_points), np.float32)

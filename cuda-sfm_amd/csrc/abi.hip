@@ -507,6 +507,36 @@ int sfm_match_soa(sfm_ctx *ctx, const float *d_desc1, int n1, int ld1, const flo
     return launch_match_ambiguity_quirk(ctx, d_desc1, n1, ld1, d_desc2, n2, ld2, nullptr, d_second);
 }
 
+// ---- guided match (match_guided.hip) ---------------------------------------------------------------
+void sfm_match_guided_default_params(sfm_match_guided_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->band_px = 4.0f;
+}
+
+int sfm_match_guided(sfm_ctx *ctx, sfm_sift_point *d_sift1, int n1, const sfm_sift_point *d_sift2, int n2,
+                     const float *d_F, const sfm_match_guided_params *p)
+{
+    SFM_REQUIRE(ctx && d_sift1 && d_sift2 && d_F && p, SFM_E_INVALID, "null argument");
+    SFM_REQUIRE(n1 >= 0 && n2 >= 0, SFM_E_INVALID, "negative point count");
+    SFM_REQUIRE(p->band_px > 0.0f && p->band_px < __builtin_inff(), SFM_E_INVALID, "sfm_match_guided_params.band_px must be finite and > 0");
+    for (int i = 0; i < 4; ++i) SFM_REQUIRE(p->reserved[i] == 0, SFM_E_INVALID, "sfm_match_guided_params.reserved[%d] must be zero", i);
+    if (n1 == 0 || n2 == 0) return SFM_OK;
+    SFM_HIP_TRY(hipSetDevice(ctx->device));
+    return launch_match_guided(ctx, d_sift1, n1, d_sift2, n2, d_F, p->band_px);
+}
+
+int sfm_pair_fundamental(sfm_pair *pair, int refined, float *d_F)
+{
+    SFM_REQUIRE(pair && d_F, SFM_E_INVALID, "null argument");
+    SFM_REQUIRE(refined == 0 || refined == 1, SFM_E_INVALID, "refined must be 0 or 1");
+    SFM_FLUSH(pair);
+    if (refined) SFM_NEED(pair, kRefined); else SFM_NEED(pair, kE);
+    SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
+    return launch_pair_fundamental(pair, refined, d_F);
+}
+
 // ---- ExtractSift ---------------------------------------------------------------------------------
 int sfm_sift_temp_layout(int width, int height, int num_octaves, int scale_up, sfm_sift_layout *layout)
 {

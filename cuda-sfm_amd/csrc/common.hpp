@@ -488,5 +488,8 @@ int match_poll_check(sfm_ctx *ctx);                                             
 int launch_match(sfm_ctx *ctx, const float *d1, int n1, int ld1, const float *d2, int n2, int ld2,
                  float *d_best, float *d_second, int32_t *d_index,
                  sfm_sift_point *sift1, const sfm_sift_point *sift2);
+// match_guided.hip: the exact matcher behind the epipolar gate of d_F (ticket merge), and F from a pair's E and K^-1
+int launch_match_guided(sfm_ctx *ctx, sfm_sift_point *sift1, int n1, const sfm_sift_point *sift2, int n2, const float *d_F, float band_px);
+int launch_pair_fundamental(sfm_pair *pair, int refined, float *d_F);
 
 } // namespace sfm

@@ -20,93 +20,12 @@
 // group hit 16 distinct 16-byte slots.  Inside each group of 8 floats the order is
 // (d0 d2 d4 d6 | d1 d3 d5 d7) so that one b128 read yields the operands of four consecutive MFMA
 // k-steps for the lane's k-parity (lane >> 5).
-#include "match_common.hpp"
+//
+// The staging, the MFMA loop and the launch plan are in match_mfma.hpp, the ticket merge in match_ticket_merge.inc (both shared
+// with match_guided.hip).
+#include "match_mfma.hpp"
 
 namespace sfm {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kRowsPerStage = 64;        // database rows per LDS stage (RT = 2 MFMA row tiles)
-constexpr int kLdsStride = 132;          // floats per staged row
-
-// Stage `rows` descriptor rows (first row `row0`, zero beyond `nrows`) into buf[rows][132].  The loads are unconditional
-// (from a clamped row; the zeros are selected when the values are stored): with branches around them the compiler cannot
-// count the loads in flight and waits for ALL of them -- the prefetch it has just issued -- before the stage's first MFMA.
-template <int W>
-__device__ __forceinline__ void stage_load(const float *__restrict__ base, int ld, int row0, int nrows,
-                                           float4 (&regs)[16 / W][2])
-{
-    const int c8 = threadIdx.x & 15;             // which 8-float chunk of the 128
-    const int rr = threadIdx.x >> 4;             // 4*W rows per pass
-#pragma unroll
-    for (int pass = 0; pass < 16 / W; ++pass) {
-        const int row = min(row0 + pass * (4 * W) + rr, nrows - 1);
-        const float4 *src = reinterpret_cast<const float4 *>(base + (size_t)row * ld + 8 * c8);
-        regs[pass][0] = src[0];
-        regs[pass][1] = src[1];
-    }
-}
-
-template <int W>
-__device__ __forceinline__ void stage_store(float *buf, const float4 (&regs)[16 / W][2], int row0, int nrows)
-{
-    const int c8 = threadIdx.x & 15;
-    const int rr = threadIdx.x >> 4;
-#pragma unroll
-    for (int pass = 0; pass < 16 / W; ++pass) {
-        float4 *dst = reinterpret_cast<float4 *>(buf + (pass * (4 * W) + rr) * kLdsStride + 8 * c8);
-        const bool real = row0 + pass * (4 * W) + rr < nrows;
-        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        const float4 a = real ? regs[pass][0] : z, b = real ? regs[pass][1] : z;
-        dst[0] = make_float4(a.x, a.z, b.x, b.z);      // even d: k-parity 0
-        dst[1] = make_float4(a.y, a.w, b.y, b.w);      // odd d : k-parity 1
-    }
-}
-
-// The scores of one staged block of database rows (RT row tiles of 32) against the wavefront's resident queries, folded into
-// the running top-2 in ascending database index.
-template <int CT, int RT>
-__device__ __forceinline__ void stage_scores(const float *cur, const float (&bq)[CT][64], Top2 (&top)[CT], int stage_row0)
-{
-    const int lane = threadIdx.x & 63;
-    const int col = lane & 31;
-    const int half = lane >> 5;
-    f32x16 acc[RT][CT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[rt][ct][r] = 0.0f;
-
-    const float *a0p = cur + col * kLdsStride + 4 * half;
-    const float *a1p = a0p + 32 * kLdsStride;
-#pragma unroll
-    for (int m = 0; m < 16; ++m) {
-        const float4 a0 = *reinterpret_cast<const float4 *>(a0p + 8 * m);
-        const float a0v[4] = { a0.x, a0.y, a0.z, a0.w };
-        float a1v[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-        if (RT == 2) {
-            const float4 a1 = *reinterpret_cast<const float4 *>(a1p + 8 * m);
-            a1v[0] = a1.x; a1v[1] = a1.y; a1v[2] = a1.z; a1v[3] = a1.w;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-                acc[0][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0v[k], bq[ct][4 * m + k], acc[0][ct], 0, 0, 0);
-                if (RT == 2) acc[RT - 1][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1v[k], bq[ct][4 * m + k], acc[RT - 1][ct], 0, 0, 0);
-            }
-    }
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int p2 = stage_row0 + rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) top2_push(top[ct], acc[rt][ct][r], p2);
-        }
-}
 
 // One block: W waves x CT column tiles = 32*CT*W queries against database rows [row_begin, row_end).
 // W = 8 puts two wavefronts on every SIMD of the CU (one block per CU, 67.6 KB of LDS): while one
@@ -276,61 +195,8 @@ __device__ __forceinline__ void match_body(const float *__restrict__ q, int nq, 
         }
         return;
     }
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-        Top2 o;
-        o.best = __shfl_xor(top[ct].best, 32);
-        o.second = __shfl_xor(top[ct].second, 32);
-        o.idx = __shfl_xor(top[ct].idx, 32);
-        const Top2 mrg = top2_merge(top[ct], o);
-        const int p1 = q0 + (wave * CT + ct) * 32 + col;
-        if (half == 0 && p1 < nq) {
-            // agent-scope stores (written through this XCD's L2): the block that merges may sit on another XCD
-            const size_t w = (size_t)split * nq + p1;
-            __hip_atomic_store(&ws_best[w], mrg.best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&ws_second[w], mrg.second, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&ws_idx[w], mrg.idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    // ---- the LAST split block of this query block merges the partials (ascending database ranges) and writes the results,
-    // either to plain arrays or into the SiftPoint fields MatchSiftData updates (matching.cu:391-395): no merge launch.
-    // Ordering without a fence: the partials are agent-scope stores, acknowledged (vmcnt) before the block's ticket is drawn;
-    // the merging block reads them with agent-scope loads after its own ticket came back.
-    __shared__ int s_last;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned int t = atomicAdd(&tickets[qblock], 1u);
-        s_last = (t == (unsigned int)nsplit - 1u) ? 1 : 0;
-        if (s_last) __hip_atomic_store(&tickets[qblock], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // ready for the next call
-    }
-    __syncthreads();
-    if (!s_last) return;
-    for (int k = threadIdx.x; k < CT * 32 * W; k += blockDim.x) {
-        const int p1 = q0 + k;
-        if (p1 >= nq) break;
-        Top2 t{ __hip_atomic_load(&ws_best[p1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
-                __hip_atomic_load(&ws_second[p1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
-                __hip_atomic_load(&ws_idx[p1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) };
-        // sixteen splits' partials are requested before the first is merged: one memory round trip per sixteen splits, not
-        // per split (the loads are atomics, which the compiler never hoists over the merge of the previous split); one-match
-        // launches have up to 16 or 17 splits for the small sizes, i.e. ONE trip
-        constexpr int kMergeBatch = 16;
-        for (int sp0 = 1; sp0 < nsplit; sp0 += kMergeBatch) {
-            Top2 part[kMergeBatch];
-#pragma unroll
-            for (int u = 0; u < kMergeBatch; ++u) {
-                const size_t w = (size_t)min(sp0 + u, nsplit - 1) * nq + p1;
-                part[u].best = __hip_atomic_load(&ws_best[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                part[u].second = __hip_atomic_load(&ws_second[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                part[u].idx = __hip_atomic_load(&ws_idx[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-#pragma unroll
-            for (int u = 0; u < kMergeBatch; ++u)
-                if (sp0 + u < nsplit) t = top2_merge(t, part[u]);
-        }
-        match_emit(p1, t, out_best, out_second, out_idx, sift1, sift2);
-    }
+    // ---- the ticket merge: the partials, and the last split block to arrive merges them and writes the results ----
+#include "match_ticket_merge.inc"
 }
 
 template <int CT, int W, bool POLL>
@@ -561,29 +427,9 @@ int launch_match(sfm_ctx *ctx, const float *d1, int n1, int ld1, const float *d2
     }
     if (pick == SFM_MATCH_FUSED) return launch_match_fused(ctx, d1, n1, ld1, d2, n2, ld2, d_best, d_second, d_index, sift1, sift2);
     ctx->last_match_kernel = SFM_MATCH_EXACT;
-    // three configurations (column tiles per wavefront, wavefronts per block), crossovers measured with profiles/match_cfg_probe.py
-    // (TFLOP/s at n x n):  n      3000   4500   5500   7000   9000   10000  12000  14000  16384
-    //                      (1,4)  64     79     72     79     81
-    //                      (1,8)  58     78     91     98     105    104    110    106    123
-    //                      (2,8)  42     70     84     91     103    102    112    118    127
-    static const char *cfg_env = getenv("SFM_MATCH_CFG");    // profiling only: "ct,wv"
-    int ct = n1 > 11000 ? 2 : 1;
-    int wv = n1 > 4500 ? 8 : 4;                      // wavefronts per block
-    if (cfg_env && cfg_env[0] && cfg_env[1] && cfg_env[2]) { ct = cfg_env[0] == '2' ? 2 : 1; wv = cfg_env[2] == '8' ? 8 : 4; }
-    const int qper = ct * 32 * wv;                          // queries per block
-    const int qblocks = (n1 + qper - 1) / qper;
-    // (query block, database split) pairs: as many as fit in ONE round over the CUs, not more -- rounding the split
-    // count up (11 x 24 = 264 blocks on 256 CUs) costs a whole second round (12000 x 12000: 0.44 -> 0.30 ms), and two
-    // blocks per CU of the small configuration only add prologues and partials (2048 x 2048: 0.026 -> 0.022 ms)
-    int nsplit = ctx->num_cus / qblocks;
-    const int max_split = (n2 + kRowsPerStage - 1) / kRowsPerStage;
-    if (nsplit > max_split) nsplit = max_split;
-    if (nsplit < 1) nsplit = 1;
-    // a split is a whole number of 32-row tiles (its last stage runs one row tile instead of two when 32 rows or fewer are
-    // left): 2155 x 2170 is 14 splits of 160 rows = 2.5 stages of matrix work per wavefront instead of 12 x 192 = 3
-    int rows_per_split = (n2 + nsplit - 1) / nsplit;
-    rows_per_split = round_up(rows_per_split, kRowsPerStage / 2);
-    nsplit = (n2 + rows_per_split - 1) / rows_per_split;
+    // the configuration by n1 and the split of the database over blocks (match_mfma.hpp)
+    const ExactMatchPlan plan = exact_match_plan(ctx->num_cus, n1, n2);
+    const int ct = plan.ct, wv = plan.wv, qblocks = plan.qblocks, nsplit = plan.nsplit, rows_per_split = plan.rows_per_split;
 
     unsigned int *tickets; float *wb, *wsnd; int *wi;
     const int wrc = match_partials_workspace(ctx, qblocks, nsplit, n1, &tickets, &wb, &wsnd, &wi);

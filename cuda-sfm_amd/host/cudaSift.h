@@ -142,6 +142,33 @@ inline double MatchSiftData(SiftData &data1, SiftData &data2)
     return ms;
 }
 
+// Not part of the reference API: MatchSiftData restricted to the epipolar band of d_F (sfm_match_guided) -- 9 DEVICE floats,
+// u2^T F u1 = 0 with u1 a feature of data1 and u2 one of data2, in pixels (SfM::Image_pair::fundamental of sfm.h) -- band_px wide
+// on either side of the lines.  The same fields come back; a feature with no candidate in the band gets match -1, score 0.
+inline double MatchSiftDataGuided(SiftData &data1, SiftData &data2, const float *d_F, float band_px = 4.0f)
+{
+    sfm_ctx *ctx = sfm_facade::context();
+    const int numPts1 = data1.numPts, numPts2 = data2.numPts;
+    if (!numPts1 || !numPts2) return 0.0;
+    if (data1.d_data == nullptr || data2.d_data == nullptr) return 0.0;
+    sfm_match_guided_params p;
+    sfm_match_guided_default_params(&p);
+    p.band_px = band_px;
+    SFM_FACADE_CALL(sfm_ctx_timer_start(ctx));
+    SFM_FACADE_CALL(sfm_match_guided(ctx, data1.d_data, numPts1, data2.d_data, numPts2, d_F, &p));
+    if (data1.h_data != nullptr) {
+        float *h_ptr = &data1.h_data[0].score;
+        const float *d_ptr = &data1.d_data[0].score;     // address arithmetic only, never dereferenced on the host
+        SFM_FACADE_CALL(sfm_copy_to_host_2d(ctx, h_ptr, sizeof(SiftPoint), d_ptr, sizeof(SiftPoint), 5 * sizeof(float), (size_t)numPts1));
+    }
+    float ms = 0.f;
+    SFM_FACADE_CALL(sfm_ctx_timer_stop(ctx, &ms));
+#ifndef VERBOSE
+    std::printf("MatchSiftDataGuided time =    %.2f ms\n", ms);
+#endif
+    return ms;
+}
+
 // matching.cu:1000-1087.  Same signature and defaults as the reference (cudaSift.h:43); returns the
 // elapsed milliseconds.  The sample is seeded (SFM_HOMOGRAPHY_SEED, default 0) instead of rand().
 #ifndef SFM_HOMOGRAPHY_SEED

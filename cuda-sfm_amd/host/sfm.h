@@ -206,6 +206,7 @@ struct AlignScratch {
 
 class Image_pair {
     sfm_pair *pair_ = nullptr;
+    float *d_F_ = nullptr;                     // fundamental()'s result, allocated at its first call
     int num_points_ = 0;
     int pose_mode_ = SFM_POSE_REFERENCE;       // drop-in default: the reference's own behaviour
     sfm_ransac_params params_;
@@ -217,7 +218,7 @@ public:
     }
     Image_pair(const Image_pair &) = delete;
     Image_pair &operator=(const Image_pair &) = delete;
-    ~Image_pair() { if (pair_) sfm_pair_destroy(pair_); }
+    ~Image_pair() { if (d_F_) sfm_device_free(sfm_facade::context(), d_F_); if (pair_) sfm_pair_destroy(pair_); }
 
     // ---- the reference's call surface --------------------------------------------------------
     void fillXU(SiftPoint *data) { SFM_FACADE_CALL(sfm_fill_xu(pair_, data)); }               // sfm.cu:80-92
@@ -295,6 +296,14 @@ public:
     }
     sfm_refine_report getRefineReport() { sfm_refine_report r; SFM_FACADE_CALL(sfm_get_refine_report(pair_, &r)); return r; }
     void getRefinedPose(float P[16], float E[9]) { SFM_FACADE_CALL(sfm_get_refined_pose(pair_, P, E)); }   // [R|t; 0 0 0 1], [t]x R
+    // the pair's fundamental matrix for MatchSiftDataGuided (sfm_pair_fundamental): 9 DEVICE floats owned by the pair, from the
+    // refined E or (refined = false) the E of estimateE; view 1 = the records' (xpos, ypos).  Enqueue only; each call overwrites it.
+    const float *fundamental(bool refined = true)
+    {
+        if (!d_F_) SFM_FACADE_CALL(sfm_device_alloc(sfm_facade::context(), 9 * sizeof(float), (void **)&d_F_));
+        SFM_FACADE_CALL(sfm_pair_fundamental(pair_, refined ? 1 : 0, d_F_));
+        return d_F_;
+    }
     std::vector<float> getRefinedPoints()   // 4 x N: used points refined, the others triangulated against the refined pose
     {
         std::vector<float> p((size_t)4 * num_points_);

@@ -137,6 +137,31 @@ int sfm_match_soa(sfm_ctx *ctx, const float *d_desc1, int n1, int ld1,
                   const float *d_desc2, int n2, int ld2,
                   float *d_best, float *d_second, int32_t *d_index);
 
+/* ---- guided match: the descriptor match restricted to a pair's epipolar band ---------------------
+ * For every record of d_sift1: best / second-best dot product (sfm_match's scores, bit for bit) over the rows of d_sift2
+ * that pass the gate under d_F, lowest index on ties; writes score, match, match_xpos, match_ypos and ambiguity exactly as
+ * sfm_match does (no row in the band: match -1, score 0, positions 0, ambiguity 0).  d_F: 9 DEVICE floats, row-major, in
+ * pixel coordinates; a true correspondence has u2^T F u1 = 0 with u1 = (xpos, ypos, 1) of the d_sift1 record (view 1) and
+ * u2 = (xpos, ypos, 1) of the d_sift2 record (view 2: what the match leaves in match_xpos / match_ypos); the scale of F
+ * does not matter.  A row passes when u2 lies within band_px pixels of the line F u1 AND u1 within band_px pixels of the
+ * line F^T u2.  NaN positions, a feature on the epipole, and an F that is zero or not finite pass nothing.
+ * The quirk flags and sfm_ctx_set_match_kernel do not apply (sfm_ctx_last_match_kernel keeps its value); n1 == 0 or
+ * n2 == 0 is a no-op.  All checks precede the first enqueue: on SFM_E_INVALID (null arguments, negative sizes, band_px not
+ * finite or <= 0, non-zero reserved) nothing is written. */
+typedef struct sfm_match_guided_params {
+    float   band_px;       /* finite, > 0; default 4.0 (the registration's threshold_px) */
+    int32_t reserved[4];   /* must be zero (else SFM_E_INVALID)                           */
+} sfm_match_guided_params;
+void sfm_match_guided_default_params(sfm_match_guided_params *p);
+int sfm_match_guided(sfm_ctx *ctx, sfm_sift_point *d_sift1, int n1, const sfm_sift_point *d_sift2, int n2,
+                     const float *d_F, const sfm_match_guided_params *p);            /* enqueue only */
+/* The fundamental matrix of a pair for sfm_match_guided: F = Kinv^T E Kinv from the pair's own K^-1, transposed so that the
+ * pair's OWN records satisfy the convention above -- view 1 (u1) is (xpos, ypos), the side fillXU reads into X0 / U0, view 2
+ * (u2) is (match_xpos, match_ypos).  refined = 0: the E of estimateE (needs E); refined = 1: the refined E of
+ * sfm_refine_two_view (needs the refinement); SFM_E_STATE otherwise.  Computed in fp64 on the device, scaled to unit
+ * Frobenius norm (all zero where E is zero or not finite), rounded once.  Reads the pair, writes d_F (9 DEVICE floats). */
+int sfm_pair_fundamental(sfm_pair *pair, int refined, float *d_F);                   /* enqueue only */
+
 /* ---- SIFT extraction: ExtractSift (CudaSift/cudaSiftH.cu:72-232; cudaSift.h:37-39) ---------------------
  * d_image: height x pitch floats on the device (8-bit grey values as float, what CudaImage::Download
  * uploads).  Builds the pyramid (optional 2x upsampling, low pass init_blur, num_octaves levels),
