@@ -18,7 +18,7 @@
 //     software-pipelined by hand: while the vector unit scans the accumulators of step k, the matrix cores work on step
 //     k + 1 and the fragments of step k + 2 are on their way from LDS (two accumulator sets, sched_group_barrier);
 //     round 11, per-tile rule, large launches: the passes come in PAIRS -- 64 hypotheses, one per lane, prepared at once and scanned in
-//     two halves (kPair below);
+//     two halves (kPair below); round 13: the two halves share ONE walk of the tile -- a block's fragments are read once (kInter);
 //   * lanes with a surviving pair append one word per two steps to the wavefront's ring in LDS; 64 entries at a time go
 //     through the exact filter, one entry per lane, and inliers bump the hypothesis' counter in LDS;
 //   * partial counts reach counts[] through integer atomics (order-independent, so the result is deterministic): large launches
@@ -193,6 +193,10 @@ constexpr int kPfVarSinglePass = 64;
 // (kPfTagScan, prefilter_math.hpp: pf_ring_row), so the first scan's leftovers ride in the second scan's full flushes.  This bit keeps
 // round 11's drain between the scans (lab bench: reserved[1] = 21).
 constexpr int kPfVarPairDrain = 128;
+// Round 13: a pair's two scans run INTERLEAVED over one walk of the tile -- every 32-point block's B fragments are read from LDS once
+// and multiplied with the A fragments of hypotheses 0..31 and then with those of 32..63.  This bit keeps round 12's two
+// scans back to back, ring carried (lab bench: reserved[1] = 22).
+constexpr int kPfVarPairSeq = 256;
 
 // FL2 (experiment): a ring of 256 entries, flushed 128 at a time -- two entries per lane, their LDS reads issued together
 // WIDE (experiment): ring entries of 16 bytes that cover FOUR steps (two conversions): half as many appends
@@ -202,12 +206,12 @@ constexpr int kPfVarPairDrain = 128;
 // of the NEXT pipelined call is meant to run next to it (sfm_estimate_E_pipelined), so 4 scoring wavefronts must leave a solve wavefront's
 // registers free on every SIMD: 4 x 96 + 88 (ransac_solve_lanes1_qr: 88, allocated in eights) = 472 of 512.  The two instances the
 // product runs are compiled for five wavefronts per SIMD, which caps them at 96; the lab bench's variants keep the default.
-// The paired passes of the per-tile rule (VAR = 0) hold the second scan's fragments -- eight registers -- across the first scan: that
+// The paired passes of the per-tile rule (VAR = 0) hold both halves' fragments -- eight registers more -- through the scan: that
 // instance may take 104 (4 x 104 + 88 = 504), which no whole number of wavefronts per SIMD asks for, so it is compiled for four and
 // held to 104 by tests/test_register_budget.py.
 constexpr int pf_score_waves_per_simd(int var, int rule, int fl2, int pipe, int wide, int prio)
 {
-    if ((var == 0 || var == kPfVarPairDrain) && rule == kPfRuleBandTile && !fl2 && !pipe && !wide && !prio) return 4;
+    if ((var == 0 || var == kPfVarPairDrain || var == kPfVarPairSeq) && rule == kPfRuleBandTile && !fl2 && !pipe && !wide && !prio) return 4;
     return ((var & kPfVarTickets) == 0 && (rule == kPfRuleBandTile || rule == kPfRuleBandPack) && !fl2 && !pipe && !wide && !prio) ? 5 : 4;
 }
 
@@ -254,9 +258,12 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
     static_assert(!(VAR & kPfVarSinglePass) || (kTile && VAR == kPfVarSinglePass), "single passes: the per-tile rule's summing instance");
     // paired passes: the unit of work is 64 hypotheses (two scans of 32) prepared at once, one hypothesis per lane
     static_assert(!(VAR & kPfVarPairDrain) || (kTile && VAR == kPfVarPairDrain), "paired passes drained between the scans: the per-tile rule's summing instance");
-    constexpr bool kPair = kTile && kTail9 && (VAR == 0 || VAR == kPfVarPairDrain);
+    static_assert(!(VAR & kPfVarPairSeq) || (kTile && VAR == kPfVarPairSeq), "paired passes scanned back to back: the per-tile rule's summing instance");
+    constexpr bool kPair = kTile && kTail9 && (VAR == 0 || VAR == kPfVarPairDrain || VAR == kPfVarPairSeq);
     // the ring is carried across the boundary between a pair's scans: its entries name their scan themselves
-    constexpr bool kCarry = kPair && VAR == 0;
+    constexpr bool kCarry = kPair && VAR != kPfVarPairDrain;
+    // a pair's two scans share one walk of the tile: a block's B fragments are read once and meet both halves' A fragments
+    constexpr bool kInter = kPair && VAR == 0;
     constexpr int kRows = kPair ? kPfPairRows : kPfPassRows, kUnit = kRows;       // rows of the wavefront's table = hypotheses per unit
     constexpr int kDrainMore = !kTail9 ? 0 : (VAR & kPfVarDrainK1) ? 1 : (VAR & kPfVarDrainK7) ? 7 : (VAR & kPfVarDrainLocal) ? 3 : 0;
     constexpr bool kDecodeTable = !(kTail9 && (VAR & kPfVarClosedDecode));
@@ -432,7 +439,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
     const ThrBand band = make_band(thr);
     uint32_t passes_done = 0;
 #if SFM_AB
-    uint32_t carried = 0;                                 // ring entries held when a second scan began, over this wavefront's pairs (clk[6] >> 32)
+    uint32_t carried = 0;                                 // ring entries held when a second scan began (interleaved scans: whenever a group of the second half appends), over this wavefront's pairs (clk[6] >> 32)
 #endif
 
     // ---- 32 hypotheses per pass of this wavefront (no block-level synchronisation from here on)
@@ -442,7 +449,8 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
         const int nvalid_unit = (int)min((uint32_t)kUnit, count - h_first);
         // a scan's 32 rows: `nvalid` of them are hypotheses, `hoff` is the first one's row in the table (paired: 32 x scan)
         int nvalid = min(nvalid_unit, kPfGroup), hoff = 0;
-        const int nscan = (kPair && nvalid_unit > kPfGroup) ? 2 : 1;
+        const bool two_scans = kPair && nvalid_unit > kPfGroup;
+        const int nscan = (two_scans && !kInter) ? 2 : 1;               // scans run one after the other (interleaved: the two share the walk below)
 #if SFM_AB
         const bool probe1 = probe && passes_done == 0u;
         unsigned long long w_scan_end = 0;
@@ -461,11 +469,13 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
         // (paired: the flag is the lane's own -- the ballot's low word names rows of the first scan, its high word rows of the second)
         const unsigned long long scan_rows = __ballot(key0 != 0u);
         int head = 0, nq = 0;                       // ring state (wave-uniform)
+        // (interleaved scans patch both halves before the walk, when `hoff` still names the first: the second half's rows patch bfrag_n0 / n1)
         auto patch_zero_divisor_rows = [&](int sc) {
             uint32_t todo = kPair ? (uint32_t)(sc ? scan_rows >> 32 : scan_rows) : ((uint32_t)scan_rows | (uint32_t)(scan_rows >> 32));
             uint32_t survive = 0u;                                      // rows whose pairs must all survive in this tile
+            const int row0 = kInter ? kPfGroup * sc : hoff;
             while (todo) {
-                const int r = __builtin_ctz(todo) + hoff;
+                const int r = __builtin_ctz(todo) + row0;
                 todo &= todo - 1u;
                 const float se[6] = { etab[6 * kRows + r], etab[2 * kRows + r], etab[r], etab[3 * kRows + r], etab[7 * kRows + r], etab[4 * kRows + r] };          // e0 .. e5 (slots 6 2 0 3 7 4)
                 bool z = false;
@@ -473,12 +483,17 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
                     const float4 q = pts[j * 64 + lane];
                     z = z || prefilter_zero_divisor(se, q.x, q.z);              // NaN padding never compares equal to 0
                 }
-                if (__ballot(z) != 0ull) survive |= 1u << (r - hoff);
+                if (__ballot(z) != 0ull) survive |= 1u << (r - row0);
             }
             if (survive != 0u && ((survive >> row) & 1u)) {             // nt = 0, G = 2^-10 for real points (prefilter_hyp_slots)
                 const h8 zero = {};
+                if (kInter && sc) {
+                    bfrag_n0 = zero; bfrag_n1 = zero;
+                    if (half) bfrag_n1[3] = (_Float16)1.0f;
+                } else {
                 afrag.n0 = zero; afrag.n1 = zero; afrag.t = zero;
                 if (half) { afrag.n1[3] = (_Float16)1.0f; afrag.t[7] = (_Float16)0.0009765625f; }      // k-slots 27 and 15
+                }
             }
         };
 
@@ -612,6 +627,9 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
 
         for (int sc = 0; ; ++sc) {
         patch_zero_divisor_rows(sc);
+        if constexpr (kInter) {                                         // rows flagged in the ballot's high word: the second half's fragments
+            if (two_scans) patch_zero_divisor_rows(1);
+        }
 #if SFM_AB
         if (sc == 0) PF_PHASE(3);
         else if (probe1) reinterpret_cast<uint32_t *>(clk + 3)[1] = (uint32_t)(wall_clock64() - w_scan_end);       // first scan's end -> second scan's start
@@ -670,11 +688,14 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
         } else if constexpr (kPack) {
         // ---- packed scan: the four MFMAs of two steps, then (under them) the survivors of the previous two, then ONE conversion
         // that waits for the MFMAs -- the other wavefronts of the SIMD issue meanwhile
-        PfFrags fa = load_point_frags<RULE>(frag_lane, 0), fb = load_point_frags<RULE>(frag_lane, 1);
+        // (interleaved instance: each of its two loops asks for the fragments of blocks 0 and 1 itself)
+        PfFrags fa = kInter ? PfFrags{} : load_point_frags<RULE>(frag_lane, 0), fb = kInter ? PfFrags{} : load_point_frags<RULE>(frag_lane, 1);
         lds_ch8 *fp = frag_lane + 2 * (LT::kBlockBytes / 16);
         f16v g0, n0, n1;
         u6v dpk = {};
-        auto append = [&](const u6v &d, int pp) {
+        // (scan_tag: kPfTagScan for a group of the second half's rows in the interleaved walk, where lane_tag never takes the bit -- it is
+        // clear in lane_tag, so it rides in the wave-uniform addend; 0 everywhere else)
+        auto append = [&](const u6v &d, int pp, uint32_t scan_tag) {
             const uint32_t rej32 = pack_reject_bits(d);
             const bool mine = rej32 != 0xFFFFFFFFu;
             const unsigned long long any = __ballot(mine);
@@ -682,7 +703,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
             if (any) {
                 while (nq >= 64) flush(64, kInLoop);
                 const int slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(any >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)any, 0u));
-                if (mine) *ring_at(((uint32_t)(head + nq) + (uint32_t)slot) * 8u) = u2v{ ~rej32, lane_tag + ((uint32_t)pp << 10) };
+                if (mine) *ring_at(((uint32_t)(head + nq) + (uint32_t)slot) * 8u) = u2v{ ~rej32, lane_tag + (((uint32_t)pp << 10) | scan_tag) };
                 nq += __builtin_popcountll(any);
             }
         };
@@ -698,11 +719,61 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
             }
         };
         auto after_phase = [&](const u6v &d, int pp) {      // what happens to the conversion of phase pp
-            if (!WIDE) { append(d, pp); return; }
+            if (!WIDE) { append(d, pp, 0u); return; }
             const uint32_t rej32 = pack_reject_bits(d);
             if ((pp & 1) == 0) rej_even = rej32;
             else append_w(rej_even, rej32, pp - 1);
         };
+        bool walked = false;
+        if constexpr (kInter) {
+        // ---- a pair's two scans over ONE walk of the tile: the B fragments of two 32-point blocks meet the A fragments of rows 0..31
+        // and then, from the same registers, those of rows 32..63; the loads of the next two blocks go out behind the second group.
+        // One accumulator set and one conversion register set alternate between the groups, so each group's survivors are appended
+        // under the other group's MFMAs; entries of the second group carry kPfTagScan (decide_first takes the row from the table).
+        if (two_scans) {
+            const PfFrags bfrag = { bfrag_n0, bfrag_n1, h8{} };
+            // (an address of its own: with one load feeding both loops the fragments of the plain loop below were given a second set of
+            // sixteen registers and copies into them -- 121 registers instead of 102)
+            lds_ch8 *fl = frag_lane;
+            asm("" : "+v"(fl));
+            fa = load_point_frags<RULE>(fl, 0); fb = load_point_frags<RULE>(fl, 1);
+            fp = fl + 2 * (LT::kBlockBytes / 16);
+            for (int pp = 0; pp < npp; ++pp) {
+                SFM_PHASE("scan_two_steps");
+                mfma_step<RULE>(afrag, fa, g0, n0);
+                mfma_step<RULE>(afrag, fb, g0, n1);
+                __builtin_amdgcn_sched_barrier(0);
+                if (pp > 0) {
+#if SFM_AB
+                    carried += (uint32_t)nq;
+#endif
+                    append(dpk, pp - 1, kPfTagScan);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                dpk = __builtin_amdgcn_cvt_scalef32_2xpk16_bf6_f32(n0, n1, 1.0f);
+                __builtin_amdgcn_sched_barrier(0);
+                SFM_PHASE("scan_two_steps");
+                mfma_step<RULE>(bfrag, fa, g0, n0);
+                mfma_step<RULE>(bfrag, fb, g0, n1);
+                // (the last iteration reads past the tile, inside the block's LDS, as the plain loop below does)
+                fa = load_point_frags<RULE>(fp, 0);
+                fb = load_point_frags<RULE>(fp, 1);
+                fp += 2 * (LT::kBlockBytes / 16);
+                __builtin_amdgcn_sched_barrier(0);
+                append(dpk, pp, 0u);
+                __builtin_amdgcn_sched_barrier(0);
+                dpk = __builtin_amdgcn_cvt_scalef32_2xpk16_bf6_f32(n0, n1, 1.0f);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#if SFM_AB
+            carried += (uint32_t)nq;
+#endif
+            append(dpk, npp - 1, kPfTagScan);
+            walked = true;
+        }
+        }
+        if (!walked) {
+        if constexpr (kInter) { fa = load_point_frags<RULE>(frag_lane, 0); fb = load_point_frags<RULE>(frag_lane, 1); }
         for (int pp = 0; pp < npp; ++pp) {
             SFM_PHASE("scan_two_steps");
             if (PRIO == 1) __builtin_amdgcn_s_setprio(2);
@@ -722,6 +793,7 @@ void ransac_score_prefilter(const float *__restrict__ X0, const float *__restric
         }
         after_phase(dpk, npp - 1);
         if (WIDE && (npp & 1)) append_w(rej_even, 0xFFFFFFFFu, npp - 1);      // an odd number of phases: the last one alone
+        }
         } else {
         PfFrags fa = load_point_frags<RULE>(frag_lane, 0), fb = load_point_frags<RULE>(frag_lane, 1);
         f16v g0, n0, g1, n1;
@@ -1317,7 +1389,7 @@ static int pf_rule_switch(const sfm_ransac_params &p)      // lab bench: the rul
     if (SFM_SW(p, 3) == 5 || SFM_SW(p, 1) == 5 || SFM_SW(p, 1) == 7 || SFM_SW(p, 1) == 9) return kPfRuleBand;
     if (SFM_SW(p, 3) == 6 || SFM_SW(p, 1) == 11 || SFM_SW(p, 1) == 12) return kPfRuleBandPack;
     if (SFM_SW(p, 3) == 7 || SFM_SW(p, 1) == 13 || SFM_SW(p, 1) == 14 || SFM_SW(p, 1) == 15) return kPfRuleBandTile;
-    return -1;          // (reserved[1] = 19 / 20 / 21, paired / single / paired-and-drained passes of the summing per-tile instance, leave the rule to the product's choice)
+    return -1;          // (reserved[1] = 19 .. 22, paired / single / paired-and-drained / paired back-to-back passes of the summing per-tile instance, leave the rule to the product's choice)
 }
 
 // The product's choice.  Per-tile band constants (tiles = runs of a Morton-ordered copy of the correspondences, sigma and the coefficient
@@ -1370,19 +1442,22 @@ int prefilter_tile_points(const sfm_pair *pair, const sfm_ransac_params &p) { re
 // per-hypothesis rule of a first call as it is).
 // Round 12: the paired passes carry the survivor ring from a pair's first scan into its second (an entry names its scan).  Lab bench:
 // reserved[1] = 21 is 19 with round 11's drain between the scans (kPfVarPairDrain), so that the two can be alternated on one box.
+// Round 13: a pair's two scans share one walk of the tile (VAR = 0).  Lab bench: reserved[1] = 22 is 19 with round 12's two scans back
+// to back, ring carried (kPfVarPairSeq).
 static int pf_tail_var(const sfm_pair *pair, const sfm_ransac_params &p, uint32_t count)
 {
     const bool large = pf_sums_counts_at(count, pair->ld, pf_tile_of(pair, p));
     if (SFM_SW(p, 1) == 19) return 0;
     if (SFM_SW(p, 1) == 20) return pair->pf_rule == kPfRuleBandTile ? kPfVarSinglePass : 0;
     if (SFM_SW(p, 1) == 21) return pair->pf_rule == kPfRuleBandTile ? kPfVarPairDrain : 0;
+    if (SFM_SW(p, 1) == 22) return pair->pf_rule == kPfRuleBandTile ? kPfVarPairSeq : 0;
     if (pair->pf_rule == kPfRuleBandTile && SFM_SW(p, 1) == 16) return kPfVarDrainK1;
     if (pair->pf_rule == kPfRuleBandTile && SFM_SW(p, 1) == 17) return kPfVarDrainK7;
     int var = 0;
     const bool lab = SFM_SW(p, 3) >= 8 && SFM_SW(p, 3) < 16;
     if (lab && (SFM_SW(p, 3) & 1)) var |= kPfVarDrainLocal;
     if (lab && (SFM_SW(p, 3) & 2)) var |= kPfVarClosedDecode;
-    const bool sum = (lab && (SFM_SW(p, 3) & 4)) ? false : (large || (SFM_SW(p, 1) >= 16 && SFM_SW(p, 1) <= 18));     // (19 .. 21: answered above)
+    const bool sum = (lab && (SFM_SW(p, 3) & 4)) ? false : (large || (SFM_SW(p, 1) >= 16 && SFM_SW(p, 1) <= 18));     // (19 .. 22: answered above)
     if (!sum) var |= kPfVarAnswerEpilogue;
     if (var == 0 && pair->pf_rule == kPfRuleBandTile && !pf_pairs_passes_at(count, pair->ld, pf_tile_of(pair, p))) var = kPfVarSinglePass;
     return var;
@@ -1412,8 +1487,8 @@ int launch_score_prefilter(sfm_pair *pair, ShardSlot &s, hipStream_t stream, con
     const int rule = pair->pf_rule;
     const int tail_var = pf_tail_var(pair, p, count);
     const bool wide = rule == kPfRuleBandTile && SFM_SW(p, 1) == 13;                     // (AB build: 16-byte ring entries covering four steps)
-    // (the instances the chain below picks for paired passes: <16, 0 or kPfVarPairDrain, kPfRuleBandTile> with none of the recorded variants' switches)
-    const bool paired_units = rule == kPfRuleBandTile && (tail_var == 0 || tail_var == kPfVarPairDrain) && waves == kPfWaves && !wide && SFM_SW(p, 1) != 14 && SFM_SW(p, 1) != 15;
+    // (the instances the chain below picks for paired passes: <16, 0, kPfVarPairDrain or kPfVarPairSeq, kPfRuleBandTile> with none of the recorded variants' switches)
+    const bool paired_units = rule == kPfRuleBandTile && (tail_var == 0 || tail_var == kPfVarPairDrain || tail_var == kPfVarPairSeq) && waves == kPfWaves && !wide && SFM_SW(p, 1) != 14 && SFM_SW(p, 1) != 15;
     const uint32_t nunits = paired_units ? (npass + 1u) / 2u : npass;             // what a wavefront takes at a time: a pass, or a pair of passes
     const uint32_t iters = (nunits + (uint32_t)waves - 1) / (uint32_t)waves;      // block iterations per tile
     // one block per CU is resident (152 KiB of LDS), so the grid is at most one block per CU, spread over the tiles: columns =
@@ -1460,6 +1535,7 @@ int launch_score_prefilter(sfm_pair *pair, ShardSlot &s, hipStream_t stream, con
         case kPfVarDrainK1: rcl = launch(&ransac_score_prefilter<16, kPfVarDrainK1, kPfRuleBandTile>); break;
         case kPfVarDrainK7: rcl = launch(&ransac_score_prefilter<16, kPfVarDrainK7, kPfRuleBandTile>); break;
         case kPfVarPairDrain: rcl = launch(&ransac_score_prefilter<16, kPfVarPairDrain, kPfRuleBandTile>); break;
+        case kPfVarPairSeq: rcl = launch(&ransac_score_prefilter<16, kPfVarPairSeq, kPfRuleBandTile>); break;
         default: set_error("pass-tail switches %d: no such instance", tail_var); break;
         }
 #undef PF_TAIL_CASE

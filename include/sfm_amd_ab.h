@@ -43,7 +43,10 @@ extern "C" {
  *       20 the single passes it replaced, with the summing epilogue, at every size (the product: between 2^21 and 2^22 partial counts) --
  *       21 the paired passes of 19 with the survivor ring EMPTIED between a pair's two scans, as in round 11 (the product and 19 carry the
  *       first scan's leftover entries into the second scan's flushes: an entry's tag names its scan; profiles/NOTES_r12.md) --
- *       19, 20 and 21 leave the choice between the per-hypothesis and the per-tile form to the product's rule (combine with [3] = 7);
+ *       22 the paired passes of 19 with the pair's two scans run BACK TO BACK over two walks of the tile, ring carried, as in round 12 (the
+ *       product and 19 interleave them over one walk: a 32-point block's fragments are read from LDS once and multiplied with both halves'
+ *       operands; profiles/NOTES_r13.md) --
+ *       19 .. 22 leave the choice between the per-hypothesis and the per-tile form to the product's rule (combine with [3] = 7);
  *   [2] k > 0: minimum hypothesis batches per scoring block (default 8); pre-filter kernel: grid columns;
  *   [3] 1 AUTO never picks SFM_KERNEL_PREFILTER; 2 the round-2 pre-filter kernel (csrc/ab/ransac_prefilter_r2.hip);
  *       3 per-hypothesis records from the stand-alone kernel instead of the lane-solve kernel; 4 the G rule of rounds 2-4
@@ -64,7 +67,10 @@ extern "C" {
  * coefficients prepared, [4] first 32-hypothesis block scanned and drained, [5] first pass done (counts and ticket out),
  * [6] number of passes wavefront 0 ran (paired passes: pairs) in the low 32 bits; paired passes also leave in [6] >> 32 the ring entries
  * wavefront 0 held when a second scan began, summed over its pairs (0 when the ring is emptied between the scans), and in [3] >> 32 the
- * ticks from the end of its first pair's first scan to the start of that pair's second ([3]'s low 32 bits: the stamp).
+ * ticks from the end of its first pair's first scan to the start of that pair's second ([3]'s low 32 bits: the stamp).  With the
+ * interleaved scans (the product's instance, reserved[1] = 19) no second scan begins: [6] >> 32 is the number of entries waiting in the
+ * ring each time a group of the second half's rows appends (once per two 32-point blocks), summed over the wavefront's two-scan pairs,
+ * and [3] >> 32 is 0.
  * Zero where the kernel that ran has no such probe.  Synchronises. */
 int sfm_ransac_last_phases(sfm_pair *pair, uint64_t ticks[8]);
 /* Profiling aid: when did every block / wavefront of the last pre-filter scoring launch start and finish?  20 words per
