@@ -70,7 +70,7 @@ EXPORTS = [
     "sfm_ctx_synchronize", "sfm_ctx_own_stream", "sfm_ctx_get_stream", "sfm_ctx_get_device", "sfm_ctx_timer_start", "sfm_ctx_timer_stop", "sfm_ctx_kernel_timing",
     "sfm_ctx_kernel_timing_read", "sfm_device_alloc", "sfm_device_free", "sfm_copy_to_device", "sfm_copy_to_host",
     "sfm_copy_to_host_2d", "sfm_copy_to_device_2d", "sfm_find_homography", "sfm_sift_temp_layout", "sfm_extract_sift", "sfm_extract_sift_begin", "sfm_extract_sift_end", "sfm_match", "sfm_match_soa",
-    "sfm_match_guided_default_params", "sfm_match_guided", "sfm_pair_fundamental",
+    "sfm_match_guided_default_params", "sfm_match_guided", "sfm_pair_fundamental", "sfm_pair_fundamentals",
     "sfm_pair_create", "sfm_pair_destroy", "sfm_pair_reset", "sfm_get_result", "sfm_fill_xu", "sfm_set_points", "sfm_ransac_default_params",
     "sfm_ransac_permutation_indices", "sfm_estimate_E", "sfm_ransac_score", "sfm_ransac_score_candidates", "sfm_ransac_score_into", "sfm_ransac_finalize",
     "sfm_ransac_finalize_key", "sfm_ransac_finalize_key_on", "sfm_ransac_score_into_slot", "sfm_estimate_E_pipelined", "sfm_pair_flush", "sfm_ransac_export_key", "sfm_pose_candidates", "sfm_choose_pose", "sfm_triangulate", "sfm_pose_chain",
@@ -361,6 +361,7 @@ _lib.sfm_match_guided_default_params.argtypes = [C.POINTER(MatchGuidedParams)]
 _lib.sfm_match_guided_default_params.restype = None
 _lib.sfm_match_guided.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.POINTER(MatchGuidedParams)]
 _lib.sfm_pair_fundamental.argtypes = [_vp, C.c_int, _vp]
+_lib.sfm_pair_fundamentals.argtypes = [C.POINTER(_vp), C.c_int, C.c_int, _vp]
 _lib.sfm_pair_create.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(_vp)]
 _lib.sfm_pair_destroy.argtypes = [_vp]
 _lib.sfm_fill_xu.argtypes = [_vp, _vp]
@@ -509,6 +510,20 @@ def match_guided(ctx, d_sift1, n1, d_sift2, n2, d_F, **kw):
     p = match_guided_params(**kw)
     _check(_lib.sfm_match_guided(ctx._h if ctx is not None else None, _ptr(d_sift1), int(n1), _ptr(d_sift2), int(n2), _ptr(d_F), C.byref(p)),
            "sfm_match_guided")
+
+
+def pair_fundamentals(pairs, refined=True, out=None):
+    """sfm_pair_fundamentals (enqueue only): ImagePair.fundamental for a list of pairs (one Context, none twice) in one launch,
+    as a (num_pairs, 9) float32 device tensor; row i is pairs[i].fundamental(refined), bit for bit."""
+    n = len(pairs)
+    if out is None:
+        device = torch.device("cuda", pairs[0].ctx.device) if n else torch.device("cuda")
+        out = torch.empty((n, 9), dtype=torch.float32, device=device)
+    if n == 0:
+        return out
+    handles = (_vp * n)(*[p._h.value for p in pairs])
+    _check(_lib.sfm_pair_fundamentals(handles, n, 1 if refined else 0, _ptr(out)), "sfm_pair_fundamentals")
+    return out
 
 
 def refine_params(**kw):

@@ -300,6 +300,7 @@ static int ctx_destroy_now(sfm_ctx *ctx)
     job_array_free(ctx->chain_jobs);
     if (ctx->chain_ws) (void)hipFree(ctx->chain_ws);
     job_array_free(ctx->ring_jobs);
+    job_array_free(ctx->fundamental_jobs);
     if (ctx->ring_ws) (void)hipFree(ctx->ring_ws);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     for (auto &t : ctx->tev) for (hipEvent_t e : t) if (e) (void)hipEventDestroy(e);
@@ -535,6 +536,24 @@ int sfm_pair_fundamental(sfm_pair *pair, int refined, float *d_F)
     if (refined) SFM_NEED(pair, kRefined); else SFM_NEED(pair, kE);
     SFM_HIP_TRY(hipSetDevice(pair->ctx->device));
     return launch_pair_fundamental(pair, refined, d_F);
+}
+
+int sfm_pair_fundamentals(sfm_pair *const *pairs, int num_pairs, int refined, float *d_F)
+{
+    // the checks that need no device first, all of them before anything is enqueued
+    SFM_REQUIRE(pairs && d_F, SFM_E_INVALID, "null argument");
+    SFM_REQUIRE(num_pairs >= 0, SFM_E_INVALID, "negative pair count");
+    SFM_REQUIRE(refined == 0 || refined == 1, SFM_E_INVALID, "refined must be 0 or 1");
+    if (num_pairs == 0) return SFM_OK;
+    int rc = list_entries_present(pairs, num_pairs, "pairs[%d] is null");
+    if (rc != SFM_OK) return rc;
+    sfm_ctx *ctx = pairs[0]->ctx;
+    rc = list_one_context_each_once(pairs, num_pairs, ctx, "pairs[%d] belongs to another context than pairs[0]", "pairs", "", "a pair has one F");
+    if (rc == SFM_OK) rc = list_flush(pairs, num_pairs);
+    if (rc == SFM_OK) rc = list_stages(pairs, num_pairs, "pairs", "", [refined](int) { return (uint32_t)(refined ? kRefined : kE); });
+    if (rc != SFM_OK) return rc;
+    SFM_HIP_TRY(hipSetDevice(ctx->device));
+    return launch_pair_fundamentals(ctx, pairs, num_pairs, refined, d_F);
 }
 
 // ---- ExtractSift ---------------------------------------------------------------------------------

@@ -208,6 +208,7 @@ struct sfm_ctx {
     // (align.hip); sfm_fuse_chain and sfm_adjust_chain: the FusePair (fuse_math.hpp) of every pair
     // sfm_close_ring: the RingLink (ring_math.hpp) of every link
     sfm::JobArray refine_jobs, register_jobs, view_points_jobs, adjust_jobs, align_jobs, fuse_jobs, chain_jobs, ring_jobs;
+    sfm::JobArray fundamental_jobs;    // sfm_pair_fundamentals: the FundamentalJob (pair_fundamentals.hip) of every pair
     void *fuse_ws = nullptr;           // sfm_fuse_chain: per-node keys, successors, path lengths and classes, the block counts (fuse.hip)
     size_t fuse_ws_bytes = 0;
     void *chain_ws = nullptr;          // sfm_adjust_chain and sfm_adjust_ring: states, points, partial bands, the band and the segments (chain_adjust.hip); sfm_intersect_tracks: the list of long tracks
@@ -491,5 +492,6 @@ int launch_match(sfm_ctx *ctx, const float *d1, int n1, int ld1, const float *d2
 // match_guided.hip: the exact matcher behind the epipolar gate of d_F (ticket merge), and F from a pair's E and K^-1
 int launch_match_guided(sfm_ctx *ctx, sfm_sift_point *sift1, int n1, const sfm_sift_point *sift2, int n2, const float *d_F, float band_px);
 int launch_pair_fundamental(sfm_pair *pair, int refined, float *d_F);
+int launch_pair_fundamentals(sfm_ctx *ctx, sfm_pair *const *pairs, int num_pairs, int refined, float *d_F);
 
 } // namespace sfm

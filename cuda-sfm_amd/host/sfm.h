@@ -416,6 +416,19 @@ inline std::vector<sfm_refine_report> refine_pairs(Image_pair *const *pairs, int
     return reports;
 }
 
+// the fundamental matrices of many pairs in one launch (sfm_pair_fundamentals), for MatchSiftDataGuided pair by pair: 9 * count
+// DEVICE floats, pair i's F at get() + 9 i, each bit-equal to that pair's own fundamental(refined); freed with the last copy of the handle
+inline std::shared_ptr<float> fundamentals(Image_pair *const *pairs, int count, bool refined = true)
+{
+    float *d_F = nullptr;
+    SFM_FACADE_CALL(sfm_device_alloc(sfm_facade::context(), (size_t)9 * sizeof(float) * (size_t)(count > 0 ? count : 1), (void **)&d_F));
+    std::shared_ptr<float> owner(d_F, [](float *p) { if (p) sfm_device_free(sfm_facade::context(), p); });
+    std::vector<sfm_pair *> handles;
+    for (int i = 0; i < count; ++i) handles.push_back(pairs[i] ? pairs[i]->handle() : nullptr);
+    SFM_FACADE_CALL(sfm_pair_fundamentals(handles.data(), count, refined ? 1 : 0, d_F));
+    return owner;
+}
+
 // a further view registered to each of many pairs in one batched call (sfm_register_views), on the refined points like
 // registerView: data[i] = image 1's records of pair i re-matched against that pair's new view; every pair is left as its own
 // registerView() leaves it, bit for bit; returns the reports in the order of the list (one wait for the device)

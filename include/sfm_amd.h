@@ -161,6 +161,13 @@ int sfm_match_guided(sfm_ctx *ctx, sfm_sift_point *d_sift1, int n1, const sfm_si
  * sfm_refine_two_view (needs the refinement); SFM_E_STATE otherwise.  Computed in fp64 on the device, scaled to unit
  * Frobenius norm (all zero where E is zero or not finite), rounded once.  Reads the pair, writes d_F (9 DEVICE floats). */
 int sfm_pair_fundamental(sfm_pair *pair, int refined, float *d_F);                   /* enqueue only */
+/* sfm_pair_fundamental for many pairs of one context in ONE launch: pair i's F at d_F + 9 i, bit-equal to the single call.
+ * SFM_E_INVALID for null arguments, num_pairs < 0, refined outside {0, 1}, pairs of different contexts or a pair named twice;
+ * SFM_E_STATE for a pair without E (refined = 0) or without the refinement (refined = 1).  All checks precede the first
+ * enqueue: nothing is written on a refusal.  Pending pipelined work of the pairs is flushed as the single call flushes it;
+ * num_pairs == 0 is a no-op. */
+int sfm_pair_fundamentals(sfm_pair *const *pairs, int num_pairs, int refined,
+                          float *d_F /* 9 * num_pairs device floats */);             /* enqueue only */
 
 /* ---- SIFT extraction: ExtractSift (CudaSift/cudaSiftH.cu:72-232; cudaSift.h:37-39) ---------------------
  * d_image: height x pitch floats on the device (8-bit grey values as float, what CudaImage::Download
