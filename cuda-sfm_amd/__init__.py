@@ -70,7 +70,7 @@ EXPORTS = [
     "sfm_ctx_synchronize", "sfm_ctx_own_stream", "sfm_ctx_get_stream", "sfm_ctx_get_device", "sfm_ctx_timer_start", "sfm_ctx_timer_stop", "sfm_ctx_kernel_timing",
     "sfm_ctx_kernel_timing_read", "sfm_device_alloc", "sfm_device_free", "sfm_copy_to_device", "sfm_copy_to_host",
     "sfm_copy_to_host_2d", "sfm_copy_to_device_2d", "sfm_find_homography", "sfm_sift_temp_layout", "sfm_extract_sift", "sfm_extract_sift_begin", "sfm_extract_sift_end", "sfm_match", "sfm_match_soa",
-    "sfm_match_guided_default_params", "sfm_match_guided", "sfm_pair_fundamental", "sfm_pair_fundamentals",
+    "sfm_match_guided_default_params", "sfm_match_guided", "sfm_pair_fundamental", "sfm_pair_fundamentals", "sfm_match_guided_pairs",
     "sfm_pair_create", "sfm_pair_destroy", "sfm_pair_reset", "sfm_get_result", "sfm_fill_xu", "sfm_set_points", "sfm_ransac_default_params",
     "sfm_ransac_permutation_indices", "sfm_estimate_E", "sfm_ransac_score", "sfm_ransac_score_candidates", "sfm_ransac_score_into", "sfm_ransac_finalize",
     "sfm_ransac_finalize_key", "sfm_ransac_finalize_key_on", "sfm_ransac_score_into_slot", "sfm_estimate_E_pipelined", "sfm_pair_flush", "sfm_ransac_export_key", "sfm_pose_candidates", "sfm_choose_pose", "sfm_triangulate", "sfm_pose_chain",
@@ -108,6 +108,11 @@ class RansacParams(C.Structure):
 class MatchGuidedParams(C.Structure):
     """sfm_match_guided_params (include/sfm_amd.h)."""
     _fields_ = [("band_px", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+class MatchGuidedJob(C.Structure):
+    """sfm_match_guided_job (include/sfm_amd.h)."""
+    _fields_ = [("d_sift1", C.c_void_p), ("n1", C.c_int32), ("d_sift2", C.c_void_p), ("n2", C.c_int32), ("d_F", C.c_void_p)]
 
 
 class RefineParams(C.Structure):
@@ -360,6 +365,7 @@ _lib.sfm_match_soa.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int
 _lib.sfm_match_guided_default_params.argtypes = [C.POINTER(MatchGuidedParams)]
 _lib.sfm_match_guided_default_params.restype = None
 _lib.sfm_match_guided.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.POINTER(MatchGuidedParams)]
+_lib.sfm_match_guided_pairs.argtypes = [_vp, C.POINTER(MatchGuidedJob), C.c_int, C.POINTER(MatchGuidedParams)]
 _lib.sfm_pair_fundamental.argtypes = [_vp, C.c_int, _vp]
 _lib.sfm_pair_fundamentals.argtypes = [C.POINTER(_vp), C.c_int, C.c_int, _vp]
 _lib.sfm_pair_create.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(_vp)]
@@ -510,6 +516,23 @@ def match_guided(ctx, d_sift1, n1, d_sift2, n2, d_F, **kw):
     p = match_guided_params(**kw)
     _check(_lib.sfm_match_guided(ctx._h if ctx is not None else None, _ptr(d_sift1), int(n1), _ptr(d_sift2), int(n2), _ptr(d_F), C.byref(p)),
            "sfm_match_guided")
+
+
+def match_guided_jobs(jobs):
+    """A ctypes array of sfm_match_guided_job from (d_sift1, n1, d_sift2, n2, d_F) tuples (tensors, addresses or None)."""
+    arr = (MatchGuidedJob * max(len(jobs), 1))()
+    for k, (s1, n1, s2, n2, f) in enumerate(jobs):
+        arr[k] = MatchGuidedJob(_ptr(s1), int(n1), _ptr(s2), int(n2), _ptr(f))
+    return arr
+
+
+def match_guided_pairs(ctx, jobs, **kw):
+    """sfm_match_guided_pairs (enqueue only): match_guided for every (d_sift1, n1, d_sift2, n2, d_F) of `jobs` in at most two
+    launches; job k's d_sift1 is left as match_guided(ctx, *jobs[k]) leaves it, bit for bit.  No job's d_sift1 may overlap
+    another job's buffers; kw: the fields of sfm_match_guided_params (band_px), one band for all jobs."""
+    p = match_guided_params(**kw)
+    _check(_lib.sfm_match_guided_pairs(ctx._h if ctx is not None else None, match_guided_jobs(jobs), len(jobs), C.byref(p)),
+           "sfm_match_guided_pairs")
 
 
 def pair_fundamentals(pairs, refined=True, out=None):

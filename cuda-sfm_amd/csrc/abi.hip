@@ -301,6 +301,7 @@ static int ctx_destroy_now(sfm_ctx *ctx)
     if (ctx->chain_ws) (void)hipFree(ctx->chain_ws);
     job_array_free(ctx->ring_jobs);
     job_array_free(ctx->fundamental_jobs);
+    job_array_free(ctx->guided_jobs);
     if (ctx->ring_ws) (void)hipFree(ctx->ring_ws);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     for (auto &t : ctx->tev) for (hipEvent_t e : t) if (e) (void)hipEventDestroy(e);

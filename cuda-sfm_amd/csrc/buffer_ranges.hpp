@@ -66,4 +66,34 @@ inline RangeConflict first_conflict_across_owners(std::vector<BufferRange> &r)
     return c;
 }
 
+// The same rule for a call whose owners MAY overlap themselves (sfm_match_guided_pairs: a job may match a set against itself,
+// as the single call may): no precondition.  The sweep keeps, among all ranges seen and among the outputs, the range that ends
+// last AND the one that ends last among the other owners' -- whichever owner x has, the farthest-reaching range of another owner
+// is one of the two, so a range of x's own owner in front never hides one behind it.
+inline RangeConflict first_conflict_across_overlapping_owners(std::vector<BufferRange> &r)
+{
+    r.erase(std::remove_if(r.begin(), r.end(), [](const BufferRange &x) { return !x.p || !x.bytes; }), r.end());
+    std::sort(r.begin(), r.end(), [](const BufferRange &x, const BufferRange &y) { return reinterpret_cast<uintptr_t>(x.p) < reinterpret_cast<uintptr_t>(y.p); });
+    auto end = [](const BufferRange &x) { return reinterpret_cast<uintptr_t>(x.p) + x.bytes; };
+    struct Far {
+        const BufferRange *first = nullptr, *other = nullptr;          // ends last; ends last among the owners that are not first's
+    };
+    auto keep = [&end](Far &f, const BufferRange &x) {
+        if (!f.first) { f.first = &x; return; }
+        if (x.owner == f.first->owner) { if (end(x) > end(*f.first)) f.first = &x; return; }
+        if (end(x) > end(*f.first)) { f.other = f.first; f.first = &x; return; }
+        if (!f.other || end(x) > end(*f.other)) f.other = &x;
+    };
+    RangeConflict c;
+    Far any, out;
+    for (const BufferRange &x : r) {
+        const Far &f = x.out ? any : out;
+        const BufferRange *hit = f.first && f.first->owner != x.owner ? f.first : f.other;
+        if (hit && hit->owner != x.owner && end(*hit) > reinterpret_cast<uintptr_t>(x.p)) { c.a = &x; c.b = hit; return c; }
+        keep(any, x);
+        if (x.out) keep(out, x);
+    }
+    return c;
+}
+
 } // namespace sfm

@@ -209,6 +209,7 @@ struct sfm_ctx {
     // sfm_close_ring: the RingLink (ring_math.hpp) of every link
     sfm::JobArray refine_jobs, register_jobs, view_points_jobs, adjust_jobs, align_jobs, fuse_jobs, chain_jobs, ring_jobs;
     sfm::JobArray fundamental_jobs;    // sfm_pair_fundamentals: the FundamentalJob (pair_fundamentals.hip) of every pair
+    sfm::JobArray guided_jobs;         // sfm_match_guided_pairs: the pinned staging of the launches' GuidedJob tables (match_guided_pairs.hip); the tables themselves sit in match_jobs_ws
     void *fuse_ws = nullptr;           // sfm_fuse_chain: per-node keys, successors, path lengths and classes, the block counts (fuse.hip)
     size_t fuse_ws_bytes = 0;
     void *chain_ws = nullptr;          // sfm_adjust_chain and sfm_adjust_ring: states, points, partial bands, the band and the segments (chain_adjust.hip); sfm_intersect_tracks: the list of long tracks

@@ -18,59 +18,12 @@
 // within 3 to 10 % of (2,8).
 //
 // The merge is the ticket merge only: no block ever waits for another one.
-#include "match_mfma.hpp"
-#include "match_guided_math.hpp"
+#include "match_guided_device.hpp"
 
 namespace sfm {
 
-struct GuidedRow { float x, y, lim, pad; };          // one staged database row's position and limit (16 bytes in LDS)
-
-// positions of the rows stage_load<W> requests (same clamped rows, unconditional loads)
-template <int W>
-__device__ __forceinline__ void stage_load_pos(const sfm_sift_point *__restrict__ sift2, int row0, int nrows, float2 (&pos)[16 / W])
-{
-    const int rr = threadIdx.x >> 4;
-#pragma unroll
-    for (int pass = 0; pass < 16 / W; ++pass) {
-        const int row = min(row0 + pass * (4 * W) + rr, nrows - 1);
-        pos[pass] = *reinterpret_cast<const float2 *>(&sift2[row].xpos);        // xpos, ypos: the record's first eight bytes
-    }
-}
-
-// (x2, y2, lim2) of the rows stage_store<W> writes; lim2 = 0 for rows past the end and under an F that is not finite.  Every
-// thread of a row's sixteen forms the value, the one that stages the row's first descriptor chunk stores it.
-template <int W>
-__device__ __forceinline__ void stage_store_pos(GuidedRow *side, const float2 (&pos)[16 / W], int row0, int nrows,
-                                                const float (&F)[9], const bool f_ok, const float band)
-{
-    const int c8 = threadIdx.x & 15;
-    const int rr = threadIdx.x >> 4;
-#pragma unroll
-    for (int pass = 0; pass < 16 / W; ++pass) {
-        const int slot = pass * (4 * W) + rr;
-        const bool real = row0 + slot < nrows;
-        float lt[3];
-        guided_line_t(F, pos[pass].x, pos[pass].y, lt);
-        const float lim2 = real && f_ok ? guided_limit(lt, band) : 0.0f;
-        if (c8 == 0) side[slot] = GuidedRow{ pos[pass].x, pos[pass].y, lim2, 0.0f };
-    }
-}
-
-// stage_scores' gate: the lane's lines and limits against the stage's rows
-template <int CT>
-struct EpipolarGate {
-    typedef GuidedRow Row;
-    const GuidedRow *side;
-    float l[CT][3], lim1[CT];
-    __device__ __forceinline__ Row row(int slot) const { return side[slot]; }
-    __device__ __forceinline__ float score(int ct, float s, const Row &r) const
-    {
-        return guided_pass(guided_residual(l[ct], r.x, r.y), lim1[ct], r.lim) ? s : -__builtin_inff();
-    }
-};
-
-// block (qblock, split) of grid (query blocks, database splits): match_body's schedule (match.hip) with the rows' positions
-// staged beside their descriptors
+// block (qblock, split) of grid (query blocks, database splits); the schedule is match_guided_body.inc, shared with the
+// many-matches kernel of match_guided_pairs.hip
 template <int CT, int W>
 __global__ __launch_bounds__(W * 64)
 void match_guided_kernel(sfm_sift_point *__restrict__ sift1, int nq, const sfm_sift_point *__restrict__ sift2, int ndb,
@@ -78,71 +31,8 @@ void match_guided_kernel(sfm_sift_point *__restrict__ sift1, int nq, const sfm_s
                          float *__restrict__ ws_best, float *__restrict__ ws_second, int *__restrict__ ws_idx,
                          unsigned int *__restrict__ tickets)
 {
-    __shared__ __attribute__((aligned(16))) float lds[2][kRowsPerStage * kLdsStride];
-    __shared__ __attribute__((aligned(16))) GuidedRow side[2][kRowsPerStage];
-    constexpr int ld = (int)(sizeof(sfm_sift_point) / sizeof(float));
-    const float *q = sift1->data;
-    const float *db = sift2->data;
     const int qblock = (int)blockIdx.x, split = (int)blockIdx.y, nsplit = (int)gridDim.y;
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int col = lane & 31;
-    const int half = lane >> 5;
-    const int q0 = qblock * (CT * 32 * W);
-    const int row_begin = split * rows_per_split;
-    const int row_end = min(ndb, row_begin + rows_per_split);
-
-    float F[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) F[i] = d_F[i];        // (a uniform address: scalar loads)
-    const bool f_ok = guided_finite(F);
-
-    // the first database stage is requested before the prologue, as in match_body
-    const int nstage = (row_end - row_begin + kRowsPerStage - 1) / kRowsPerStage;
-    float4 dbregs[16 / W][2];
-    float2 dbpos[16 / W];
-    if (nstage > 0) { stage_load<W>(db, ld, row_begin, row_end, dbregs); stage_load_pos<W>(sift2, row_begin, row_end, dbpos); }
-
-    // ---- prologue: the queries' lines and limits, then their resident fragments -------------------
-    EpipolarGate<CT> gate;
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-        const int p1 = q0 + (wave * CT + ct) * 32 + col;
-        const float2 u1 = *reinterpret_cast<const float2 *>(&sift1[min(p1, nq - 1)].xpos);
-        guided_line(F, u1.x, u1.y, gate.l[ct]);
-        gate.lim1[ct] = p1 < nq && f_ok ? guided_limit(gate.l[ct], band) : 0.0f;
-    }
-    float bq[CT][64];
-    load_queries<CT, W>(q, nq, ld, q0, lds, bq);
-
-    Top2 top[CT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) { top[ct].best = 0.0f; top[ct].second = 0.0f; top[ct].idx = -1; }
-
-    // ---- main loop over database stages of 64 rows ------------------------------------------
-    float4 regs[16 / W][2];
-    float2 pos[16 / W];
-    if (nstage > 0) { stage_store<W>(lds[0], dbregs, row_begin, row_end); stage_store_pos<W>(side[0], dbpos, row_begin, row_end, F, f_ok, band); }
-    __syncthreads();
-    for (int s = 0; s < nstage; ++s) {
-        const float *cur = lds[s & 1];
-        gate.side = side[s & 1];
-        const int next_row0 = row_begin + (s + 1) * kRowsPerStage;
-        if (s + 1 < nstage) { stage_load<W>(db, ld, next_row0, row_end, regs); stage_load_pos<W>(sift2, next_row0, row_end, pos); }
-
-        // a split is a multiple of 32 rows: its last stage may hold one row tile only (wave-uniform)
-        const int stage_row0 = row_begin + s * kRowsPerStage;
-        if (row_end - stage_row0 > 32) stage_scores<CT, 2>(cur, bq, top, stage_row0, gate);
-        else stage_scores<CT, 1>(cur, bq, top, stage_row0, gate);
-
-        if (s + 1 < nstage) { stage_store<W>(lds[(s + 1) & 1], regs, next_row0, row_end); stage_store_pos<W>(side[(s + 1) & 1], pos, next_row0, row_end, F, f_ok, band); }
-        __syncthreads();
-    }
-
-    // ---- the ticket merge into the records of sift1 ------------------------------------------
-    float *const out_best = nullptr, *const out_second = nullptr;
-    int *const out_idx = nullptr;
-#include "match_ticket_merge.inc"
+#include "match_guided_body.inc"
 }
 
 int launch_match_guided(sfm_ctx *ctx, sfm_sift_point *sift1, int n1, const sfm_sift_point *sift2, int n2, const float *d_F, float band_px)

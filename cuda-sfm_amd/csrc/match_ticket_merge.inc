@@ -1,5 +1,5 @@
 // match_ticket_merge.inc -- the ticket merge of the exact MFMA matchers, a fragment of a kernel body: included at the end of
-// match_body (match.hip) and of match_guided_kernel (match_guided.hip), which must have in scope
+// match_body (match.hip) and of match_guided_body.inc (the guided matcher's kernels), which must have in scope
 //   CT, W; top[CT]; wave, col, half; nq, q0, qblock, split, nsplit; ws_best, ws_second, ws_idx, tickets; out_best, out_second,
 //   out_idx (any of them null); sift1, sift2.
 // It merges the two k-parity halves of each column, emits the split's partial, and lets the LAST split block of this query block to

@@ -20,6 +20,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../../include/sfm_amd.h"
 
@@ -165,6 +166,45 @@ inline double MatchSiftDataGuided(SiftData &data1, SiftData &data2, const float 
     SFM_FACADE_CALL(sfm_ctx_timer_stop(ctx, &ms));
 #ifndef VERBOSE
     std::printf("MatchSiftDataGuided time =    %.2f ms\n", ms);
+#endif
+    return ms;
+}
+
+// Not part of the reference API: MatchSiftDataGuided for `count` pairs in ONE batched call (sfm_match_guided_pairs): pair i matches
+// *data1[i] against *data2[i] inside the band of the F at d_F_table + 9 i (what SfM::fundamentals of sfm.h returns).  Every
+// data1[i] is left as its own MatchSiftDataGuided leaves it; two pairs that share a first view need a copy of its records each.
+// Pairs with an empty or host-only set are skipped, as the single call skips them.
+inline double MatchSiftDataGuidedPairs(SiftData *const *data1, SiftData *const *data2, const float *d_F_table, int count, float band_px = 4.0f)
+{
+    sfm_ctx *ctx = sfm_facade::context();
+    std::vector<sfm_match_guided_job> jobs;
+    std::vector<SiftData *> firsts;
+    for (int i = 0; i < count; ++i) {
+        SiftData *a = data1[i], *b = data2[i];
+        if (!a || !b || !a->numPts || !b->numPts || a->d_data == nullptr || b->d_data == nullptr) continue;
+        sfm_match_guided_job j;
+        j.d_sift1 = a->d_data; j.n1 = a->numPts;
+        j.d_sift2 = b->d_data; j.n2 = b->numPts;
+        j.d_F = d_F_table + (size_t)9 * (size_t)i;
+        jobs.push_back(j);
+        firsts.push_back(a);
+    }
+    if (jobs.empty()) return 0.0;
+    sfm_match_guided_params p;
+    sfm_match_guided_default_params(&p);
+    p.band_px = band_px;
+    SFM_FACADE_CALL(sfm_ctx_timer_start(ctx));
+    SFM_FACADE_CALL(sfm_match_guided_pairs(ctx, jobs.data(), (int)jobs.size(), &p));
+    for (SiftData *a : firsts)
+        if (a->h_data != nullptr) {
+            float *h_ptr = &a->h_data[0].score;
+            const float *d_ptr = &a->d_data[0].score;        // address arithmetic only, never dereferenced on the host
+            SFM_FACADE_CALL(sfm_copy_to_host_2d(ctx, h_ptr, sizeof(SiftPoint), d_ptr, sizeof(SiftPoint), 5 * sizeof(float), (size_t)a->numPts));
+        }
+    float ms = 0.f;
+    SFM_FACADE_CALL(sfm_ctx_timer_stop(ctx, &ms));
+#ifndef VERBOSE
+    std::printf("MatchSiftDataGuidedPairs time = %.2f ms (%d pairs)\n", ms, (int)jobs.size());
 #endif
     return ms;
 }

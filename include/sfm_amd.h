@@ -168,6 +168,23 @@ int sfm_pair_fundamental(sfm_pair *pair, int refined, float *d_F);              
  * num_pairs == 0 is a no-op. */
 int sfm_pair_fundamentals(sfm_pair *const *pairs, int num_pairs, int refined,
                           float *d_F /* 9 * num_pairs device floats */);             /* enqueue only */
+/* sfm_match_guided for a list of jobs in at most two launches: job k leaves in its d_sift1 exactly what
+ * sfm_match_guided(ctx, d_sift1, n1, d_sift2, n2, d_F, p) leaves -- the five match fields bit for bit, every other byte of both
+ * record arrays untouched.  One band_px serves all jobs.  SFM_E_INVALID for null ctx, jobs or p, num_jobs < 0, a bad band_px or
+ * a non-zero reserved word, a job with a negative size, a job with a null pointer whose sizes are both positive, a job whose
+ * d_sift1 bytes overlap ANOTHER job's d_sift1, d_sift2 or d_F (two pairs that share a view each hold their own copy of the
+ * records they write; within one job the single call's rules hold), and a plan beyond the launch limits (more than 2^31 - 1
+ * (job, query block, split) units in a launch, byte counts beyond size_t).  All checks precede the first enqueue and the first
+ * device allocation: nothing is written on a refusal.  No C++ exception leaves the call; a failed allocation is SFM_E_NOMEM.
+ * num_jobs == 0 is a no-op, and so is a job with n1 == 0 or n2 == 0 inside a list that otherwise runs.  The quirk flags and
+ * sfm_ctx_set_match_kernel do not apply; sfm_ctx_last_match_kernel keeps its value. */
+typedef struct sfm_match_guided_job {
+    sfm_sift_point       *d_sift1; int32_t n1;   /* updated in place, as sfm_match_guided does */
+    const sfm_sift_point *d_sift2; int32_t n2;
+    const float          *d_F;                   /* 9 device floats, e.g. sfm_pair_fundamentals' d_F + 9 i */
+} sfm_match_guided_job;
+int sfm_match_guided_pairs(sfm_ctx *ctx, const sfm_match_guided_job *jobs, int num_jobs,
+                           const sfm_match_guided_params *p);      /* enqueue only */
 
 /* ---- SIFT extraction: ExtractSift (CudaSift/cudaSiftH.cu:72-232; cudaSift.h:37-39) ---------------------
  * d_image: height x pitch floats on the device (8-bit grey values as float, what CudaImage::Download
